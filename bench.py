@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the STC-GNN hot path on MI355X: BASELINE.json's metric on BASELINE.json's config.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 either comes in already launched by ``torch.distributed.run`` (one rank per GPU, RANK / WORLD_SIZE in
 the environment) or -- plain ``python bench.py --gpus N`` -- launches itself that way: before anything
@@ -15,7 +15,15 @@ bucket (N > 1) and the Adam update.  Workload: 224x224 row-stocha
 T = 18 observed + 6 predicted steps, Bernoulli(0.1635) inputs, batch per GPU fixed (weak scaling:
 the batch x time-window dimension is sharded, the graph replicated, no data-path collective).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes its outputs (``--dump-outputs``) and prints
+the contract fields (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` and the run's configuration).
+
+``--dump-outputs DIR`` writes what the last timed step computed, as float32 ``DIR/<name>.npy``: ``loss``, ``prediction`` (the model's
+output), ``param.<name>`` (the parameters after the step's optimizer update) and ``grad.<name>`` (their gradients); a tensor of more than
+2^20 values is written as a fixed seeded sample of 2^20 of its flat elements.  The inputs are seeded, so the same arguments give the same
+inputs in every run.
+
+``--full`` adds everything else the bench measures (the plain run does none of it): besides the contract fields the line then carries
   roofline      the PLAIN aggregation launch Y = S.X of the train step (entry point stc_patch_spmm_f32, device kernel
                 spmm_patch_kernel; stc_bcsr_spmm_* / spmm_bcsr_kernel for bf16 storage and graphs without a patch plan):
                 SURVEY 8(d3)'s algorithmic bytes nnz*(4+4) + 4*(N+1) + 2*B*N*F*4 per launch / its mean
@@ -31,6 +39,9 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   kernels       time share of every C-ABI entry point: the priced ones (plain aggregation, dominant cell kernels) over the timed steps, the
                 rest from two further steps with every launch timed, scaled to the step count
   cpu_baseline  the CPU oracle (oracle/stc_oracle.py) on a bounded sample: 2 warm-up + 7 timed shots, median
+
+``--full`` also runs the timed steps with HIP events around the priced launches and, on one GPU, the side measurements
+(``alt_formats`` / ``value_fp32_grade``, ``permuted``, ``power``) and the ``presets`` block.
 
 ``--preset cfg4 | cfg5 | sf`` selects BASELINE.json's other configurations (same schema, not the metric); ``--preset cfg2`` times the single
 BDG_Dif layer of configuration 2.  ``--global-batch G`` fixes the total batch (strong scaling: G / N samples per GPU).
@@ -93,6 +104,11 @@ def parse(argv=None):
                     help='(one GPU; not the default line) time replays of the train step captured into a HIP graph: removes the launch gaps that '
                          'matter at small N; the per-kernel events then come from eager steps after the timed region')
     ap.add_argument('--eager', dest='hip_graph', action='store_false', help='per-launch dispatch where a preset defaults to HIP-graph replay (--preset sf)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline: launch events, roofline, kernel table, step breakdown, power, CPU baseline, side '
+                         'measurements, SURVEY 8(d3) unit, presets block (the --no-* flags switch parts of it off); off = the plain timed run')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's results (loss, prediction, parameters, gradients) as float32 DIR/<name>.npy, at most 64 MB")
     ap.add_argument('--storage', choices=('f32', 'bf16'), default='f32',
                     help='storage type of states / gates / their gradients: f32 = the metric (reference arithmetic); bf16 = BASELINE configuration 5 '
                          '(not the metric: bf16 has no reference behaviour), fp32 parameters and fp32 sums inside every kernel')
@@ -138,6 +154,37 @@ def self_launch(a) -> int:
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={a.gpus}',
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
     return subprocess.call(cmd, env=env)
+
+
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: values per tensor beyond which a fixed seeded sample of its flat elements is written
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(model, pred, loss):
+    """What a caller of the train step receives: its loss and prediction, the parameters after the update and their gradients."""
+    return ([('loss', loss.reshape(1)), ('prediction', pred)] + [('param.' + n, p) for n, p in model.named_parameters()]
+            + [('grad.' + n, p.grad) for n, p in model.named_parameters() if p.grad is not None])
+
+
+def dump_outputs(out_dir, tensors):
+    """--dump-outputs: each (name, tensor) as ``out_dir/<name>.npy``, float32 (float64 stays float64)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays, total = {}, 0
+    for name, t in tensors:
+        t = t.detach()
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            flat = flat.index_select(0, idx.to(flat.device))
+        flat = flat.double() if t.dtype == torch.float64 else flat.float()
+        arrays[name] = flat.cpu().numpy().reshape(flat.shape if t.numel() > DUMP_SAMPLE else t.shape)
+        total += arrays[name].nbytes
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'--dump-outputs: {total / 2**20:.1f} MB of outputs, more than the {DUMP_LIMIT_BYTES >> 20} MB allowed')
+    import numpy as np
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), arr)
 
 
 def _median(xs):
@@ -500,7 +547,7 @@ def run_presets(parent_reserved_gb, steps=3, timeout_s=150):
     """BASELINE.json's other configurations for the default line: each ``--preset`` as a CHILD process of this bench (3 timed steps, 1 warm-up, HIP-graph
     replays where the preset defaults to them, no CPU baseline), one after the other, after the metric's own measurements; the digest of each child's line.
     Never re-execs this process (it has touched the GPU); a child that fails or overruns leaves an ``error`` entry instead of ending the line."""
-    digest = {'what': f'python bench.py --preset <name> --steps {steps} --warmup 1 --no-cpu-baseline --no-unit-d3, one child process each, run after the timed region '
+    digest = {'what': f'python bench.py --preset <name> --steps {steps} --warmup 1 --full --no-cpu-baseline --no-unit-d3, one child process each, run after the timed region '
                       'of the metric (its memory handed back first); not the metric -- the full lines of builder runs are profiles/rNN/preset_*.json',
               'parent_reserved_gb_while_they_ran': parent_reserved_gb}
     if parent_reserved_gb > 60.0:
@@ -515,7 +562,7 @@ def run_presets(parent_reserved_gb, steps=3, timeout_s=150):
             continue
         t0 = time.perf_counter()
         try:
-            res = subprocess.run([sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(steps), '--warmup', '1', '--no-cpu-baseline',
+            res = subprocess.run([sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(steps), '--warmup', '1', '--full', '--no-cpu-baseline',
                                   '--no-unit-d3'] + flags, env=env, capture_output=True, text=True, timeout=timeout_s)
             lines = [ln for ln in res.stdout.strip().split('\n') if ln.startswith('{')]
             if res.returncode != 0 or not lines:
@@ -570,7 +617,7 @@ def main():
     learned = a.graph_mode == 'dense-learned'
     model = M.STCGNN(N, C, a.order, a.order, 1, a.hidden, a.layers, a.pred, graph_mode=a.graph_mode, reorder_nodes=not a.no_reorder,
                      storage_dtype=torch.bfloat16 if a.storage == 'bf16' else torch.float32)
-    sd_cpu = None if a.no_cpu_baseline else {k: v.clone() for k, v in model.state_dict().items()}
+    sd_cpu = None if (a.no_cpu_baseline or not a.full) else {k: v.clone() for k, v in model.state_dict().items()}
     model = model.to(dev)
     Gc = Gc_cpu.to(dev)
     # learned graphs: MGP_Gen takes the raw adjacencies (the reference's Main.py hands it the 0/1 grid adjacency and a category matrix)
@@ -588,13 +635,18 @@ def main():
     opt = (StcAdam if learned else torch.optim.Adam)(model.parameters(), lr=2e-3, weight_decay=1e-4, capturable=graphed, **({'fused': True} if learned else {}))
     stream = torch.cuda.current_stream(dev)
     marks = []                                                                  # (t_begin, t_backward_done, t_allreduce_done, t_adam_done) events
+    kept = {}                                                                   # --dump-outputs: the prediction of the last timed step
 
-    def step(mark=False):
+    def step(mark=False, keep=False):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if mark else None
         if mark:
             ev[0].record(stream)
         bucket.zero()
-        loss = crit(model(X_seq=X, As=As_in, Ac=Gc), Y)
+        pred = model(X_seq=X, As=As_in, Ac=Gc)
+        if keep:
+            kept['prediction'] = pred
+        loss = crit(pred, Y)
+        del pred
         loss.backward()
         if mark:
             ev[1].record(stream)
@@ -625,57 +677,68 @@ def main():
         torch.cuda.empty_cache()                                     # the graph gets a memory pool of its own: hand the eager pool back first
         cg = torch.cuda.CUDAGraph()
         with torch.cuda.graph(cg):
-            step()
+            loss = step(keep=bool(a.dump_outputs))                   # (static tensors: after the replays they hold the last replay's results)
         cg.replay()
         fence()
-        sampler = PowerSampler(local)
-        sampler.start()
+        sampler = PowerSampler(local) if a.full else None
+        if sampler:
+            sampler.start()
         t0 = time.perf_counter()
         for _ in range(a.steps):
             cg.replay()
         fence()
         elapsed = time.perf_counter() - t0
-        power = sampler.stop()
+        power = sampler.stop() if sampler else None
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, step_outputs(model, kept['prediction'], loss))
+        kept.clear()
         del cg
         torch.cuda.empty_cache()
-        hip.timer = KernelTimer()
-        for _ in range(min(a.steps, 3)):
-            loss = step(mark=True)
-        fence()
-        per_kernel = hip.timer.summary()
-        for d_ in per_kernel.values():                               # scale the event sums to the step count of the line
-            for key in ('launches', 'ms', 'bytes'):
-                d_[key] = d_[key] * a.steps / min(a.steps, 3)
-                for t_ in d_.get('tags', {}).values():
-                    t_[key] = t_[key] * a.steps / min(a.steps, 3)
-        hip.timer = None
+        if a.full:
+            hip.timer = KernelTimer()
+            for _ in range(min(a.steps, 3)):
+                loss = step(mark=True)
+            fence()
+            per_kernel = hip.timer.summary()
+            for d_ in per_kernel.values():                           # scale the event sums to the step count of the line
+                for key in ('launches', 'ms', 'bytes'):
+                    d_[key] = d_[key] * a.steps / min(a.steps, 3)
+                    for t_ in d_.get('tags', {}).values():
+                        t_[key] = t_[key] * a.steps / min(a.steps, 3)
+            hip.timer = None
     else:
-        # timed region: HIP events around the launches the roofline block prices (the plain aggregation and the dominant cell kernels), not
+        # timed region (--full): HIP events around the launches the roofline block prices (the plain aggregation and the dominant cell kernels), not
         # around all ~700 launches of a step -- 1 400 event records per step cost 2 ms of the 174; the complete per-kernel table comes
-        # from two further steps with every launch timed, scaled to the step count (the priced entry points keep their timed-region numbers)
-        hip.timer = KernelTimer(only=PRICED_ENTRY_POINTS)
-        sampler = PowerSampler(local)
-        sampler.start()
+        # from two further steps with every launch timed, scaled to the step count (the priced entry points keep their timed-region numbers).
+        # A plain run times the bare steps.
+        hip.timer = KernelTimer(only=PRICED_ENTRY_POINTS) if a.full else None
+        sampler = PowerSampler(local) if a.full else None
+        if sampler:
+            sampler.start()
         t0 = time.perf_counter()
-        for _ in range(a.steps):
-            loss = step(mark=True)
+        for i in range(a.steps):
+            loss = step(mark=a.full, keep=bool(a.dump_outputs) and i == a.steps - 1)
         fence()
         elapsed = time.perf_counter() - t0
-        power = sampler.stop()
-        priced = hip.timer.summary()
-        hip.timer = KernelTimer()
-        table_steps = min(a.steps, 2)
-        for _ in range(table_steps):
-            step()
-        fence()
-        per_kernel = hip.timer.summary()
-        hip.timer = None
-        for d_ in per_kernel.values():
-            for key in ('launches', 'ms', 'bytes'):
-                d_[key] = d_[key] * a.steps / table_steps
-                for t_ in d_.get('tags', {}).values():
-                    t_[key] = t_[key] * a.steps / table_steps
-        per_kernel.update(priced)
+        power = sampler.stop() if sampler else None
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, step_outputs(model, kept['prediction'], loss))
+        kept.clear()
+        if a.full:
+            priced = hip.timer.summary()
+            hip.timer = KernelTimer()
+            table_steps = min(a.steps, 2)
+            for _ in range(table_steps):
+                step()
+            fence()
+            per_kernel = hip.timer.summary()
+            hip.timer = None
+            for d_ in per_kernel.values():
+                for key in ('launches', 'ms', 'bytes'):
+                    d_[key] = d_[key] * a.steps / table_steps
+                    for t_ in d_.get('tags', {}).values():
+                        t_[key] = t_[key] * a.steps / table_steps
+            per_kernel.update(priced)
     n_ranks_seen = 1
     per_rank = {'ms_per_step': [1e3 * elapsed / a.steps], 'build_s': [t_built - t_start], 'warmup_s': [t_warm - t_built]}
     if dist.is_initialized():
@@ -692,21 +755,22 @@ def main():
         n_ranks_seen = int(ones.item())
     phases = [sum(ev[i].elapsed_time(ev[i + 1]) for ev in marks) / max(1, len(marks)) for i in range(3)]
 
-    # the same step with the per-launch event records off: what the instrumentation of the timed region costs
+    # the same step with the per-launch event records off: what the instrumentation of the timed region costs (--full)
     untimed_steps = min(a.steps, 3)
-    fence()
-    t1 = time.perf_counter()
-    for _ in range(untimed_steps):
-        step()
-    fence()
-    untimed_ms = 1e3 * (time.perf_counter() - t1) / max(1, untimed_steps)
+    if a.full:
+        fence()
+        t1 = time.perf_counter()
+        for _ in range(untimed_steps):
+            step()
+        fence()
+        untimed_ms = 1e3 * (time.perf_counter() - t1) / max(1, untimed_steps)
 
-    # Side measurements of the metric line (one GPU, default configuration): what used to exist as builder-run numbers only.
+    # Side measurements of the metric line (--full, one GPU, default configuration): what used to exist as builder-run numbers only.
     #   alt_formats.bf16x3   the same step on the 24-bit operand format (three bf16 pieces, six products; the default keeps 22 bits)
     #   permuted             SURVEY 8(d1) variant B: the same graph under a seeded random node order (the host renumbers it: reverse
     #                        Cuthill-McKee, then greedy clusters for the patch form), with the rate of its plain aggregation launches
     extras = {}
-    if rank == 0 and world == 1 and not graphed and not a.no_extras and a.preset is None and not learned and a.storage == 'f32':
+    if a.full and rank == 0 and world == 1 and not graphed and not a.no_extras and a.preset is None and not learned and a.storage == 'f32':
         from stc_hip import _lib as _l
 
         def side(model_, As_, n=3):
@@ -762,7 +826,7 @@ def main():
                                       patch_stats={k: list(v) for k, v in getattr(used, 'patch_stats', {}).items()})
             del model_p, graph_p
 
-    if rank == 0:
+    if rank == 0 and a.full:
         total_ms = sum(d['ms'] for d in per_kernel.values()) or 1.0
 
         def gather(names, tag=None):
@@ -871,6 +935,7 @@ def main():
         if not a.no_unit_d3:
             roofline['unit_d3'] = spmm_unit_d3(graph, dev, C, 2 * a.hidden, torch.bfloat16 if a.storage == 'bf16' else torch.float32,
                                                reorder=not a.no_reorder)
+    if rank == 0:
         value = world * B * a.steps / elapsed
         out = {
             'metric': METRIC, 'value': value, 'unit': 'samples/s',
@@ -890,22 +955,28 @@ def main():
                        **({'preset': a.preset} if a.preset else {}),
                        'operand_format': {0: 'bf16x3', 1: 'f16x2'}.get(getattr(hip, 'operand_format', None)),
                        'grad_bucket_bytes': bucket.nbytes, 'grad_large_bytes': bucket.large_nbytes, 'input_seeds': 'X, Y: Bernoulli(0.1635), torch seed 1000 + rank'},
-            'roofline': roofline,
-            'power': power,
-            'step_breakdown': {'fwd_loss_bwd_ms': phases[0], 'grad_allreduce_ms': phases[1], 'adam_ms': phases[2],
-                               'samples_per_s_excluding_optimizer': world * B / ((phases[0] + phases[1]) / 1e3) if phases[0] > 0 else None,
-                               'ms_per_step_without_launch_events': untimed_ms,
-                               'note': 'value / ms_per_step are the whole step (Adam included) with two HIP-event records around every PRICED launch (the plain aggregation and the dominant cell kernels); '
-                                       'the phases are HIP events on the compute stream of rank 0; ms_per_step_without_launch_events re-times '
-                                       f'{untimed_steps} steps with the launch timer off'},
-            **extras,
-            'kernels': {k: {'launches': d['launches'], 'ms_per_step': d['ms'] / a.steps, 'share': d['ms'] / total_ms,
-                            **({'GBps': d['bytes'] / 1e9 / (d['ms'] / 1e3)} if d['bytes'] and d['ms'] > 0 else {})}
-                        for k, d in sorted(per_kernel.items(), key=lambda kv: -kv[1]['ms'])},
+        }
+        if a.full:
+            out.update({
+                'roofline': roofline,
+                'power': power,
+                'step_breakdown': {'fwd_loss_bwd_ms': phases[0], 'grad_allreduce_ms': phases[1], 'adam_ms': phases[2],
+                                   'samples_per_s_excluding_optimizer': world * B / ((phases[0] + phases[1]) / 1e3) if phases[0] > 0 else None,
+                                   'ms_per_step_without_launch_events': untimed_ms,
+                                   'note': 'value / ms_per_step are the whole step (Adam included) with two HIP-event records around every PRICED launch (the plain aggregation and the dominant cell kernels); '
+                                           'the phases are HIP events on the compute stream of rank 0; ms_per_step_without_launch_events re-times '
+                                           f'{untimed_steps} steps with the launch timer off'},
+                **extras,
+                'kernels': {k: {'launches': d['launches'], 'ms_per_step': d['ms'] / a.steps, 'share': d['ms'] / total_ms,
+                                **({'GBps': d['bytes'] / 1e9 / (d['ms'] / 1e3)} if d['bytes'] and d['ms'] > 0 else {})}
+                            for k, d in sorted(per_kernel.items(), key=lambda kv: -kv[1]['ms'])},
+            })
+        out.update({
             'loss': float(loss.detach()),
             'hbm_peak_allocated_gb': torch.cuda.max_memory_allocated(dev) / 1e9,
             'hbm_peak_reserved_gb': torch.cuda.max_memory_reserved(dev) / 1e9,
-        }
+            'full': bool(a.full),
+        })
         fmt_name = out['config']['operand_format']
         if 'alt_formats' in extras:
             g24 = extras['alt_formats']['bf16x3']
@@ -919,13 +990,13 @@ def main():
         out['dtype_detail'] = ('bf16 state storage, fp32 parameters and sums' if a.storage == 'bf16' else
                                'fp32 planes, parameters and sums; aggregations in fp32 fmaf; matrix-core products on fp32 operands split as '
                                + {'f16x2': 'two fp16 pieces (22 significant bits)', 'bf16x3': 'three bf16 pieces (24 significant bits)'}.get(fmt_name, str(fmt_name)))
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             if N <= 1024:                                        # small graphs: the whole model through the oracle's dense (reference) algorithm
                 out['cpu_baseline'] = cpu_baseline_small(a, graph.to_dense(), Gc_cpu, sd_cpu,
                                                          As_dense=CsrGraph.queen_grid(a.grid, a.grid, normalize=False).to_dense() if learned else None)
             else:
                 out['cpu_baseline'] = cpu_baseline(a, _sparse_T(graph), Gc_cpu, sd_cpu)
-        if world == 1 and a.preset is None and not (a.no_presets or a.no_extras or graphed or learned or a.permute) and a.storage == 'f32':
+        if a.full and world == 1 and a.preset is None and not (a.no_presets or a.no_extras or graphed or learned or a.permute) and a.storage == 'f32':
             # BASELINE.json's other configurations in the same line: the metric's memory goes back first (a preset is a process of its own)
             del loss
             model.zero_grad(set_to_none=True)
@@ -1001,9 +1072,12 @@ def bench_cfg2(a):
             ms_f, ms_fb = timed(capture(fwd)), timed(capture(fwd_bwd))
         except RuntimeError as e:                                  # (something on the path synchronised with the host: the eager numbers stand)
             graphed, eager['capture_error'] = False, str(e).split('\n')[0][:200]
+    if a.dump_outputs:                                           # the layer's output and the gradients of the last forward + backward
+        dump_outputs(a.dump_outputs, [('output', fwd()), ('grad.X', X.grad), ('grad.Gs', Gs.grad), ('grad.Gc', Gc.grad)]
+                     + [('grad.' + n, p.grad) for n, p in layer.named_parameters()])
     ref = {2: (13.3, 25.8), 3: (29.6, 55.2)}.get(K)
     cpu = None
-    if not a.no_cpu_baseline:                                    # the oracle's bdg_dif (the reference's algorithm op for op) on the host cores
+    if a.full and not a.no_cpu_baseline:                         # the oracle's bdg_dif (the reference's algorithm op for op) on the host cores
         from oracle import stc_oracle as O
         threads = min(os.cpu_count() or 1, 32)
         torch.set_num_threads(threads)

@@ -28,6 +28,8 @@ stored, only numbers.  Sets follow SURVEY.md section 8(c4):
   g15_sf_shape_k3   the same at K=3 (the small-graph cell kernels' order-3 form: T_2(S) as a second graph)
   g8b_large_n10000_grads   g8 with backward: sampled rows of Ht, dXt, dHt + the full parameter gradients
   g8c_large_n10000_k3      the same cell at Chebyshev order K = 3 (BASELINE configuration 4) through the dense reference, with backward
+  g16_live_cells    one STC_Cell per seed at small random shapes (inputs, parameters, output): test_oracle_golden's random-shape cases
+  sf_incidents_4h   the SF-incidents data file's arrays (incident series, mask, thresholds, s_adj, c_cor): the data-file tests
 
 Large inputs (g7, g8) are regenerated from seeds by ``synth_inputs`` below,
 which the tests import too; a few checksums are stored to catch RNG drift.
@@ -518,8 +520,42 @@ def metrics_golden(ref_framework='/root/reference/framework'):
     _save('g10_metrics', **out)
 
 
+def live_cell_shapes(seed):
+    """The random STC_Cell shape of seed ``seed`` (test_oracle_golden's random-shape cases): B, N, C, cin, h, K."""
+    g = torch.Generator().manual_seed(1000 + seed)
+    return tuple(int(torch.randint(lo, hi, (1,), generator=g)) for lo, hi in ((1, 4), (2, 20), (1, 7), (1, 5), (1, 9), (1, 5)))
+
+
+def live_cells_golden(ref_framework):
+    """g16: one reference STC_Cell per seed 0..5 at the random shapes of ``live_cell_shapes`` -- inputs, parameters and output."""
+    sys.path.insert(0, ref_framework)
+    import STC_GNN as ref
+    out = {}
+    for seed in range(6):
+        B, N, C, cin, h, K = live_cell_shapes(seed)
+        torch.manual_seed(seed)
+        cell = ref.STC_Cell(N, C, K, K, cin, h)
+        Xt, Ht = torch.randn(B, N, C, cin), torch.randn(B, N, C, h)
+        Gs, Gc = torch.randn(N, N) * 0.2, torch.randn(C, C) * 0.3
+        with torch.no_grad():
+            want = cell(Gs, Gc, Xt, Ht)
+        for k, v in dict(Xt=Xt, Ht=Ht, Gs=Gs, Gc=Gc, gW=cell.gates.W, gb=cell.gates.b, cW=cell.candi.W, cb=cell.candi.b, H=want).items():
+            out[f's{seed}/{k}'] = v
+    _save('g16_live_cells', **out)
+
+
+def sf_data_golden(data_dir):
+    """sf_incidents_4h: the arrays of the SF-incidents file that ``stc_hip.data.load_incidents`` reads (``metadata`` left out)."""
+    with np.load(os.path.join(data_dir, 'SF-incidents-4h.npz')) as z:
+        _save('sf_incidents_4h', **{k: z[k] for k in ('incident', 'mask', 'threshold', 's_adj', 'c_cor')})
+
+
 if __name__ == '__main__':
-    if len(sys.argv) > 1 and sys.argv[1] == 'metrics':
+    if len(sys.argv) > 2 and sys.argv[1] == 'live_cells':         # make_golden.py live_cells <reference framework directory>
+        live_cells_golden(sys.argv[2])
+    elif len(sys.argv) > 2 and sys.argv[1] == 'sf_data':          # make_golden.py sf_data <directory of SF-incidents-4h.npz>
+        sf_data_golden(sys.argv[2])
+    elif len(sys.argv) > 1 and sys.argv[1] == 'metrics':
         metrics_golden()
     elif len(sys.argv) > 1 and sys.argv[1] == 'pipeline':
         pipeline_golden()

@@ -117,7 +117,41 @@ def test_presets_block_runs_children_and_survives_their_failures(monkeypatch):
     d = bench.run_presets(0.5)
     assert [c[c.index('--preset') + 1] for c, _ in seen] == ['cfg2', 'cfg2', 'cfg4', 'cfg5', 'sf', 'sf-learned']
     assert all('RANK' not in e and c[0] == sys.executable and '--no-cpu-baseline' in c and c[c.index('--steps') + 1] == '3' for c, e in seen)
+    assert all('--full' in c for c, _ in seen)                          # the digest reads the roofline block: children run the full line
     assert d['cfg2']['value'] == 7.0 and d['cfg2']['roofline']['dominant'] == {'entry_point': 'e', 'frac': 0.4} and d['sf-learned']['roofline']['frac'] == 0.5
     assert 'boom' in d['cfg4']['error'] and 'no line within' in d['cfg5']['error'] and 'exit code 0' in d['sf']['error']
     seen.clear()
     assert 'error' in bench.run_presets(140.0) and not seen
+
+
+def test_plain_run_by_default_full_and_dump_outputs_opt_in():
+    a = bench.parse(['--gpus', '1', '--steps', '4', '--warmup', '2'])
+    assert a.full is False and a.dump_outputs is None and a.steps == 4 and a.warmup == 2
+    a = bench.parse(['--full', '--dump-outputs', 'out'])
+    assert a.full is True and a.dump_outputs == 'out'
+
+
+def test_dump_outputs_float32_files_and_a_fixed_sample_of_large_tensors(tmp_path, monkeypatch):
+    """``--dump-outputs``: loss, prediction, parameters and gradients as float32 .npy (float64 kept); a tensor above DUMP_SAMPLE values is the same
+    seeded sample of its flat elements in every run; more than DUMP_LIMIT_BYTES in all is an error, not a partial dump."""
+    import numpy as np
+    import torch
+    model = torch.nn.Linear(3, 2)
+    model(torch.ones(4, 3)).sum().backward()
+    pred = torch.arange(bench.DUMP_SAMPLE + 7, dtype=torch.bfloat16).reshape(-1, 1)
+    loss = torch.tensor(0.5, dtype=torch.float64)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), bench.step_outputs(model, pred, loss))
+    names = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert names == ['grad.bias.npy', 'grad.weight.npy', 'loss.npy', 'param.bias.npy', 'param.weight.npy', 'prediction.npy']
+    w = np.load(tmp_path / 'a' / 'param.weight.npy')
+    assert w.dtype == np.float32 and np.array_equal(w, model.weight.detach().numpy())
+    assert np.array_equal(np.load(tmp_path / 'a' / 'grad.bias.npy'), model.bias.grad.numpy())
+    assert np.load(tmp_path / 'a' / 'loss.npy').dtype == np.float64
+    p = np.load(tmp_path / 'a' / 'prediction.npy')
+    assert p.dtype == np.float32 and p.shape == (bench.DUMP_SAMPLE,) and np.array_equal(p, np.load(tmp_path / 'b' / 'prediction.npy'))
+    assert np.all(np.diff(p) >= 0) and set(p.tolist()) <= set(pred.float().reshape(-1).tolist())
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 1024)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / 'c'), bench.step_outputs(model, pred, loss))
+    assert not (tmp_path / 'c').exists() or not any((tmp_path / 'c').iterdir())

@@ -17,7 +17,7 @@ from stc_hip.trainer import Trainer
 from tests.conftest import REPO, load_golden, sub_dict
 from tests.golden.make_golden import pipeline_inputs
 
-SF = '/root/reference/data/SF-incidents-4h.npz'
+SF = os.path.join(REPO, 'tests', 'golden', 'sf_incidents_4h.npz')      # the SF-incidents file's arrays (make_golden.py sf_data)
 
 
 @pytest.mark.parametrize('device', ['cpu', pytest.param('cuda:0', marks=pytest.mark.gpu)])
@@ -51,7 +51,6 @@ def test_sliding_windows_are_views_and_edge_cases():
     assert sdata.split_lengths(7, [1, 3, 3]) == {'validate': 3, 'test': 3, 'train': 1}
 
 
-@pytest.mark.skipif(not os.path.exists(SF), reason='SF data file not present')
 def test_sf_file_counts():
     data = sdata.load_incidents(SF)
     assert data['inc'].shape == (5124, 10, 10, 5) and data['s_adj'].shape == (100, 100) and data['c_cor'].shape == (5, 5)
@@ -190,7 +189,7 @@ def _run_bench(extra, env=None, timeout=900):
     import json
     import subprocess
     import sys
-    cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '2', '--warmup', '1', '--batch-per-gpu', '2', '--obs', '3', '--pred', '2'] + extra
+    cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--steps', '2', '--warmup', '1', '--batch-per-gpu', '2', '--obs', '3', '--pred', '2'] + extra
     if '--presets' in cmd:
         cmd.remove('--presets')
     else:
@@ -247,6 +246,34 @@ def test_bench_line_contract(storage):
 
 
 @pytest.mark.gpu
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run (no --full) prints the contract fields and nothing it would need further runs for; ``--dump-outputs`` writes the last
+    timed step's loss, prediction, parameters and gradients, and two runs with the same arguments start from the same inputs."""
+    import json
+    import subprocess
+    import sys
+    got = {}
+    for run in ('a', 'b'):
+        cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--grid', '12', '--batch-per-gpu', '2',
+               '--obs', '3', '--pred', '2', '--dump-outputs', str(tmp_path / run)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.strip().split('\n') if l.startswith('{')]
+        assert len(lines) == 1, out.stdout[-2000:]
+        got[run] = json.loads(lines[0])
+    d = got['a']
+    assert d['full'] is False and d['steps'] == 3 and d['warmup'] == 1 and d['unit'] == 'samples/s' and d['higher_is_better'] is True and d['dtype'] == 'f32'
+    assert abs(d['value'] - 2 * 1e3 / d['ms_per_step']) < 1e-6 * d['value']
+    assert not {'roofline', 'step_breakdown', 'kernels', 'power', 'cpu_baseline', 'alt_formats', 'permuted', 'presets'} & set(d)
+    files = {p.name: np.load(p) for p in (tmp_path / 'a').iterdir()}
+    assert {'loss.npy', 'prediction.npy'} <= set(files) and any(n.startswith('param.') for n in files) and any(n.startswith('grad.') for n in files)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in files.values())
+    assert files['prediction.npy'].shape == (2, 2, 144, 32) and abs(float(files['loss.npy'][0]) - d['loss']) < 1e-6
+    for name, v in files.items():
+        assert np.allclose(v, np.load(tmp_path / 'b' / name), rtol=1e-5, atol=1e-6), name
+
+
+@pytest.mark.gpu
 def test_bench_presets_block_and_fp32_grade_value():
     """The default one-GPU line carries (a) ``value_fp32_grade``: the same step on the 24-bit operand format over the SAME --steps as ``value``, and
     (b) ``presets``: BASELINE.json's other configurations, each a child process run after the metric's measurements (here two of them, by name)."""
@@ -273,7 +300,7 @@ def test_bench_launches_its_own_ranks():
     import json
     import subprocess
     import sys
-    cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--grid', '32', '--batch-per-gpu', '2',
+    cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--grid', '32', '--batch-per-gpu', '2',
            '--obs', '3', '--pred', '2']
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env={**env, 'STC_DIST_BACKEND': 'gloo', 'STC_DIST_ONE_DEVICE': '1'})
     assert out.returncode == 0, out.stderr[-3000:]
@@ -296,7 +323,7 @@ def test_bench_many_ranks_contract():
     import subprocess
     import sys
     n = 4
-    cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', str(n), '--steps', '3', '--warmup', '1', '--grid', '32', '--batch-per-gpu', '2',
+    cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--gpus', str(n), '--steps', '3', '--warmup', '1', '--grid', '32', '--batch-per-gpu', '2',
            '--obs', '3', '--pred', '2']
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env={**env, 'STC_DIST_BACKEND': 'gloo', 'STC_DIST_ONE_DEVICE': '1'})
     assert out.returncode == 0, out.stderr[-3000:]
@@ -330,7 +357,7 @@ def test_bench_two_ranks_over_rccl():
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT', 'STC_DIST_BACKEND', 'STC_DIST_ONE_DEVICE')}
-    base = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--grid', '32', '--obs', '3', '--pred', '2']
+    base = [sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--grid', '32', '--obs', '3', '--pred', '2']
     got = {}
     for name, extra, e in (('rccl', ['--batch-per-gpu', '2'], env), ('gloo', ['--batch-per-gpu', '2'], {**env, 'STC_DIST_BACKEND': 'gloo'}),
                            ('strong', ['--global-batch', '4'], env)):
@@ -374,7 +401,7 @@ def test_bench_preset_cfg2(K):
     import json
     import subprocess
     import sys
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--preset', 'cfg2', '--order', str(K)], capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--preset', 'cfg2', '--order', str(K)], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.strip().split('\n') if l.startswith('{')][0])
     assert d['config']['preset'] == 'cfg2' and d['forward_ms'] > 0 and d['forward_backward_ms'] > 0      # (timings of a 0.1-1 ms launch: no ordering asserted)
@@ -389,7 +416,7 @@ def test_bench_preset_sf(preset):
     import json
     import subprocess
     import sys
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--preset', preset, '--steps', '3', '--warmup', '2', '--no-cpu-baseline'],
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--preset', preset, '--steps', '3', '--warmup', '2', '--no-cpu-baseline'],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.strip().split('\n') if l.startswith('{')][0])

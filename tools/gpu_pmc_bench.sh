@@ -4,6 +4,7 @@
 # with the hash of the kernel sources and the bench configuration it was collected on (bench.py quotes roofline.traffic
 # from the copy committed as profiles/rNN/hbm_traffic_bench.json (the newest round) only while both still match).
 set -u
+BENCH_ARGS="--full ${BENCH_ARGS:-}"        # the steps here read the --full line (roofline, kernel table) or profile its complete run
 R=${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p $R/gpurun_out && cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do

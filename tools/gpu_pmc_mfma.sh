@@ -3,6 +3,7 @@
 # trace domains besides --kernel-trace): per kernel  mfma_util = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs * 1024 SIMDs).
 # BENCH_ARGS selects the configuration; TAG names the output (gpurun_out/mfma_util_$TAG.json).
 set -u
+BENCH_ARGS="--full ${BENCH_ARGS:-}"        # the steps here read the --full line (roofline, kernel table) or profile its complete run
 R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${TAG:-f32}
 mkdir -p $R/gpurun_out && cd /tmp && export TMPDIR=/tmp

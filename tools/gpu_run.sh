@@ -10,6 +10,7 @@
 #   mfma             SQ / GRBM PMC passes (tools/gpu_pmc_mfma.sh) -> gpurun_out/mfma_util_f32.json
 # BENCH_ARGS is appended to every bench command.
 set -u
+BENCH_ARGS="--full ${BENCH_ARGS:-}"        # the steps here read the --full line (roofline, kernel table) or profile its complete run
 cd "${GRAFT_REPO_ROOT:-.}"; R=$PWD; mkdir -p gpurun_out
 for step in "$@"; do
   case "$step" in

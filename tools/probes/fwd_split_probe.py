@@ -4,7 +4,7 @@ for p in (REPO, os.path.join(REPO, 'stc-gnn_amd')):
     sys.path.insert(0, p)
 import stc_hip._lib as L
 L.HipKernels.SMALL_STAGED_ROWS = int(sys.argv[1])
-sys.argv = ['bench.py', '--preset', 'sf', '--steps', '20', '--warmup', '3', '--no-cpu-baseline']
+sys.argv = ['bench.py', '--full', '--preset', 'sf', '--steps', '20', '--warmup', '3', '--no-cpu-baseline']
 import bench
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
