@@ -36,7 +36,6 @@ class _Bf16Emulated:
     GPU tests bound)."""
 
     name = 'emulated-cpu-bf16'
-    folds_dH = True
 
     def __init__(self, em):
         self.em = em
@@ -585,9 +584,6 @@ class EmulatedKernels:
     # planar forms: the [Xt | H] rows as two (R, C, 16) planes -- emulated by concatenating them
     def cell_planar_supported(self, Ks, Kc, Cc, h) -> bool:
         return Ks == 2 and Kc == 2 and h == 16
-
-    def cell_planar_post_fused(self, Cc) -> bool:
-        return True
 
     def cell_gates_fwd_planar(self, X, H, SX, SH, Tc, W, bias, U, Rg, RH, post=None, act_amax=None):
         cin, h = X.shape[-1], H.shape[-1]                        # cin = h, or 1..4 (narrow input plane, layer 0)

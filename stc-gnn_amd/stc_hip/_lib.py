@@ -237,8 +237,6 @@ class HipKernels:
     """Tensor-level front of the C ABI; the one object ``stc_hip.ops`` launches through."""
 
     name = 'hip-gfx950'
-    #: the planar gates backward adds the state's share from its gate prologue into the H plane's gradient itself (dH=None)
-    folds_dH = True
     #: operand format of the split-operand matrix-core cell kernels (include/stc_hip.h "operand formats"): two fp16 pieces / three
     #: products by default, STC_OPERAND_FORMAT=bf16x3 keeps three bf16 pieces / six products (fp32's range, twice the matrix instructions)
     operand_format = {'f16x2': FMT_F16X2, 'bf16x3': FMT_BF16X3}[os.environ.get('STC_OPERAND_FORMAT', 'f16x2')]
@@ -1576,7 +1574,6 @@ class _Bf16Planar:
     Only what an all-planar schedule needs exists here; interleaved rows and state copies are fp32-path features."""
 
     name = 'hip-gfx950-bf16'
-    folds_dH = True          # cell_gates_bwd_planar(dH=None) adds the prologue's share of the previous state into the H plane's gradient
 
     def __init__(self, base: HipKernels):
         self.b = base
@@ -1592,9 +1589,6 @@ class _Bf16Planar:
 
     def node_post_supported(self, Ks, Kc, Cc, L, Ho) -> bool:
         return self.cell_planar_supported(Ks, Kc, Cc, Ho) and L in (20, 32)
-
-    def cell_planar_post_fused(self, Cc) -> bool:
-        return True
 
     def csr_spmm(self, rowptr, colidx, val, n_rows, n_cols, X, Y0, Y, alpha, beta, plan=None):
         self.b.csr_spmm_bf16(rowptr, colidx, val, n_rows, n_cols, X, Y0, Y, alpha, beta, plan=plan)
@@ -1633,9 +1627,6 @@ class _Bf16Planar:
         b._launch('stc_cell_gates_fwd_planar_bf16', H, _ptr(X), _ptr(H), _ptr(SX), _ptr(SH), _ptr(Tc), _ptr(W), _ptr(bias),
                   _ptr(U), _ptr(Rg), _ptr(RH), _ptr(Wc), _ptr(bc), _ptr(A), _ptr(Bm), R, Cc, cin + h, h,
                      nbytes=2 * R * Cc * (2 * cin + 2 * h + h * (2 + (RH is not None) + (2 if post is not None else 0))))
-
-    def node_post_fwd(self, *a, **kw):
-        raise StcError('bf16 planar path: the candidate projection runs inside cell_gates_fwd_planar (post=); STC_FUSE_POST=0 is an fp32-path switch')
 
     def spmm_blend_fwd(self, rowptr, colidx, val, plan, Bm, A, U, H, Cand, Hnew, copies=(), side=None):
         b = self.b

@@ -24,7 +24,7 @@ first call raises ``StcError``.
 """
 from __future__ import annotations
 
-import weakref
+import enum
 from typing import Optional
 
 import torch
@@ -32,7 +32,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .graph import SpatialOperand
-from .small import small_graph_supported, stc_small_graph
+from .small import _alias, _check_guard, _guard, _out_slots, _stacks, _unpack, small_graph_supported, stc_small_graph
 
 _kernels = None
 
@@ -520,14 +520,11 @@ def stc_cell(Xt, H, op: SpatialOperand, Tc, Wg, bg, Wc, bc, Ks: int):
 
 
 # ----------------------------------------------------------------------------- a whole schedule of cells as ONE autograd node
-# Which forms the cell-graph executor uses.  Module constants (tests flip them to reach the forms other shapes still take -- C = 64 runs the
-# two-launch backward, K = 3 the order-3 planar cells, other widths the interleaved rows); not environment switches.
+# Which kernels the cell-graph executor uses.  Module constants, looked up at every call (tests flip them to reach the forms other shapes still
+# take -- C = 64 runs the two-launch backward, K = 3 the order-3 planar cells, other widths the interleaved rows); not environment switches.
 _CELL_GRAPH = True       # encoder + decoder as ONE autograd node (False: one node per cell, ``_StcCell``)
-_FUSE_POST = True        # candidate projection as a second stage of the planar gates forward
 _PLANAR = True           # cells with 16 + 16-column inputs read them as two planes (no concat, shared S.state)
 _POST_AGG = True         # candidate convolution as Y = A + S.Bm (narrow SpMM after the node kernel)
-_PLANAR_K3 = True        # Chebyshev order 3: planar cells on three planes per side (T_0, T_1, T_2 of S)
-_ACC_PLANES = True       # one-launch cell backward: a state's second consumer adds into the first one's planes
 _SMALL = True            # small graphs (N*C rows per sample fit the caches, C <= 16): one launch per cell step and direction
 _RING2 = True            # state gradient + transpose aggregation of dY in one launch where the graph has a two-ring plan (no dY plane)
 _RING2_FWD = True        # ... and the forward's blend + aggregation of the new state (stc_ring2_blend_f32)
@@ -545,23 +542,443 @@ def cell_graph_supported(op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widt
     if Tc.requires_grad or op.fwd_val.requires_grad:
         return False
     if dtype == torch.bfloat16:
-        return (_PLANAR and _POST_AGG and _FUSE_POST and Ks == 2 and Tc.shape[0] == 2 and k.bf16.cell_planar_supported(Ks, 2, C, h)
+        return (_PLANAR and _POST_AGG and Ks == 2 and Tc.shape[0] == 2 and k.bf16.cell_planar_supported(Ks, 2, C, h)
                 and all(w == h or 1 <= w <= 4 for w in x_widths))
     return all(k.cell_fused_supported(Ks, Tc.shape[0], C, w + h + (-(w + h)) % 4, h) for w in set(x_widths))
-
-
-def _alias_slice(base: torch.Tensor, i: int) -> torch.Tensor:
-    """base[i] as a tensor of its own that shares the storage WITHOUT being a view of ``base`` in autograd's books: the
-    slice is saved for backward while ``base`` is returned as the Function's output, which view tracking forbids."""
-    t = base.new_empty(0)
-    t.set_(base.untyped_storage(), base.storage_offset() + i * base.stride(0), base.shape[1:], base.stride()[1:])
-    return t
 
 
 def _amplification(op: SpatialOperand, Ks: int) -> float:
     """What one BDG_Dif of order Ks can amplify a state by: the graph's largest absolute row sum to the power Ks - 1 (T_2(S) = 2 S^2 - I has
     row sums of up to 2 r^2 + 1; order 3 on a graph with row sums of 8 puts the reference's own fp32 noise at 3.5e-4 on the prediction)."""
     return float(op.row_sum_bound) ** max(1, Ks - 1)
+
+
+class _Form(enum.Enum):
+    """The form one cell of ``_StcCellGraph`` runs in, chosen once per cell before the forward's launches (``_cell_forms``).  Every form
+    saves (H, U, R, Cand) for backward and then, in this order:"""
+    PLANAR3 = 'order-3 planar'          # Zx[0..2], Zh[1..2], Zr[0..2]: gates and slab-planar candidate on three Chebyshev planes per side
+    PLANAR_ONE_BWD = 'planar, one-launch backward'     # X, S.X, S.H: the backward re-forms R*H, which is never stored
+    PLANAR = 'planar'                   # X, S.X, S.H, R*H: node_post backward of the candidate, then the planar gates backward
+    ROWS_POST = 'rows, post-aggregation'   # Zg[0..Ks-1], CandIn: interleaved [Xt | H | 0] rows, candidate as Y = A + S.Bm (Ks = 2)
+    ROWS_SLABS = 'rows, slabs'          # Zg[0..Ks-1], Zc[0..Ks-1]: interleaved rows, candidate convolution on its Chebyshev slabs
+
+    def saved(self, Ks: int) -> int:
+        return 4 + {'PLANAR3': 8, 'PLANAR_ONE_BWD': 3, 'PLANAR': 4, 'ROWS_POST': Ks + 1, 'ROWS_SLABS': 2 * Ks}[self.name]
+
+    @property
+    def planar(self) -> bool:
+        return self not in (_Form.ROWS_POST, _Form.ROWS_SLABS)
+
+
+def _cell_forms(k, Ks: int, Kc: int, C: int, h: int, cin, bf16: bool):
+    """The ``_Form`` of every cell from its input width ``cin[j]``: planar where the planar kernels take the shape -- 16 + 16 columns, or
+    (layer 0) a narrow input plane of 1..4 columns beside the 16 state columns -- else interleaved rows."""
+    planar2 = (_PLANAR and _POST_AGG and Ks == 2 and k.cell_planar_supported(Ks, Kc, C, h)
+               and k.node_post_supported(Ks, Kc, C, 2 * h, h))
+    post20 = bool(planar2) and k.node_post_supported(Ks, Kc, C, 20, h)
+    # order 3 (BASELINE configuration 4): planar cells on the three Chebyshev planes of each side, candidate in slab-planar form
+    planar3 = bool(_PLANAR and not bf16 and Ks == 3 and Kc == 3 and k.cell_planar_k_supported(Ks, C, h))
+    forms = []
+    for w in cin:
+        if planar3 and (w == h or 1 <= w <= 4):
+            forms.append(_Form.PLANAR3)
+        elif planar2 and (w == h or (post20 and 1 <= w <= 4)):
+            # the one-launch backward (stc_cell_bwd_planar_f32) forms R*H itself
+            one_bwd = k.cell_bwd_planar_supported(C, h, w) if bf16 else k.cell_bwd_planar_supported(C, h)
+            forms.append(_Form.PLANAR_ONE_BWD if one_bwd else _Form.PLANAR)
+        else:                                                       # (Ks = 1 has no S.Bm term: slabs)
+            post = Ks > 1 and _POST_AGG and k.node_post_supported(Ks, Kc, C, w + h + (-(w + h)) % 4, h)
+            forms.append(_Form.ROWS_POST if post else _Form.ROWS_SLABS)
+    return forms
+
+
+class _Pass:
+    """What the cells of one pass of ``_StcCellGraph`` share: kernel set, graph, shapes, forms and the activation-maximum slots (fp16 x 2
+    operand format: every planar forward launch leaves the maxima of its input planes in a row of ``zmax_all``; the matching backward launch
+    scales the activation operands of its dW products by them -- _lib.act_amax_buffer)."""
+
+    def __init__(self, k, op: SpatialOperand, Ks: int, Tc, schedule, cin, forms, dims, bf16: bool, zmax_all, graph):
+        self.k, self.op, self.Ks, self.Tc, self.schedule, self.cin, self.forms = k, op, Ks, Tc, schedule, cin, forms
+        (self.B, self.N, self.C), self.h, self.bf16, self.zmax_all = dims, 16, bf16, zmax_all
+        self.graph = graph                                          # (rowptr, colidx, val, plan) of S (forward) or S^T (backward)
+
+    def spmm(self, X, Y0=None, Y=None, alpha=1.0, beta=0.0):        # Y = alpha S.X + beta Y0 on (B, N, C, w) tensors (S^T in the backward)
+        Y = torch.empty_like(X) if Y is None else Y
+        v3 = lambda t: None if t is None else t.view(self.B, self.N, -1)
+        self.k.csr_spmm(*self.graph[:3], self.N, self.N, v3(X), v3(Y0), v3(Y), alpha, beta, plan=self.graph[3])
+        return Y
+
+    def rows(self, ts):
+        return [None if t is None else t.view(self.B * self.N, self.C, t.shape[-1]) for t in ts]
+
+    def act_slots(self, j, which=0):                                # which: 0 = the gates convolution's planes, 1 = the candidate's (order 3)
+        return {} if self.zmax_all is None else dict(act_amax=self.zmax_all[j, which])
+
+
+class _ForwardPass(_Pass):
+    """... and, in the forward, the new states, the input rows of the interleaved cells and the aggregations of every source tensor (formed
+    once for all the planar cells that consume it)."""
+
+    def __init__(self, k, op: SpatialOperand, Ks: int, Tc, fwd_val, schedule, ext, cin, forms, bf16: bool):
+        zmax_all = k.act_amax_buffer(ext[0], len(schedule), 2, 2 * Ks) if (not bf16 and any(f.planar for f in forms)) else None   # (one zero fill)
+        super().__init__(k, op, Ks, Tc, schedule, cin, forms, ext[0].shape[:3], bf16, zmax_all, (op.fwd_rowptr, op.fwd_colidx, fwd_val, op.fwd_plan))
+        self.fwd_val, self.ext = fwd_val, ext
+        self.state = [None] * len(schedule)                         # plain (B,N,C,h) new state of every cell
+        self.XH, self.agg = {}, {}
+        self.consumers = [[] for _ in schedule]
+        for j, (_, x, hs) in enumerate(schedule):
+            for src, role in ((hs, 'h'), (x, 'x')):
+                if src[0] == 'cell':
+                    self.consumers[src[1]].append((j, role))
+        # two aggregations in one launch where the graph has a two-ring plan (stc_ring2_chain_f32 / stc_ring2_blend_f32; fp32 planes only)
+        self.ring2 = _RING2_FWD and not bf16 and op.fwd_ring2 is not None and k.ring2_fits(self.B, self.N, self.C, self.h)
+
+    def source(self, src):
+        return self.ext[src[1]] if src[0] == 'ext' else self.state[src[1]]
+
+    def rows_of(self, j):                                           # input rows of an interleaved cell, allocated at first touch
+        if j not in self.XH:
+            w = self.cin[j]
+            self.XH[j] = self.ext[0].new_empty(self.B, self.N, self.C, w + self.h + (-(w + self.h)) % 4)
+        return self.XH[j]
+
+    def aggregated(self, src, planes=False):                        # S.source -- order 3: its Chebyshev planes -- once per source tensor,
+        if src not in self.agg:                                     # shared by every cell that consumes it
+            self.agg[src] = self.cheb_planes(self.source(src)) if planes else self.spmm(self.source(src))
+        return self.agg[src]
+
+    def cheb_planes(self, t):                                       # [t, S.t, 2 S.(S.t) - t]: the feature-side recurrence, order 3
+        if not (self.ring2 and t.shape[-1] == self.h):
+            s1 = self.spmm(t)
+            return [t, s1, self.spmm(s1, t, alpha=2.0, beta=-1.0)]
+        # both aggregations in one launch: S.t for a patch's first ring is formed in LDS and aggregated from there (stc_ring2_chain_f32)
+        s1, s2 = torch.empty_like(t), torch.empty_like(t)
+        self.k.ring2_chain(*self.graph[:3], self.op.fwd_ring2, t, None, 1.0, [], s1, 2.0, [(t, -1.0)], s2)
+        return [t, s1, s2]
+
+    def copy_plan(self, j):
+        """Where else cell j's new state goes: straight into the input rows of the INTERLEAVED cells that consume it -- (copies, side) for the
+        blend launch's epilogue, (late_copies, late_rows) for torch after it."""
+        B, N, C, h, cin, schedule = self.B, self.N, self.C, self.h, self.cin, self.schedule
+        copies, side, late_copies, late_rows = [], None, [], []
+        for (d, role) in self.consumers[j]:
+            if self.forms[d].planar:
+                continue                                            # planar consumers read the state tensor itself
+            Xd = self.rows_of(d)
+            view = Xd.view(B * N, C, Xd.shape[-1])
+            if role == 'x':
+                copies.append((view, 0))
+            elif schedule[d][1][0] == 'ext':                        # H part + the consumer's external X part and pad columns
+                if side is None:
+                    copies.insert(0, (view, cin[d]))
+                    side = self.ext[schedule[d][1][1]].view(B * N, C, cin[d])
+                else:
+                    late_rows.append(d)
+            elif Xd.shape[-1] > cin[d] + h:
+                late_rows.append(d)                                 # pad columns to zero: not a case the kernel handles
+            else:
+                copies.append((view, cin[d]))
+        first = 1 if side is not None else 0
+        while len(copies) > 2:                                      # the kernel takes two destinations; the rest by torch
+            late_copies.append(copies.pop(len(copies) - 1 if len(copies) - 1 >= first else first))
+        return copies, side, late_copies, late_rows
+
+    def finish(self, j, Hnew, late_copies, late_rows):
+        for buf, off in late_copies:
+            buf[..., off:off + self.h].copy_(Hnew.view(self.B * self.N, self.C, self.h))
+        for d in late_rows:
+            Xd, xs, w = self.rows_of(d), self.schedule[d][1], self.cin[d]
+            if xs[0] == 'ext':
+                self.k.concat2(self.ext[xs[1]], Hnew, Xd)
+            else:
+                Xd[..., w:w + self.h].copy_(Hnew)
+                Xd[..., w + self.h:].zero_()
+        self.state[j] = Hnew
+
+    # ---- one function per form: the launches of cell j; returns what it saves after (H, U, R, Cand)
+    def planar3(self, j, Wg, bg, Wc, bc, Hprev, U, Rg, Cand, Hnew, copies, side):
+        k, rows, (_, x, hs) = self.k, self.rows, self.schedule[j]
+        Zx, Zh, RH = self.aggregated(x, planes=True), self.aggregated(hs, planes=True), torch.empty_like(Hprev)
+        k.cell_gates_fwd_planar_k(rows(Zx), rows(Zh), self.Tc, Wg, bg, *rows((U, Rg, RH)), **self.act_slots(j, 0))
+        Zr = self.cheb_planes(RH)                                   # the candidate's H side: T_n(S) of R*H (its X side is Zx again)
+        k.cell_cand_fwd_planar_k(rows(Zx), rows(Zr), self.Tc, Wc, bc, *rows((U, Hprev, Cand, Hnew)), **self.act_slots(j, 1))
+        return [*Zx, *Zh[1:], *Zr]
+
+    def planar(self, j, Wg, bg, Wc, bc, Hprev, U, Rg, Cand, Hnew, copies, side):
+        """PLANAR_ONE_BWD and PLANAR: the candidate's projection rides in the gates launch; only PLANAR stores the R*H plane."""
+        k, op, rows, (_, x, hs) = self.k, self.op, self.rows, self.schedule[j]
+        Xp, SXp, SHp = self.source(x), self.aggregated(x), self.aggregated(hs)
+        RH = None if self.forms[j] is _Form.PLANAR_ONE_BWD else torch.empty_like(Hprev)
+        A, Bm = torch.empty_like(Hprev), torch.empty_like(Hprev)
+        k.cell_gates_fwd_planar(*rows((Xp, Hprev, SXp, SHp)), self.Tc, Wg, bg, *rows((U, Rg, RH)), post=(Wc, bc, *rows((A, Bm))), **self.act_slots(j))
+        # the blend and the aggregation of the new state in one launch where the graph has a two-ring plan and some planar cell will
+        # ask for S.Hnew (stc_ring2_blend_f32: the new state is summed out of LDS instead of being read back by a launch of its own; on ring-bounded
+        # clusters it measured 792 us against 548 + 203 for the two launches: tiles only)
+        if (self.ring2 and not op.ring2_clusters and not copies and side is None
+                and any(self.forms[d].planar for d, _ in self.consumers[j])):
+            SHn = torch.empty_like(Hprev)
+            k.ring2_blend(*self.graph[:3], op.fwd_ring2, Bm, A, U, Hprev, Cand, Hnew, SHn)
+            self.agg[('cell', j)] = SHn
+        else:
+            k.spmm_blend_fwd(*self.graph, Bm, A, U, Hprev, Cand, Hnew, copies=copies, side=side)
+        return [Xp, SXp, SHp] + ([] if RH is None else [RH])
+
+    def rows_cell(self, j, Wg, bg, Wc, bc, Hprev, U, Rg, Cand, Hnew, copies, side):
+        """ROWS_POST and ROWS_SLABS: gates convolution on the Chebyshev slabs of the [Xt | H | 0] rows, gate math in its epilogue."""
+        k, op, rows, Tc, (_, x, hs) = self.k, self.op, self.rows, self.Tc, self.schedule[j]
+        Xj = self.rows_of(j)
+        w = self.cin[j]
+        if x[0] == 'ext' and hs[0] == 'ext':
+            k.concat2(self.ext[x[1]], Hprev, Xj)
+        elif x[0] == 'cell' and hs[0] == 'ext':                     # X part came from its producer; complete the row
+            Xj[..., w:w + self.h].copy_(Hprev)
+            if Xj.shape[-1] > w + self.h:
+                Xj[..., w + self.h:].zero_()
+        # (H part from a cell: its producer also wrote an external X part and the pad columns, see copy_plan)
+        CandIn = torch.empty_like(Xj)
+        Zg = _spatial_slabs(Xj, self.fwd_val, op, self.Ks)
+        k.cell_gates_fwd(rows(Zg), Tc, Wg, bg, *rows((Hprev, U, Rg, CandIn)))
+        if self.forms[j] is _Form.ROWS_POST:
+            # candidate convolution as Y = A + S.Bm: project first, aggregate C*h-float rows, blend in the SpMM's epilogue
+            A, Bm = torch.empty_like(Hprev), torch.empty_like(Hprev)
+            k.node_post_fwd(*rows((CandIn,)), Tc, Wc, bc, *rows((A, Bm)))
+            k.spmm_blend_fwd(*self.graph, Bm, A, U, Hprev, Cand, Hnew, copies=copies, side=side)
+            return [*Zg, CandIn]
+        Zc = _spatial_slabs(CandIn, self.fwd_val, op, self.Ks)
+        k.cell_blend_fwd(rows(Zc), Tc, Wc, bc, *rows((U, Hprev, Cand, Hnew)), copies=copies, side=side)
+        return [*Zg, *Zc]
+
+
+class _BackwardPass(_Pass):
+    """... and, in the backward, the gradients owed to every state -- finished tensors (``G``) from the outputs and interleaved consumers,
+    pieces from planar consumers -- and the parameter-gradient rows of the planar cells."""
+
+    def __init__(self, k, op: SpatialOperand, Ks: int, Tc, schedule, stacks, cin, forms, dims, bf16: bool, zmax_all):
+        super().__init__(k, op, Ks, Tc, schedule, cin, forms, dims, bf16, zmax_all, (op.bwd_rowptr, op.bwd_colidx, op.bwd_val, op.bwd_plan))
+        self.stacks = stacks
+        # state gradient sums fused with a transpose aggregation where the graph has a two-ring plan (stc_ring2_sum_f32 / _chain_f32)
+        self.ring2 = _RING2 and not bf16 and op.bwd_ring2 is not None and k.ring2_fits(self.B, self.N, self.C, self.h)
+        self.G = {}                                                 # cell -> gradient its state is owed so far
+        # Planar consumers leave PIECES of a state's gradient instead of a finished tensor: direct planes (what the state
+        # is owed as a plane of their inputs) and aggregated planes (what its aggregation S.state is owed).  Aggregation
+        # being linear, the state's gradient is  sum(direct) + S^T sum(aggregated): ONE narrow SpMM per state with the
+        # sums in its gather / epilogue -- instead of a wide transpose SpMM and a split pass per consuming cell.
+        self.pieces = {}
+        # Parameter gradients of the planar cells: every cell writes its (dWg, dbg, dWc, dbc) into its own row of ONE buffer per parameter
+        # set, summed once at the end -- instead of four accumulation passes per cell (176 five-microsecond launches per metric step).
+        self.rows_of_set = {}
+
+    def grads_for(self, s_id):                                      # the next row of the set's buffer
+        if s_id not in self.rows_of_set:
+            Wg_, bg_, Wc_, bc_ = self.stacks[s_id]
+            sizes = [Wg_.numel(), 0 if bg_ is None else 2 * self.h, Wc_.numel(), 0 if bc_ is None else self.h]
+            self.rows_of_set[s_id] = [Wg_.new_zeros(sum(1 for sc in self.schedule if sc[0] == s_id), sum(sizes)), 0, sizes]
+        entry = self.rows_of_set[s_id]
+        entry[1] += 1
+        return self.param_views(s_id, entry[0][entry[1] - 1])
+
+    def param_views(self, s_id, row):                               # (dWg, dbg, dWc, dbc) as views of one row of the set's buffer
+        Wg_, bg_, Wc_, bc_ = self.stacks[s_id]
+        parts = row.split(self.rows_of_set[s_id][2])
+        return parts[0].view_as(Wg_), None if bg_ is None else parts[1], parts[2].view_as(Wc_), None if bc_ is None else parts[3]
+
+    def leave(self, kid, direct, aggregated):
+        pc = self.pieces.setdefault(kid, dict(direct=[], agg=[]))
+        pc['direct'] += direct
+        pc['agg'].append(aggregated)
+
+    def owed(self, kid, blend=None):
+        """The gradient of state ``kid`` from what its consumers left; with ``blend`` = (U, Cand) of its cell also dY = gradient * U * (1 - Cand^2)."""
+        base = self.G.pop(kid, None)                                # from interleaved consumers / the outputs: a finished tensor
+        pc = self.pieces.pop(kid, None)
+        if pc is None:
+            if blend is None:
+                return base
+            dY = torch.empty_like(base)
+            self.k.gru_blend_bwd(base, blend[0], None, blend[1], dY, None, None)
+            return base, dY
+        if 'd2' in pc:                                              # pieces of order-3 consumers (``leave3``; their states need no blend)
+            return self.clenshaw(pc['d0'] + ([base] if base is not None else []), pc['d1'], pc['d2'])
+        add = pc['direct'] + ([base] if base is not None else [])
+        aggs = pc['agg']
+        while len(add) > 5:                                         # more consumers than the kernel takes addends for: pre-sum
+            add.append(add.pop() + add.pop())
+        while len(aggs) > 2:
+            aggs = [aggs[0] + aggs[1]] + aggs[2:]
+        out = torch.empty_like(aggs[0])
+        dY = torch.empty_like(out) if blend is not None else None
+        self.k.spmm_sum(*self.graph, aggs[0], aggs[1] if len(aggs) > 1 else None, [(t, 0) for t in add], out,
+                   blend=None if blend is None else (blend[0], blend[1], dY))
+        return out if blend is None else (out, dY)
+
+    def owed_ring2(self, kid, U_, Cand_):
+        """(gradient of state ``kid``, S^T (gradient * U * (1 - Cand^2))) in one launch where the graph has a two-ring plan; None: the two
+        launches (``owed`` with its blend epilogue, then the narrow aggregation)."""
+        pc = self.pieces.get(kid)
+        if not self.ring2 or pc is None:
+            return None
+        add = pc['direct'] + ([self.G[kid]] if kid in self.G else [])
+        # (the forms that fit the register file: one aggregated plane, up to two addends -- 590 / 680 us for the 555 + 185 they replace; with a
+        #  second aggregated plane the kernel spills and takes 840 - 1 150 us: the two launches stay)
+        if len(add) > 2 or len(pc['agg']) != 1:
+            return None
+        self.G.pop(kid, None)
+        self.pieces.pop(kid)
+        out, dBm_ = torch.empty_like(pc['agg'][0]), torch.empty_like(pc['agg'][0])
+        self.k.ring2_sum(*self.graph[:3], self.op.bwd_ring2, pc['agg'][0], None, add, U_, Cand_, out, dBm_)
+        return out, dBm_
+
+    # Order 3: a consumer leaves direct planes d0 and the gradients d1, d2 of the S / T_2(S) planes; the source's gradient is
+    #   sum d0 - sum d2 + S^T (sum d1 + 2 S^T sum d2)          (Clenshaw form of sum_n T_n(S)^T d_n)
+    # = two narrow SpMMs with the sums in their gather / epilogue (alpha and signed addends of stc_spmm_sum_f32).
+    def leave3(self, kid, d0, d1, d2):
+        pc = self.pieces.setdefault(kid, dict(d0=[], d1=[], d2=[]))
+        pc['d0'] += list(d0); pc['d1'] += list(d1); pc['d2'] += list(d2)
+
+    def clenshaw(self, d0, d1, d2):
+        """sum d0 - sum d2 + S^T (sum d1 + 2 S^T sum d2) from lists of planes (d2 non-empty)."""
+        k = self.k
+        while len(d2) > 2:                                          # the kernel gathers two operands: pre-sum the rest
+            d2 = [d2[0] + d2[1]] + d2[2:]
+        if self.ring2 and len(d1) <= 2 and 1 <= len(d0) + len(d2) <= k.RING2_MAX_ADD:
+            # both transpose aggregations in one launch (stc_ring2_chain_f32): the inner sum d1 + 2 S^T d2 never leaves the chip
+            out = torch.empty_like(d2[0])
+            k.ring2_chain(*self.graph[:3], self.op.bwd_ring2, d2[0], d2[1] if len(d2) > 1 else None, 2.0, list(d1), None, 1.0,
+                          [(a, 1.0) for a in d0] + [(a, -1.0) for a in d2], out)
+            return out
+        t = torch.empty_like(d2[0])
+        k.spmm_sum(*self.graph, d2[0], d2[1] if len(d2) > 1 else None, [(a, 0) for a in d1], t, alpha=2.0)
+        adds = [(a, 0) for a in d0] + [(a, 0, -1.0) for a in d2]
+        while len(adds) > 8:
+            (a, _), (b_, _) = adds.pop(0), adds.pop(0)
+            adds.insert(0, (a + b_, 0))
+        out = torch.empty_like(t)
+        k.spmm_sum(*self.graph, t, None, adds, out, blend=None)
+        return out
+
+    # ---- one function per form: the launches of cell j's backward from what its forward saved (``_Form``)
+    def planar3(self, j, Wg, bg, Wc, bc, saved):
+        k, rows, Tc, (s_id, x, hs) = self.k, self.rows, self.Tc, self.schedule[j]
+        Hprev, U, Rg, Cand, Zx0, Zx1, Zx2, Zh1, Zh2, *Zr = saved
+        Zx, Zh = [Zx0, Zx1, Zx2], [Hprev, Zh1, Zh2]
+        wide = self.cin[j] == self.h
+        new = lambda: torch.empty_like(Hprev)
+        dWg, dbg, dWc, dbc = self.grads_for(s_id)                   # (parameter gradients: rows of the set's buffer, summed at the end)
+        dHnew = self.owed(j)
+        dX, dR = ([new(), new(), new()] if wide else [None] * 3), [new(), new(), new()]
+        k.cell_cand_bwd_planar_k(rows(Zx), rows(Zr), Tc, Wc, *rows((dHnew, U, Cand)), rows(dX), rows(dR), dWc, dbc, **self.act_slots(j, 1))
+        dRH = self.clenshaw([dR[0]], [dR[1]], [dR[2]])              # gradient of the R*H plane from its three Chebyshev planes
+        del dR
+        # the kernel ADDS the gates' X-side gradients into the candidate's three planes (accumulate_x), so the source gets one plane per
+        # order from this cell and its Clenshaw sums need no pre-sum; it adds the prologue's share into the H plane's gradient (dH = None)
+        dHg = [new(), new(), new()]
+        k.cell_gates_bwd_planar_k(rows(Zx), rows(Zh), Tc, Wg, *rows((dRH, Cand, U, Rg, dHnew)), rows(dX), rows(dHg), dWg, dbg, None,
+                                  accumulate_x=wide, **self.act_slots(j, 0))
+        if wide and x[0] == 'cell':
+            self.leave3(x[1], dX[:1], dX[1:2], dX[2:])
+        if hs[0] == 'cell':
+            self.leave3(hs[1], dHg[:1], dHg[1:2], dHg[2:])
+
+    def planar_one_bwd(self, j, Wg, bg, Wc, bc, saved):
+        k, (s_id, x, hs) = self.k, self.schedule[j]
+        Hprev, U, Rg, Cand, Xp, SXp, SHp = saved
+        fused = self.owed_ring2(j, U, Cand)                         # state gradient + S^T dY in one launch, no dY plane (stc_ring2_sum_f32)
+        if fused is not None:
+            dHnew, dBm = fused
+        else:
+            dHnew, dY = self.owed(j, (U, Cand))
+            dBm = self.spmm(dY)
+            del dY                                                  # (the kernel re-forms dY from dHnew, U, Cand)
+        new = lambda: torch.empty_like(Hprev)
+        dWg, dbg, dWc, dbc = self.grads_for(s_id)
+        # A state has two consumers (next step as H, next layer as X): the first one processed writes the state's direct and
+        # aggregated gradient planes, the second ADDS into them (accumulate_x / accumulate_h), so the state-gradient SpMM gathers
+        # one operand instead of two and reads one direct plane instead of two.
+        taken = set()
+
+        def planes_of_state(src):
+            if src[0] != 'cell':
+                return new(), new(), False                          # an external tensor: gradients computed, nobody owed
+            pc = self.pieces.get(src[1])
+            if not self.bf16 and pc is not None and pc.get('own') is not None and src[1] not in taken:
+                taken.add(src[1])
+                return pc['own'][0], pc['own'][1], True
+            d, a_ = new(), new()
+            self.leave(src[1], (d,), a_)
+            if self.pieces[src[1]].get('own') is None:
+                self.pieces[src[1]]['own'] = (d, a_)
+                taken.add(src[1])
+            return d, a_, False
+
+        dXd, dSX, acc_x = planes_of_state(x) if self.cin[j] == self.h else (None, None, False)
+        dHd, dSH, acc_h = planes_of_state(hs)
+        k.cell_bwd_planar(*self.rows((Xp, Hprev, SXp, SHp)), self.Tc, Wg, Wc, *self.rows((U, Rg, Cand, dHnew, dBm)),
+                          self.rows((dXd, dSX, dHd, dSH)), dWg, dbg, dWc, dbc,
+                          **(dict(accumulate_x=acc_x, accumulate_h=acc_h, **self.act_slots(j)) if not self.bf16 else {}))
+
+    def planar(self, j, Wg, bg, Wc, bc, saved):
+        k, rows, Tc, (s_id, x, hs) = self.k, self.rows, self.Tc, self.schedule[j]
+        Hprev, U, Rg, Cand, Xp, SXp, SHp, RH = saved
+        dHnew, dY = self.owed(j, (U, Cand))
+        wide = self.cin[j] == self.h                                # else: narrow input plane (layer 0), which needs no gradient
+        # the candidate's input planes are (X, R*H): X's maximum as the gates forward left it, R*H rides on H's (|R*H| <= |H|).  Slot
+        # rows of that launch: wide {X, S.X, H, S.H}, narrow {H, S.H, x, S.x}; the post kernel takes (16-wide plane, other plane).
+        zr = None if self.zmax_all is None else self.zmax_all[j, 0]
+        post_kw, gates_kw = ({}, {}) if zr is None else (dict(act_amax=(zr[0], zr[2])), dict(act_amax=zr))
+        dBm = self.spmm(dY)
+        dRH = torch.empty_like(Hprev)
+        dWg, dbg, dWc, dbc = self.grads_for(s_id)
+        dHd, dSH = torch.empty_like(Hprev), torch.empty_like(Hprev)
+        if wide:
+            dXc, dXd, dSX = (torch.empty_like(Hprev) for _ in range(3))
+            k.node_post_bwd(*rows((Xp,)), Tc, Wc, *rows((dY, dBm, dXc)), dWc, dbc, X2=RH.view(-1, self.C, self.h), dX2=dRH.view(-1, self.C, self.h),
+                            **post_kw)
+            planes = rows((dXd, dSX, dHd, dSH))
+        else:
+            k.node_post_bwd(*rows((RH,)), Tc, Wc, *rows((dY, dBm, dRH)), dWc, dbc, X2=Xp.view(-1, self.C, self.cin[j]), **post_kw)
+            planes = [None, None] + rows((dHd, dSH))
+        del dY, dBm
+        # (dH = None: the kernel adds the prologue's share into the H plane's gradient)
+        k.cell_gates_bwd_planar(*rows((Xp, Hprev, SXp, SHp)), Tc, Wg, *rows((dRH, Cand, U, Rg, dHnew)), planes, dWg, dbg, None, **gates_kw)
+        if wide and x[0] == 'cell':
+            self.leave(x[1], (dXd, dXc), dSX)                       # as the X plane: gates' and candidate's direct shares
+        if hs[0] == 'cell':
+            self.leave(hs[1], (dHd,), dSH)                          # as the H plane, the gates prologue's share included
+
+    def rows_cell(self, j, Wg, bg, Wc, bc, saved):
+        """ROWS_POST and ROWS_SLABS; the sources get finished gradient tensors.  Returns the cell's (dWg, dbg, dWc, dbc)."""
+        k, op, Ks, h, Tc, (s_id, x, hs) = self.k, self.op, self.Ks, self.h, self.Tc, self.schedule[j]
+        Hprev, U, Rg, Cand, *Z = saved
+        Zg, Zc = Z[:Ks], Z[Ks:]
+        post = self.forms[j] is _Form.ROWS_POST                     # candidate backward starts from dY = dHnew * U * (1 - Cand^2)
+        dHnew, dY = self.owed(j, (U, Cand)) if post else (self.owed(j), None)
+        dH = torch.empty_like(Hprev)
+        if post:                                                    # the forward ran this convolution as Y = A + S.Bm (no Z_1 slab)
+            dBm = self.spmm(dY)
+            dci, dWc = torch.empty_like(Zc[0]), torch.empty_like(Wc)
+            dbc = Wc.new_empty(h) if bc is not None else None
+            k.node_post_bwd(*self.rows((Zc[0],)), Tc, Wc, *self.rows((dY, dBm, dci)), dWc, dbc)
+        else:                                                       # slab form, blend backward in the node kernel's prologue
+            g, dWc, dbc, _, _ = _bdg_backward_slabs(None, Zc, Wc, Tc, op, Ks, bc is not None, False, False, cand=(dHnew, U, Cand))
+            if Ks > 1:
+                self.spmm(g[1], g[0], g[0], 1.0, 1.0)
+            dci = g[0]
+        # gates convolution, gate + blend backward in its prologue
+        g, dWg, dbg, _, _ = _bdg_backward_slabs(None, Zg, Wg, Tc, op, Ks, bg is not None, False, False, gates=(dci, Cand, Hprev, U, Rg, dHnew, dH))
+        need_x, need_h = x[0] == 'cell', hs[0] == 'cell'
+        if need_x or need_h:
+            if Ks > 1:
+                self.spmm(g[1], g[0], g[0], 1.0, 1.0)
+            dXt = Hprev.new_empty(Hprev.shape[:-1] + (self.cin[j],))
+            same = need_x and need_h and x[1] == hs[1]
+            owedA = self.G.get(x[1]) if need_x else None
+            owedB = self.G.get(hs[1]) if (need_h and not same) else None
+            k.split2(g[0], dXt, dH, addA=dci, addB=dH, addA_ld=Zc[0].shape[-1], addA2=owedA, addB2=owedB)
+            if need_h and not same:
+                self.G[hs[1]] = dH
+            if need_x:
+                self.G[x[1]] = dXt.add_(dH) if same else dXt
+        return dWg, dbg, dWc, dbc
 
 
 class _StcCellGraph(Function):
@@ -576,505 +993,77 @@ class _StcCellGraph(Function):
       * the candidate convolution in post-aggregation form where the kernels exist (``_POST_AGG``);
       * no autograd accumulation passes: a state consumed by two cells (next step, next layer) gets its two gradient
         contributions summed inside the consumers' final split (``stc_split2_f32`` addA2 / addB2), in schedule order.
+    Every cell runs in one of five forms (``_Form``), chosen once before the forward's launches: PLANAR3 (order 3), PLANAR_ONE_BWD and
+    PLANAR (order 2: one-launch or two-launch backward), ROWS_POST and ROWS_SLABS (interleaved rows; candidate as Y = A + S.Bm or on slabs).
+    The launches of each form are one method of ``_ForwardPass`` and one of ``_BackwardPass``.
     schedule[j] = (stack, ('ext', i) | ('cell', k), ('ext', i) | ('cell', k)): parameter set, source of Xt, source of H.
     """
 
     @staticmethod
     def forward(ctx, op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, *tensors):
         k = kernels().for_graph(_amplification(op, Ks))              # (a heavy graph: the 24-bit operand format, _lib.HEAVY_ROW_SUM)
-        ext = [_c(t) for t in tensors[:n_ext]]
+        ext, stacks, Tc, fwd_val = _unpack(n_ext, Tc, fwd_val, tensors)
         bf16 = ext[0].dtype == torch.bfloat16                       # bf16 state planes: the all-planar bf16 kernel set
         if bf16:
             k = k.bf16
-        flat = tensors[n_ext:]
-        stacks = [tuple(None if p is None else _c(p) for p in flat[i:i + 4]) for i in range(0, len(flat), 4)]   # (Wg, bg, Wc, bc)
-        Tc, fwd_val = _c(Tc), _c(fwd_val)
         h = 16
-        n_cells = len(schedule)
-        width = lambda src: ext[src[1]].shape[-1] if src[0] == 'ext' else h
-        cin = [width(x) for _, x, _ in schedule]
-        consumers = [[] for _ in range(n_cells)]
-        for j, (_, x, hs) in enumerate(schedule):
-            if hs[0] == 'cell':
-                consumers[hs[1]].append((j, 'h'))
-            if x[0] == 'cell':
-                consumers[x[1]].append((j, 'x'))
-        ref = ext[0]
-        B, N, C = ref.shape[:3]
-        rows = lambda ts: [t.view(B * N, C, t.shape[-1]) for t in ts]
-        source = lambda src: ext[src[1]] if src[0] == 'ext' else state[src[1]]
-        planar_ok = (_PLANAR and _POST_AGG and Ks == 2 and k.cell_planar_supported(Ks, Tc.shape[0], C, h)
-                     and k.node_post_supported(Ks, Tc.shape[0], C, 2 * h, h))
-        post20 = bool(planar_ok) and k.node_post_supported(Ks, Tc.shape[0], C, 20, h)
-        # order 3 (BASELINE configuration 4): planar cells on the three Chebyshev planes of each side, candidate in slab-planar form
-        planar_k = bool(_PLANAR and _PLANAR_K3 and not bf16 and Ks == 3 and Tc.shape[0] == 3 and k.cell_planar_k_supported(Ks, C, h))
-        # 16 + 16 columns, or (layer 0) a narrow input plane of 1..4 columns beside the 16 state columns
-        planar = [bool((planar_ok and (cin[j] == h or (post20 and 1 <= cin[j] <= 4))) or (planar_k and (cin[j] == h or 1 <= cin[j] <= 4)))
-                  for j in range(n_cells)]
-        if bf16 and not all(planar):
+        B, N, C = ext[0].shape[:3]
+        cin = [ext[x[1]].shape[-1] if x[0] == 'ext' else h for _, x, _ in schedule]
+        forms = _cell_forms(k, Ks, Tc.shape[0], C, h, cin, bf16)
+        if bf16 and not all(f.planar for f in forms):
             raise ValueError('stc_cell_graph: bfloat16 states need an all-planar schedule (Ks = 2, inputs 16 or 1..4 columns wide)')
-        XH, agg = {}, {}
-
-        def rows_of(j):                                             # input rows of an interleaved cell, allocated at first touch
-            if j not in XH:
-                L = cin[j] + h + (-(cin[j] + h)) % 4
-                XH[j] = ref.new_empty(B, N, C, L)
-            return XH[j]
-
-        def aggregated(src):                                        # S.source, once per source tensor
-            if src not in agg:
-                t = source(src)
-                out, w = torch.empty_like(t), t.shape[-1]
-                k.csr_spmm(op.fwd_rowptr, op.fwd_colidx, fwd_val, N, N, t.view(B, N, C * w), None, out.view(B, N, C * w), 1.0, 0.0,
-                           plan=op.fwd_plan)
-                agg[src] = out
-            return agg[src]
-
-        def cheb_planes(t):                                         # [t, S.t, 2 S.(S.t) - t]: the feature-side recurrence, order 3
-            w = t.shape[-1]
-            v3 = lambda a: a.view(B, N, C * w)
-            s1, s2 = torch.empty_like(t), torch.empty_like(t)
-            if _RING2_FWD and w == h and not bf16 and op.fwd_ring2 is not None and hasattr(k, 'ring2_chain') and k.ring2_fits(B, N, C, h):
-                # both aggregations in one launch: S.t for a patch's first ring is formed in LDS and aggregated from there (stc_ring2_chain_f32)
-                k.ring2_chain(op.fwd_rowptr, op.fwd_colidx, fwd_val, op.fwd_ring2, t, None, 1.0, [], s1, 2.0, [(t, -1.0)], s2)
-                return [t, s1, s2]
-            k.csr_spmm(op.fwd_rowptr, op.fwd_colidx, fwd_val, N, N, v3(t), None, v3(s1), 1.0, 0.0, plan=op.fwd_plan)
-            k.csr_spmm(op.fwd_rowptr, op.fwd_colidx, fwd_val, N, N, v3(s1), v3(t), v3(s2), 2.0, -1.0, plan=op.fwd_plan)
-            return [t, s1, s2]
-
-        def planes_of(src):                                         # once per source tensor, shared by every cell that consumes it
-            if src not in agg:
-                agg[src] = cheb_planes(source(src))
-            return agg[src]
-
-        # fp16 x 2 operand format: every planar forward launch leaves the maxima of its input planes in a row of slots (one zero fill per
-        # forward pass); the matching backward launch scales the activation operands of its dW products by them (_lib.act_amax_buffer)
-        zmax_all = k.act_amax_buffer(ref, n_cells, 2, 2 * Ks) if (not bf16 and any(planar)) else None
-
-        def act_slots(j, which=0):                                  # which: 0 = the gates convolution's planes, 1 = the candidate's (order 3)
-            return {} if zmax_all is None else dict(act_amax=zmax_all[j, which])
-
-        state = [None] * n_cells                                    # plain (B,N,C,h) new state of every cell
-        out_stack = ref.new_empty(len(outputs), B, N, C, h)         # the requested states are produced in place, stacked
-        out_slot = {j: i for i, j in enumerate(outputs)}
-        if len(out_slot) != len(outputs):
-            raise ValueError('stc_cell_graph: duplicate output cells')
-        saved, n_saved = [], []
+        p = _ForwardPass(k, op, Ks, Tc, fwd_val, schedule, ext, cin, forms, bf16)
+        out_stack = ext[0].new_empty(len(outputs), B, N, C, h)      # the requested states are produced in place, stacked
+        out_slot = _out_slots(outputs)
+        saved = []
         for j, (s_id, x, hs) in enumerate(schedule):
-            Wg, bg, Wc, bc = stacks[s_id]
-            Hprev = source(hs)
-            # where else the new state goes: straight into the input rows of the INTERLEAVED cells that consume it
-            copies, side, late_copies, late_rows = [], None, [], []
-            for (d, role) in consumers[j]:
-                if planar[d]:
-                    continue                                        # planar consumers read the state tensor itself
-                Xd = rows_of(d)
-                view = Xd.view(B * N, C, Xd.shape[-1])
-                if role == 'x':
-                    copies.append((view, 0))
-                elif schedule[d][1][0] == 'ext':                    # H part + the consumer's external X part and pad columns
-                    if side is None:
-                        copies.insert(0, (view, cin[d]))
-                        side = ext[schedule[d][1][1]].view(B * N, C, cin[d])
-                    else:
-                        late_rows.append(d)
-                elif Xd.shape[-1] > cin[d] + h:
-                    late_rows.append(d)                             # pad columns to zero: not a case the kernel handles
-                else:
-                    copies.append((view, cin[d]))
-            first = 1 if side is not None else 0
-            while len(copies) > 2:                                  # the kernel takes two destinations; the rest by torch
-                late_copies.append(copies.pop(len(copies) - 1 if len(copies) - 1 >= first else first))
+            Hprev = p.source(hs)
+            copies, side, late_copies, late_rows = p.copy_plan(j)
             U, Rg, Cand = torch.empty_like(Hprev), torch.empty_like(Hprev), torch.empty_like(Hprev)
-            Hnew = _alias_slice(out_stack, out_slot[j]) if j in out_slot else torch.empty_like(Hprev)
-            if planar[j] and planar_k:
-                Zx, Zh, RH = planes_of(x), planes_of(hs), torch.empty_like(Hprev)
-                k.cell_gates_fwd_planar_k(rows(Zx), rows(Zh), Tc, Wg, bg, *rows((U, Rg, RH)), **act_slots(j, 0))
-                Zr = cheb_planes(RH)                                # the candidate's H side: T_n(S) of R*H (its X side is Zx again)
-                k.cell_cand_fwd_planar_k(rows(Zx), rows(Zr), Tc, Wc, bc, *rows((U, Hprev, Cand, Hnew)), **act_slots(j, 1))
-                saved += [Hprev, U, Rg, Cand, *Zx, *Zh[1:], *Zr]
-                n_saved.append(-12)                                 # negative count: planar cell (12: order 3, slab-planar candidate)
-            elif planar[j]:
-                Xp, SXp, SHp = source(x), aggregated(x), aggregated(hs)
-                fused_post = _FUSE_POST and k.cell_planar_post_fused(C)
-                # one-launch backward (stc_cell_bwd_planar_f32) forms R*H itself: with the fused projection the plane is not stored at all
-                one_bwd = fused_post and (k.cell_bwd_planar_supported(C, h, cin[j]) if bf16 else k.cell_bwd_planar_supported(C, h))
-                RH = None if one_bwd else torch.empty_like(Hprev)
-                A, Bm = torch.empty_like(Hprev), torch.empty_like(Hprev)
-                if fused_post:                                        # the candidate's projection rides in the gates launch
-                    k.cell_gates_fwd_planar(*rows((Xp, Hprev, SXp, SHp)), Tc, Wg, bg, *rows((U, Rg)), None if RH is None else RH.view(B * N, C, h),
-                                            post=(Wc, bc, *rows((A, Bm))), **act_slots(j))
-                else:
-                    k.cell_gates_fwd_planar(*rows((Xp, Hprev, SXp, SHp)), Tc, Wg, bg, *rows((U, Rg, RH)), **act_slots(j))
-                    lead, second = (Xp, RH) if cin[j] == h else (RH, Xp)     # narrow input plane: the 16-wide plane leads
-                    k.node_post_fwd(*rows((lead,)), Tc, Wc, bc, *rows((A, Bm)), X2=second.view(B * N, C, second.shape[-1]))
-                # the blend and the aggregation of the new state in one launch where the graph has a two-ring plan and some planar cell will
-                # ask for S.Hnew (stc_ring2_blend_f32: the new state is summed out of LDS instead of being read back by a launch of its own; on ring-bounded
-                # clusters it measured 792 us against 548 + 203 for the two launches: tiles only)
-                if (_RING2_FWD and not bf16 and op.fwd_ring2 is not None and not op.ring2_clusters and not copies and side is None and hasattr(k, 'ring2_blend') and k.ring2_fits(B, N, C, h)
-                        and any(planar[d] and not planar_k for d, _ in consumers[j])):
-                    SHn = torch.empty_like(Hprev)
-                    k.ring2_blend(op.fwd_rowptr, op.fwd_colidx, fwd_val, op.fwd_ring2, Bm, A, U, Hprev, Cand, Hnew, SHn)
-                    agg[('cell', j)] = SHn
-                else:
-                    k.spmm_blend_fwd(op.fwd_rowptr, op.fwd_colidx, fwd_val, op.fwd_plan, Bm, A, U, Hprev, Cand, Hnew, copies=copies, side=side)
-                del A, Bm
-                saved += [Hprev, U, Rg, Cand, Xp, SXp, SHp] + ([] if RH is None else [RH])
-                n_saved.append(-7 if RH is None else -8)            # negative count: planar cell (-7: no R*H plane, one-launch backward)
-            else:
-                Xj = rows_of(j)
-                L = Xj.shape[-1]
-                if x[0] == 'ext' and hs[0] == 'ext':
-                    k.concat2(ext[x[1]], Hprev, Xj)
-                elif x[0] == 'cell' and hs[0] == 'ext':             # X part came from its producer; complete the row
-                    Xj[..., cin[j]:cin[j] + h].copy_(Hprev)
-                    if L > cin[j] + h:
-                        Xj[..., cin[j] + h:].zero_()
-                # (H part from a cell: its producer also wrote an external X part and the pad columns, see above)
-                CandIn = torch.empty_like(Xj)
-                Zg = _spatial_slabs(Xj, fwd_val, op, Ks)
-                k.cell_gates_fwd(rows(Zg), Tc, Wg, bg, *rows((Hprev, U, Rg, CandIn)))
-                post = _POST_AGG and k.node_post_supported(Ks, Tc.shape[0], C, L, h)
-                if post:
-                    # candidate convolution as Y = A + S.Bm: project first, aggregate C*h-float rows, blend in the SpMM's epilogue
-                    Zc = [CandIn]
-                    A, Bm = torch.empty_like(Hprev), torch.empty_like(Hprev)
-                    k.node_post_fwd(*rows((CandIn,)), Tc, Wc, bc, *rows((A, Bm)))
-                    k.spmm_blend_fwd(op.fwd_rowptr, op.fwd_colidx, fwd_val, op.fwd_plan, Bm, A, U, Hprev, Cand, Hnew, copies=copies, side=side)
-                    del A, Bm
-                else:
-                    Zc = _spatial_slabs(CandIn, fwd_val, op, Ks)
-                    k.cell_blend_fwd(rows(Zc), Tc, Wc, bc, *rows((U, Hprev, Cand, Hnew)), copies=copies, side=side)
-                saved += [Hprev, U, Rg, Cand, *Zg, *Zc]
-                n_saved.append(4 + len(Zg) + len(Zc))
-            for buf, off in late_copies:
-                buf[..., off:off + h].copy_(Hnew.view(B * N, C, h))
-            for d in late_rows:
-                Xd, xs = rows_of(d), schedule[d][1]
-                if xs[0] == 'ext':
-                    k.concat2(ext[xs[1]], Hnew, Xd)
-                else:
-                    Xd[..., cin[d]:cin[d] + h].copy_(Hnew)
-                    Xd[..., cin[d] + h:].zero_()
-            state[j] = Hnew
-        ctx.save_for_backward(Tc, *[p for st in stacks for p in st if p is not None], *saved)
-        ctx.meta = (op, Ks, schedule, tuple(outputs), cin, [tuple(p is not None for p in st) for st in stacks], (B, N, C), n_saved)
-        ctx.zmax_all = zmax_all
-        # the saved states of the output cells ALIAS out_stack's storage without sharing its autograd version counter: the
-        # returned stack is read-only for its consumers; its version is checked again in backward
-        ctx.out_stack_ref, ctx.out_stack_version = weakref.ref(out_stack), out_stack._version      # (weak: no output -> ctx -> output cycle)
+            Hnew = _alias(out_stack, out_slot[j]) if j in out_slot else torch.empty_like(Hprev)
+            run = p.planar3 if forms[j] is _Form.PLANAR3 else p.planar if forms[j].planar else p.rows_cell
+            saved += [Hprev, U, Rg, Cand, *run(j, *stacks[s_id], Hprev, U, Rg, Cand, Hnew, copies, side)]
+            p.finish(j, Hnew, late_copies, late_rows)
+        ctx.save_for_backward(Tc, *[t for st in stacks for t in st], *saved)
+        ctx.meta = (op, Ks, schedule, tuple(outputs), cin, len(stacks), (B, N, C), forms)
+        ctx.zmax_all = p.zmax_all
+        _guard(ctx, out_stack)
         return out_stack
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_stack):
         k = kernels().for_graph(_amplification(ctx.meta[0], ctx.meta[1]))
-        bf16_planes = grad_stack.dtype == torch.bfloat16
-        if bf16_planes:
+        bf16 = grad_stack.dtype == torch.bfloat16
+        if bf16:
             k = k.bf16
-        op, Ks, schedule, outputs, cin, present, (B, N, C), n_saved = ctx.meta
-        stack = ctx.out_stack_ref()
-        if stack is not None and stack._version != ctx.out_stack_version:
-            raise RuntimeError('stc_cell_graph: the returned state stack was modified in place after the forward pass; the states saved for '
-                               'backward share its storage (treat the stack as read-only, or clone it before editing)')
-        sv = list(ctx.saved_tensors)
-        Tc = sv.pop(0)
-        stacks = []
-        for pres in present:
-            st = [sv.pop(0) if p else None for p in pres]
-            stacks.append(st)
-        cells, at = [], 0
-        for cnt in n_saved:
-            cells.append(sv[at:at + abs(cnt)])
-            at += abs(cnt)
-        h = 16
-        rows = lambda ts: [t.view(B * N, C, t.shape[-1]) for t in ts]
-        bwd = (op.bwd_rowptr, op.bwd_colidx, op.bwd_val)
-        G = {}                                                       # cell -> gradient its state is owed so far
+        op, Ks, schedule, outputs, cin, n_sets, dims, forms = ctx.meta
+        _check_guard(ctx)
+        Tc, *sv = ctx.saved_tensors
+        stacks, sv = _stacks(sv[:4 * n_sets]), sv[4 * n_sets:]
+        cells = []
+        for f in forms:                                              # what each cell saved, by its form
+            cells, sv = cells + [sv[:f.saved(Ks)]], sv[f.saved(Ks):]
+        p = _BackwardPass(k, op, Ks, Tc, schedule, stacks, cin, forms, dims, bf16, ctx.zmax_all)
         grad_stack = _c(grad_stack)
         for i, j in enumerate(outputs):
-            G[j] = grad_stack[i]                                     # read-only here: sums go to fresh buffers
-        acc = [[None] * 4 for _ in stacks]
-        # Parameter gradients of the planar cells: every cell writes its (dWg, dbg, dWc, dbc) into its own row of ONE buffer per parameter
-        # set, summed once at the end -- instead of four accumulation passes per cell (176 five-microsecond launches per metric step).
-        rows_of_set = {}
+            p.G[j] = grad_stack[i]                                   # read-only here: sums go to fresh buffers
+        acc = [[None] * 4 for _ in stacks]                           # parameter gradients of the interleaved cells, then of the planar ones
 
-        def grads_for(s_id):
-            Wg_, bg_, Wc_, bc_ = stacks[s_id]
-            sizes = [Wg_.numel(), 0 if bg_ is None else 2 * h, Wc_.numel(), 0 if bc_ is None else h]
-            if s_id not in rows_of_set:
-                n = sum(1 for sc in schedule if sc[0] == s_id)
-                rows_of_set[s_id] = [Wg_.new_zeros(n, sum(sizes)), 0, sizes]
-            buf, i, _ = rows_of_set[s_id]
-            rows_of_set[s_id][1] = i + 1
-            parts = buf[i].split(sizes)
-            return (parts[0].view_as(Wg_), None if bg_ is None else parts[1], parts[2].view_as(Wc_), None if bc_ is None else parts[3])
-
-        def add_to(slot, i, t):
-            if t is not None:
-                slot[i] = t if slot[i] is None else slot[i].add_(t)
-
-        def narrow_transpose_aggregation(dY):                        # dBm = S^T dY on rows of C*h floats
-            dBm = torch.empty_like(dY)
-            k.csr_spmm(*bwd, N, N, dY.view(B, N, C * h), None, dBm.view(B, N, C * h), 1.0, 0.0, plan=op.bwd_plan)
-            return dBm
-
-        # Planar consumers leave PIECES of a state's gradient instead of a finished tensor: direct planes (what the state
-        # is owed as a plane of their inputs) and aggregated planes (what its aggregation S.state is owed).  Aggregation
-        # being linear, the state's gradient is  sum(direct) + S^T sum(aggregated): ONE narrow SpMM per state with the
-        # sums in its gather / epilogue -- instead of a wide transpose SpMM and a split pass per consuming cell.
-        pieces = {}
-
-        def leave(kid, direct, aggregated):
-            pc = pieces.setdefault(kid, dict(direct=[], agg=[]))
-            pc['direct'] += [(t, 0) for t in direct]
-            pc['agg'].append(aggregated)
-
-        # fp16 x 2 operand format: the backward launches scale the activation operands of their dW products by the plane maxima the forward
-        # launches left (gradient scales they find themselves, per node)
-        zmax_all = ctx.zmax_all
-
-        def act_slots(j, which=0):                                   # what cell j's forward launches left
-            return {} if zmax_all is None else dict(act_amax=zmax_all[j, which])
-
-        def owed(kid, blend=None):
-            """The gradient of state ``kid``; with ``blend`` = (U, Cand) of its cell also dY = gradient * U * (1 - Cand^2)."""
-            base = G.pop(kid, None)                                  # from interleaved consumers / the outputs: a finished tensor
-            pc = pieces.pop(kid, None)
-            if pc is None:
-                if blend is None:
-                    return base
-                dY = torch.empty_like(base)
-                k.gru_blend_bwd(base, blend[0], None, blend[1], dY, None, None)
-                return base, dY
-            add = pc['direct'] + ([(base, 0)] if base is not None else [])
-            aggs = pc['agg']
-            while len(add) > 5:                                      # more consumers than the kernel takes addends for: pre-sum
-                (a, ao), (b_, bo) = add.pop(), add.pop()
-                add.append((a[..., ao:ao + h] + b_[..., bo:bo + h], 0))
-            while len(aggs) > 2:
-                aggs = [aggs[0] + aggs[1]] + aggs[2:]
-            out = aggs[0].new_empty(B, N, C, h)
-            dY = torch.empty_like(out) if blend is not None else None
-            k.spmm_sum(*bwd, op.bwd_plan, aggs[0], aggs[1] if len(aggs) > 1 else None, add, out,
-                       blend=None if blend is None else (blend[0], blend[1], dY))
-            return out if blend is None else (out, dY)
-
-        def owed_ring2(kid, U_, Cand_):
-            """(gradient of state ``kid``, S^T (gradient * U * (1 - Cand^2))) in one launch where the graph has a two-ring plan and the state's
-            pieces are whole planes; None: the two launches (``owed`` with its blend epilogue, then the narrow aggregation)."""
-            pc = pieces.get(kid)
-            if pc is None or op.bwd_ring2 is None or not hasattr(k, 'ring2_sum') or not k.ring2_fits(B, N, C, h):
-                return None
-            base = G.get(kid)
-            add = [t for t, off in pc['direct'] if off == 0 and t.shape[-1] == h] + ([base] if base is not None else [])
-            # (the forms that fit the register file: one aggregated plane, up to two addends -- 590 / 680 us for the 555 + 185 they replace; with a
-            #  second aggregated plane the kernel spills and takes 840 - 1 150 us: the two launches stay)
-            if len(add) != len(pc['direct']) + (base is not None) or len(add) > 2 or len(pc['agg']) != 1:
-                return None
-            G.pop(kid, None)
-            pieces.pop(kid)
-            aggs = pc['agg']
-            out, dBm_ = aggs[0].new_empty(B, N, C, h), aggs[0].new_empty(B, N, C, h)
-            k.ring2_sum(*bwd, op.bwd_ring2, aggs[0], aggs[1] if len(aggs) > 1 else None, add, U_, Cand_, out, dBm_)
-            return out, dBm_
-
-        # Order 3: a consumer leaves direct planes d0 and the gradients d1, d2 of the S / T_2(S) planes; the source's gradient is
-        #   sum d0 - sum d2 + S^T (sum d1 + 2 S^T sum d2)          (Clenshaw form of sum_n T_n(S)^T d_n)
-        # = two narrow SpMMs with the sums in their gather / epilogue (alpha and signed addends of stc_spmm_sum_f32).
-        def leave3(kid, d0, d1, d2):
-            pc = pieces.setdefault(kid, dict(d0=[], d1=[], d2=[]))
-            pc['d0'] += list(d0); pc['d1'] += list(d1); pc['d2'] += list(d2)
-
-        def clenshaw(d0, d1, d2, blend=None):
-            """sum d0 - sum d2 + S^T (sum d1 + 2 S^T sum d2) from lists of planes (d2 non-empty); with ``blend`` = (U, Cand) also
-            dY = result * U * (1 - Cand^2) from the second launch's epilogue."""
-            while len(d2) > 2:                                       # the kernel gathers two operands: pre-sum the rest
-                d2 = [d2[0] + d2[1]] + d2[2:]
-            if (_RING2 and blend is None and not bf16_planes and op.bwd_ring2 is not None and hasattr(k, 'ring2_chain') and k.ring2_fits(B, N, C, h) and len(d1) <= 2
-                    and 1 <= len(d0) + len(d2) <= k.RING2_MAX_ADD):
-                # both transpose aggregations in one launch (stc_ring2_chain_f32): the inner sum d1 + 2 S^T d2 never leaves the chip
-                out = d2[0].new_empty(B, N, C, h)
-                k.ring2_chain(*bwd, op.bwd_ring2, d2[0], d2[1] if len(d2) > 1 else None, 2.0, list(d1), None, 1.0,
-                              [(a, 1.0) for a in d0] + [(a, -1.0) for a in d2], out)
-                return out
-            t = d2[0].new_empty(B, N, C, h)
-            k.spmm_sum(*bwd, op.bwd_plan, d2[0], d2[1] if len(d2) > 1 else None, [(a, 0) for a in d1], t, alpha=2.0)
-            adds = [(a, 0) for a in d0] + [(a, 0, -1.0) for a in d2]
-            while len(adds) > 8:
-                (a, _), (b_, _) = adds.pop(0), adds.pop(0)
-                adds.insert(0, (a + b_, 0))
-            out = t.new_empty(B, N, C, h)
-            dY = torch.empty_like(out) if blend is not None else None
-            k.spmm_sum(*bwd, op.bwd_plan, t, None, adds, out, blend=None if blend is None else (blend[0], blend[1], dY))
-            return out if blend is None else (out, dY)
-
-        def owed3(kid, blend=None):
-            base = G.pop(kid, None)
-            pc = pieces.pop(kid, None)
-            if pc is None:
-                if blend is None:
-                    return base
-                dY = torch.empty_like(base)
-                k.gru_blend_bwd(base, blend[0], None, blend[1], dY, None, None)
-                return base, dY
-            return clenshaw(pc['d0'] + ([base] if base is not None else []), pc['d1'], pc['d2'], blend)
+        def add_to(s_id, grads):
+            acc[s_id] = [a if t is None else t if a is None else a.add_(t) for a, t in zip(acc[s_id], grads)]
 
         for j in range(len(schedule) - 1, -1, -1):
-            if j not in G and j not in pieces:
+            if j not in p.G and j not in p.pieces:
                 continue                                             # nothing downstream depends on this cell
-            s_id, x, hs = schedule[j]
-            Wg, bg, Wc, bc = stacks[s_id]
-            Hprev, U, Rg, Cand, *rest = cells[j]
-            if n_saved[j] == -12:                                    # order-3 planar cell
-                Zx, Zh = rest[:3], [Hprev] + rest[3:5]
-                wide = cin[j] == h
-                new = lambda: torch.empty_like(Hprev)
-                dWg, dbg, dWc, dbc = grads_for(s_id)
-                Zr = rest[5:8]                                       # slab-planar candidate
-                dHnew = owed3(j)
-                dXc, dR = ([new(), new(), new()] if wide else [None] * 3), [new(), new(), new()]
-                k.cell_cand_bwd_planar_k(rows(Zx), rows(Zr), Tc, Wc, *rows((dHnew, U, Cand)),
-                                         [None if t is None else t.view(B * N, C, h) for t in dXc], rows(dR), dWc, dbc, **act_slots(j, 1))
-                # gradient of the R*H plane from its three Chebyshev planes
-                dRH = clenshaw([dR[0]], [dR[1]], [dR[2]])
-                del dR
-                fold = getattr(k, 'folds_dH', False)                  # the kernel adds the prologue's share into the H plane's gradient
-                # slab-planar candidate on a wide input: the gates' X-side gradients are ADDED into the candidate's three planes by the
-                # kernel (accumulate_x), so the source gets one plane per order from this cell and its Clenshaw sums need no pre-sum
-                into = fold and wide
-                dXg = dXc if into else ([new(), new(), new()] if wide else [None] * 3)
-                dHg, dH = [new(), new(), new()], (None if fold else new())
-                k.cell_gates_bwd_planar_k(rows(Zx), rows(Zh), Tc, Wg, *rows((dRH, Cand, U, Rg, dHnew)),
-                                          [None if t is None else t.view(B * N, C, h) for t in dXg], rows(dHg), dWg, dbg,
-                                          None if fold else dH.view(B * N, C, h), accumulate_x=into, **act_slots(j, 0))
-                if into:
-                    dXc = [None] * 3
-                if wide and x[0] == 'cell':
-                    leave3(x[1], [t for t in (dXg[0], dXc[0]) if t is not None], [t for t in (dXg[1], dXc[1]) if t is not None],
-                           [t for t in (dXg[2], dXc[2]) if t is not None])
-                if hs[0] == 'cell':
-                    leave3(hs[1], (dHg[0],) if fold else (dHg[0], dH), (dHg[1],), (dHg[2],))
-                continue                                             # (parameter gradients: rows of the set's buffer, summed at the end)
-            post_form = n_saved[j] < 0 or (len(rest) == Ks + 1 and Ks > 1)     # candidate backward starts from dY = dHnew * U * (1 - Cand^2)
-            if Ks == 3 and j in pieces:                              # an interleaved cell whose state order-3 planar cells consumed
-                G[j] = owed3(j)
-            dBm = None
-            if n_saved[j] == -7 and _RING2 and not bf16_planes:     # state gradient + S^T dY in one launch, no dY plane (stc_ring2_sum_f32)
-                fused = owed_ring2(j, U, Cand)
-                if fused is not None:
-                    dHnew, dBm = fused
-                    dY = None
-            if dBm is None:
-                dHnew, dY = owed(j, (U, Cand)) if post_form else (owed(j), None)
-            dH = None if (n_saved[j] == -7 or (n_saved[j] < 0 and getattr(k, 'folds_dH', False))) else torch.empty_like(Hprev)
-            if n_saved[j] == -7:                                     # planar cell, candidate + gates backward in ONE launch
-                Xp, SXp, SHp = rest
-                if dBm is None:
-                    dBm = narrow_transpose_aggregation(dY)
-                del dY                                               # (the kernel re-forms dY from dHnew, U, Cand)
-                wide = cin[j] == h
-                new = lambda: torch.empty_like(Hprev)
-                dWg, dbg, dWc, dbc = grads_for(s_id)
-                # A state has two consumers (next step as H, next layer as X): the first one processed writes the state's direct and
-                # aggregated gradient planes, the second ADDS into them (accumulate_x / accumulate_h), so the state-gradient SpMM gathers
-                # one operand instead of two and reads one direct plane instead of two.
-                taken = set()
-
-                def planes_of_state(src):
-                    if src[0] != 'cell':
-                        return new(), new(), False                   # an external tensor: gradients computed, nobody owed
-                    pc = pieces.get(src[1])
-                    if _ACC_PLANES and not bf16_planes and pc is not None and pc.get('own') is not None and src[1] not in taken:
-                        taken.add(src[1])
-                        return pc['own'][0], pc['own'][1], True
-                    d, a_ = new(), new()
-                    leave(src[1], (d,), a_)
-                    if pieces[src[1]].get('own') is None:
-                        pieces[src[1]]['own'] = (d, a_)
-                        taken.add(src[1])
-                    return d, a_, False
-
-                dXd, dSX, acc_x = planes_of_state(x) if wide else (None, None, False)
-                dHd, dSH, acc_h = planes_of_state(hs)
-                k.cell_bwd_planar(*rows((Xp, Hprev, SXp, SHp)), Tc, Wg, Wc, *rows((U, Rg, Cand, dHnew, dBm)),
-                                  [None if t is None else t.view(B * N, C, h) for t in (dXd, dSX, dHd, dSH)], dWg, dbg, dWc, dbc,
-                                  **(dict(accumulate_x=acc_x, accumulate_h=acc_h, **act_slots(j)) if not bf16_planes else {}))
-                continue                                             # (parameter gradients: rows of the set's buffer, summed at the end)
-            if n_saved[j] < 0:                                       # planar cell: inputs and gradients as planes
-                Xp, SXp, SHp, RH = rest
-                wide = cin[j] == h                                   # else: narrow input plane (layer 0), which needs no gradient
-                post_kw, gates_kw = {}, {}
-                if zmax_all is not None:
-                    # the candidate's input planes are (X, R*H): X's maximum as the gates forward left it, R*H rides on H's (|R*H| <= |H|).  Slot
-                    # rows of that launch: wide {X, S.X, H, S.H}, narrow {H, S.H, x, S.x}; the post kernel takes (16-wide plane, other plane).
-                    zr = zmax_all[j, 0]
-                    post_kw.update(act_amax=(zr[0], zr[2]))
-                    gates_kw.update(act_amax=zr)
-                dBm = narrow_transpose_aggregation(dY)
-                dRH = torch.empty_like(Hprev)
-                dWg, dbg, dWc, dbc = grads_for(s_id)
-                dHd, dSH = torch.empty_like(Hprev), torch.empty_like(Hprev)
-                if wide:
-                    dXc, dXd, dSX = (torch.empty_like(Hprev) for _ in range(3))
-                    k.node_post_bwd(*rows((Xp,)), Tc, Wc, *rows((dY, dBm, dXc)), dWc, dbc, X2=RH.view(B * N, C, h), dX2=dRH.view(B * N, C, h), **post_kw)
-                    planes = rows((dXd, dSX, dHd, dSH))
-                else:
-                    k.node_post_bwd(*rows((RH,)), Tc, Wc, *rows((dY, dBm, dRH)), dWc, dbc, X2=Xp.view(B * N, C, cin[j]), **post_kw)
-                    planes = [None, None] + rows((dHd, dSH))
-                del dY, dBm
-                fold = getattr(k, 'folds_dH', False)                 # the kernel adds the prologue's share into the H plane's gradient
-                k.cell_gates_bwd_planar(*rows((Xp, Hprev, SXp, SHp)), Tc, Wg, *rows((dRH, Cand, U, Rg, dHnew)), planes, dWg, dbg,
-                                        None if fold else dH.view(B * N, C, h), **gates_kw)
-                if wide and x[0] == 'cell':
-                    leave(x[1], (dXd, dXc), dSX)                     # as the X plane: gates' and candidate's direct shares
-                if hs[0] == 'cell':
-                    leave(hs[1], (dHd,) if fold else (dHd, dH), dSH)  # as the H plane: direct share + what the gates prologue owes it
-                continue                                             # (parameter gradients: rows of the set's buffer, summed at the end)
-            else:
-                Zg, Zc = rest[:Ks], rest[Ks:]
-                L = Zc[0].shape[-1]
-                if len(Zc) == 1 and Ks > 1:                         # the forward ran this convolution as Y = A + S.Bm (no Z_1 slab)
-                    dBm = narrow_transpose_aggregation(dY)
-                    dci, dWc = torch.empty_like(Zc[0]), torch.empty_like(Wc)
-                    dbc = Wc.new_empty(h) if bc is not None else None
-                    k.node_post_bwd(*rows((Zc[0],)), Tc, Wc, *rows((dY, dBm, dci)), dWc, dbc)
-                else:                                               # slab form, blend backward in the node kernel's prologue
-                    g, dWc, dbc, _, _ = _bdg_backward_slabs(None, Zc, Wc, Tc, op, Ks, bc is not None, False, False, cand=(dHnew, U, Cand))
-                    if Ks > 1:
-                        k.csr_spmm(*bwd, N, N, g[1].view(B, N, C * L), g[0].view(B, N, C * L), g[0].view(B, N, C * L), 1.0, 1.0, plan=op.bwd_plan)
-                    dci = g[0]
-                # gates convolution, gate + blend backward in its prologue
-                g, dWg, dbg, _, _ = _bdg_backward_slabs(None, Zg, Wg, Tc, op, Ks, bg is not None, False, False,
-                                                        gates=(dci, Cand, Hprev, U, Rg, dHnew, dH))
-            v3 = lambda t: t.view(B, N, C * L)
-            need_x, need_h = x[0] == 'cell', hs[0] == 'cell'
-            if need_x or need_h:
-                if Ks > 1:
-                    k.csr_spmm(*bwd, N, N, v3(g[1]), v3(g[0]), v3(g[0]), 1.0, 1.0, plan=op.bwd_plan)
-                dXt = Hprev.new_empty(Hprev.shape[:-1] + (cin[j],))
-                same = need_x and need_h and x[1] == hs[1]
-                owedA = G.get(x[1]) if need_x else None
-                owedB = G.get(hs[1]) if (need_h and not same) else None
-                k.split2(g[0], dXt, dH, addA=dci, addB=dH, addA_ld=L, addA2=owedA, addB2=owedB)
-                if same:
-                    G[x[1]] = dXt.add_(dH)
-                else:
-                    if need_x:
-                        G[x[1]] = dXt
-                    if need_h:
-                        G[hs[1]] = dH
-            for i, t in enumerate((dWg, dbg, dWc, dbc)):
-                add_to(acc[s_id], i, t)
-        for s_id, (buf, used, sizes) in rows_of_set.items():
-            Wg_, bg_, Wc_, bc_ = stacks[s_id]
-            parts = (buf[0] if buf.shape[0] == 1 else buf.sum(0)).split(sizes)
-            for i, t in enumerate((parts[0].view_as(Wg_), None if bg_ is None else parts[1], parts[2].view_as(Wc_), None if bc_ is None else parts[3])):
-                add_to(acc[s_id], i, t)
-        flat = []
-        for st, a in zip(stacks, acc):
-            for p, gsum in zip(st, a):
-                flat.append(None if p is None else (gsum if gsum is not None else torch.zeros_like(p)))
+            s_id, f = schedule[j][0], forms[j]
+            run = {_Form.PLANAR3: p.planar3, _Form.PLANAR_ONE_BWD: p.planar_one_bwd, _Form.PLANAR: p.planar}.get(f, p.rows_cell)
+            grads = run(j, *stacks[s_id], cells[j])
+            if not f.planar:
+                add_to(s_id, grads)
+        for s_id, (buf, _, _) in p.rows_of_set.items():
+            add_to(s_id, p.param_views(s_id, buf[0] if buf.shape[0] == 1 else buf.sum(0)))
+        flat = [None if prm is None else (g if g is not None else torch.zeros_like(prm)) for st, a in zip(stacks, acc) for prm, g in zip(st, a)]
         n_ext = len(ctx.needs_input_grad) - 7 - len(flat)
         return (None,) * 7 + (None,) * n_ext + tuple(flat)
 

@@ -46,19 +46,50 @@ def small_graph_supported(k, op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_
     return all(k.cell_small_supported(Ks, Tc.shape[0], C, w, h, op.n) for w in set(x_widths))
 
 
-def _alias(base: torch.Tensor) -> torch.Tensor:
-    """The same storage as a tensor of its own (not a view in autograd's books): saved for backward while ``base`` is the node's output."""
+# ---- what both cell-graph executors (this one and ``ops._StcCellGraph``) share
+def _alias(base: torch.Tensor, i=None) -> torch.Tensor:
+    """``base`` (or base[i]) as a tensor of its own that shares the storage WITHOUT being a view of ``base`` in autograd's books: saved for
+    backward while ``base`` is the node's output, which view tracking forbids."""
+    off, shape, stride = (0, base.shape, base.stride()) if i is None else (i * base.stride(0), base.shape[1:], base.stride()[1:])
     t = base.new_empty(0)
-    t.set_(base.untyped_storage(), base.storage_offset(), base.shape, base.stride())
+    t.set_(base.untyped_storage(), base.storage_offset() + off, shape, stride)
     return t
+
+
+def _stacks(flat):
+    """[(Wg, bg, Wc, bc)] per parameter set from their flat sequence (absent biases: None, saved for backward as such)."""
+    return [tuple(flat[i:i + 4]) for i in range(0, len(flat), 4)]
+
+
+def _unpack(n_ext: int, Tc, fwd_val, tensors):
+    """(ext, stacks, Tc, fwd_val), contiguous, from an executor's arguments: the external tensors, then the parameter sets' flat sequence."""
+    return [_c(t) for t in tensors[:n_ext]], _stacks([None if p is None else _c(p) for p in tensors[n_ext:]]), _c(Tc), _c(fwd_val)
+
+
+def _out_slots(outputs):                                        # output cell -> its slot in the returned stack
+    out_slot = {j: i for i, j in enumerate(outputs)}
+    if len(out_slot) != len(outputs):
+        raise ValueError('stc_cell_graph: duplicate output cells')
+    return out_slot
+
+
+def _guard(ctx, out_stack):
+    """The saved states of the output cells ALIAS the returned stack's storage without sharing its autograd version counter: the stack is
+    read-only for its consumers; ``_check_guard`` checks its version in backward (weak: no output -> ctx -> output cycle)."""
+    ctx.out_stack_ref, ctx.out_stack_version = weakref.ref(out_stack), out_stack._version
+
+
+def _check_guard(ctx):
+    stack = ctx.out_stack_ref()
+    if stack is not None and stack._version != ctx.out_stack_version:
+        raise RuntimeError('stc_cell_graph: the returned state stack was modified in place after the forward pass; the states saved for '
+                           'backward share its storage (treat the stack as read-only, or clone it before editing)')
 
 
 def _layout(schedule, cin, n_cells, outputs):
     """Where every cell's tensors live: slot in the output stack or the inner-state buffer, position inside its width group (cells whose
     input is 16 columns wide / 1..4 columns wide keep their aggregates in two buffers of different row widths)."""
-    out_slot = {j: i for i, j in enumerate(outputs)}
-    if len(out_slot) != len(outputs):
-        raise ValueError('stc_cell_graph: duplicate output cells')
+    out_slot = _out_slots(outputs)
     pos, counts, inner_slot, nxt = [None] * n_cells, [0, 0], {}, 0
     # inside a width group the cells of ONE parameter set sit side by side (set by set, each in schedule order): the products over a set's
     # cells -- the learned graphs' dT_c through stc_mix_dt_f32 -- then take one contiguous run of planes (in schedule order the decoder's two
@@ -79,10 +110,7 @@ class _StcSmallGraph(Function):
 
     @staticmethod
     def forward(ctx, k, op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, *tensors):
-        ext = [_c(t) for t in tensors[:n_ext]]
-        flat = tensors[n_ext:]
-        stacks = [tuple(None if p is None else _c(p) for p in flat[i:i + 4]) for i in range(0, len(flat), 4)]   # (Wg, bg, Wc, bc)
-        Tc, fwd_val = _c(Tc), _c(fwd_val)
+        ext, stacks, Tc, fwd_val = _unpack(n_ext, Tc, fwd_val, tensors)
         n_cells = len(schedule)
         ref = ext[0]
         B, N, C = ref.shape[:3]
@@ -127,30 +155,21 @@ class _StcSmallGraph(Function):
                 extra = dict(graph2=(g2['fwd2_rowptr'], g2['fwd2_colidx'], g2['fwd2_val']), Zg2=slabs[w][1, i], Zc2=Zc2[0][j].view(B, N * C, H16))
             k.cell_small_fwd(op.fwd_rowptr, op.fwd_colidx, fwd_val, source(x), source(hs), Tc, Wg, bg, Wc, bc, U[j], R[j], Cand[j], state[j], RH[j],
                              slabs[w][0, i], Zc[j].view(B, N * C, H16), checked=False, splits=fwd_splits, **extra)
-        ctx.save_for_backward(Tc, out_alias, inner, planes, slabs[0], slabs[1], *ext, *[p for st in stacks for p in st if p is not None])
-        ctx.meta = (k, op, Ks, list(schedule), tuple(outputs), cin, [tuple(p is not None for p in st) for st in stacks], (B, N, C), len(ext), splits)
-        ctx.out_stack_ref, ctx.out_stack_version = weakref.ref(out_stack), out_stack._version
+        ctx.save_for_backward(Tc, out_alias, inner, planes, slabs[0], slabs[1], *ext, *[p for st in stacks for p in st])
+        ctx.meta = (k, op, Ks, list(schedule), tuple(outputs), cin, (B, N, C), len(ext), splits)
+        _guard(ctx, out_stack)
         return out_stack
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_stack):
-        k, op, Ks, schedule, outputs, cin, present, (B, N, C), n_ext, splits = ctx.meta
-        stack = ctx.out_stack_ref()
-        if stack is not None and stack._version != ctx.out_stack_version:
-            raise RuntimeError('stc_cell_graph: the returned state stack was modified in place after the forward pass; the states saved for '
-                               'backward share its storage (treat the stack as read-only, or clone it before editing)')
+        k, op, Ks, schedule, outputs, cin, (B, N, C), n_ext, splits = ctx.meta
+        _check_guard(ctx)
         Tc, out_alias, inner, planes, slabs_n, slabs_w, *rest = ctx.saved_tensors
         slabs = (slabs_n, slabs_w)
         need_Tc, need_val = ctx.needs_input_grad[6], ctx.needs_input_grad[7]
         learned = bool(need_Tc or need_val)
-        ext, rest = rest[:n_ext], rest[n_ext:]
-        stacks = []
-        for pres in present:
-            st = []
-            for p in pres:
-                st.append(rest.pop(0) if p else None)
-            stacks.append(st)
+        ext, stacks = rest[:n_ext], _stacks(rest[n_ext:])
         n_cells = len(schedule)
         out_slot, inner_slot, pos, counts = _layout(schedule, cin, n_cells, outputs)
         state = [out_alias[out_slot[j]] if j in out_slot else inner[inner_slot[j]] for j in range(n_cells)]
