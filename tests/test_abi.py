@@ -19,6 +19,16 @@ def _declared_symbols():
 
 def test_header_and_python_export_lists_agree():
     assert _declared_symbols() == sorted(_lib.EXPORTS)
+    # ... and so do the constants the host side mirrors
+    header = open(os.path.join(REPO, 'include', 'stc_hip.h')).read()
+    mirrored = {'STC_ABI_VERSION': _lib.ABI_VERSION, 'STC_MAX_K': _lib.MAX_K, 'STC_FMT_BF16X3': _lib.FMT_BF16X3, 'STC_FMT_F16X2': _lib.FMT_F16X2,
+                'STC_ACT_AMAX_SLOTS': _lib.HipKernels.ACT_AMAX_SLOTS, 'STC_SPMM_SUM_MAX_ADD': _lib.SPMM_SUM_MAX_ADD,
+                'STC_PATCH_ROWS': _lib.PATCH_ROWS, 'STC_PATCH_MAX_SRC': _lib.PATCH_MAX_SRC,
+                'STC_RING2_INTERIOR': _lib.RING2_INTERIOR, 'STC_RING2_FIRST': _lib.RING2_FIRST, 'STC_RING2_SECOND': _lib.RING2_SECOND,
+                'STC_RING2_WIDTH': _lib.RING2_WIDTH}
+    for name, value in mirrored.items():
+        defined = re.findall(rf'^#define\s+{name}\s+(\d+)\b', header, flags=re.M)
+        assert defined == [str(value)], f'{name}: header {defined}, _lib.py {value}'
 
 
 def test_library_loads_and_exports_every_declared_symbol():
@@ -111,17 +121,20 @@ def test_row_block_plan_reconstructs_the_graph():
 
 
 def test_ctypes_signatures_match_the_header():
-    """Every prototype in include/stc_hip.h has the same number and kinds of parameters as its ctypes argtypes
-    (a mismatch only shows up as a TypeError at the first launch on the GPU box otherwise)."""
+    """Every prototype in include/stc_hip.h has the same return kind and the same number and kinds of parameters as its
+    ctypes restype / argtypes (a parameter mismatch only shows up as a TypeError at the first launch on the GPU box otherwise,
+    a size_t read as int as a truncated workspace size)."""
     import ctypes as C
     text = open(os.path.join(REPO, 'include', 'stc_hip.h')).read()
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
     lib = _lib.load_library()
-    protos = re.findall(r'\b(?:int|size_t|const char\*)\s+(stc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', text)
+    protos = re.findall(r'\b(int|size_t|const char\*)\s+(stc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', text)
     assert len(protos) == len(_lib.EXPORTS)
+    returns = {'int': C.c_int, 'size_t': C.c_size_t, 'const char*': C.c_char_p}
     kind = {C.c_void_p: 'ptr', C.c_int32: 'i32', C.c_int64: 'i64', C.c_float: 'f32', C.c_double: 'f64', C.c_size_t: 'size', C.POINTER(C.c_void_p): 'ptr',
             C.POINTER(C.c_int32): 'ptr', C.POINTER(C.c_float): 'ptr'}
-    for name, params in protos:
+    for ret, name, params in protos:
+        assert getattr(lib, name).restype is returns[ret], f'{name}: ctypes restype {getattr(lib, name).restype} vs header {ret}'
         want = []
         for prm in [q.strip() for q in params.split(',') if q.strip() and q.strip() != 'void']:
             if '*' in prm:
