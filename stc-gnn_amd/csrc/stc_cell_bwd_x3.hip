@@ -498,15 +498,10 @@ int launch_cell_bwd(const CellBwdArgs& a, int* n_partials, hipStream_t stream) {
     const size_t lds = cb_lds_bytes<F>() > slabs ? cb_lds_bytes<F>() : slabs;
     static_assert(cb_lds_bytes<F>() <= stc::kMaxLdsBytes, "tables + per-wave tiles must fit the CU's LDS");
     if (lds > stc::kMaxLdsBytes) return STC_NOT_HANDLED;
-    auto kern = cell_bwd_x3_kernel<F, L, PL, ACCX, ACCH>;
-    if (int rc = stc::hip_status(stc::allow_lds(kern, lds), "hipFuncSetAttribute(cell bwd x3)")) return rc;
-    static const int resident = stc::resident_blocks(kern, CB_THREADS, lds, 1);      // (one static per instantiation)
-    const long long want = (a.nodes + CB_WAVES - 1) / CB_WAVES;
-    int grid = resident < MF_BWD_MAX_GRID ? resident : MF_BWD_MAX_GRID;
-    if (want < grid) grid = (int)want;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(CB_THREADS), lds, stream, a);
+    constexpr auto kern = cell_bwd_x3_kernel<F, L, PL, ACCX, ACCH>;
+    if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(cell bwd x3)", CB_THREADS, lds, 1, a.nodes, CB_WAVES, MF_BWD_MAX_GRID, n_partials)) return rc;
+    hipLaunchKernelGGL(kern, dim3(*n_partials), dim3(CB_THREADS), lds, stream, a);
     STC_LAUNCH_CHECK("cell_bwd_x3 launch");
-    *n_partials = grid;
     return STC_OK;
 }
 

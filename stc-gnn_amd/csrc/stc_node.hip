@@ -18,8 +18,7 @@
 // This file is the general fp32 VALU version (LDS-tiled, persistent workgroups);
 // weight-gradient partials are summed in a fixed order by a second kernel, so
 // results are bitwise reproducible.
-#include "stc_common.h"
-#include "stc_node_mfma.h"
+#include "stc_node_host.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -412,7 +411,7 @@ extern "C" int stc_cell_gates_fwd_f32(const float* const* Z, int32_t Ks, const f
     int rc = STC_NOT_HANDLED;
     if (x3_enabled()) rc = stc_cell_gates_fwd_x3(Z, Ks, Tc, W, bias, H, U, Rg, CandIn, nodes, C, L, Lw, cin, static_cast<hipStream_t>(stream));
     if (rc == STC_NOT_HANDLED) rc = stc_cell_gates_fwd_mfma(Z, Ks, Tc, W, bias, H, U, Rg, CandIn, nodes, C, L, Lw, cin, static_cast<hipStream_t>(stream));
-    return rc == STC_NOT_HANDLED ? stc::fail(STC_EUNSUPPORTED, "stc_cell_gates_fwd_f32: operands not usable by the fused path (alignment)") : rc;
+    return stc::dispatched(__func__, rc);
 }
 
 extern "C" int stc_cell_gates_bwd_f32(const float* const* Z, int32_t Ks, const float* Tc, int32_t Kc, const float* W,
@@ -425,33 +424,22 @@ extern "C" int stc_cell_gates_bwd_f32(const float* const* Z, int32_t Ks, const f
     if (!stc_cell_fused_supported(Ks, Kc, C, L, h)) return stc::fail(STC_EUNSUPPORTED, "stc_cell_gates_bwd_f32: shape not on the fused path");
     STC_REQUIRE(Z && W && dZ && dW && (Kc == 1 || Tc), STC_EINVAL, "stc_cell_gates_bwd_f32: null Z/W/dZ/dW/Tc");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nW = Ks * Kc * Lw * 2 * h, Ho = 2 * h;
-    if (nodes == 0) {
-        if (int rc = stc::hip_status(hipMemsetAsync(dW, 0, (size_t)nW * sizeof(float), s), "memset dW")) return rc;
-        if (db) if (int rc = stc::hip_status(hipMemsetAsync(db, 0, (size_t)Ho * sizeof(float), s), "memset db")) return rc;
-        return STC_OK;
-    }
+    const int Ho = 2 * h;
+    stc::ParamGrad g{dW, db, Ks * Kc * Lw * Ho, Ho, stc_bdg_node_bwd_workspace_bytes(Ks, Kc, C, L, Ho, 0)};
+    bool done;
+    if (int rc = stc::grad_tail_begin(__func__, &g, 1, nodes, workspace, workspace_bytes, STC_EALIGN, s, &done); rc || done) return rc;
     STC_REQUIRE(dCandIn && H && U && Rg && dH, STC_EINVAL, "stc_cell_gates_bwd_f32: null pointer");      // dXt may be null (not wanted)
     STC_REQUIRE((dU != nullptr) != (Cand != nullptr), STC_EINVAL, "stc_cell_gates_bwd_f32: give either dU or Cand (dU is then formed from dH_in = dHnew)");
     STC_REQUIRE(!Cand || dH_in, STC_EINVAL, "stc_cell_gates_bwd_f32: Cand needs dH_in = gradient of the new state");
     for (int n = 0; n < Ks; ++n) STC_REQUIRE(Z[n] && dZ[n], STC_EINVAL, "stc_cell_gates_bwd_f32: Z[%d]/dZ[%d] is null", n, n);
-    STC_REQUIRE(workspace && stc::aligned16(workspace), STC_EALIGN, "stc_cell_gates_bwd_f32: workspace null or not 16-byte aligned");
-    STC_REQUIRE(workspace_bytes >= stc_bdg_node_bwd_workspace_bytes(Ks, Kc, C, L, Ho, 0), STC_EINVAL,
-                "stc_cell_gates_bwd_f32: workspace of %zu B is too small", workspace_bytes);
     int n_parts = 0;
-    float* partial = static_cast<float*>(workspace);
     int rc = STC_NOT_HANDLED;
-    if (x3_enabled()) rc = stc_cell_gates_bwd_x3(Z, Ks, Tc, W, dCandIn, dU, H, U, Rg, dH_in, Cand, dZ, dXt, dH, partial, &n_parts, db != nullptr,
+    if (x3_enabled()) rc = stc_cell_gates_bwd_x3(Z, Ks, Tc, W, dCandIn, dU, H, U, Rg, dH_in, Cand, dZ, dXt, dH, g.partial, &n_parts, db != nullptr,
                                                  nodes, C, L, Lw, cin, dH_in_scaled != 0, s);
-    if (rc == STC_NOT_HANDLED) rc = stc_cell_gates_bwd_mfma(Z, Ks, Tc, W, dCandIn, dU, H, U, Rg, dH_in, Cand, dZ, dXt, dH, partial, &n_parts, db != nullptr,
+    if (rc == STC_NOT_HANDLED) rc = stc_cell_gates_bwd_mfma(Z, Ks, Tc, W, dCandIn, dU, H, U, Rg, dH_in, Cand, dZ, dXt, dH, g.partial, &n_parts, db != nullptr,
                                                             nodes, C, L, Lw, cin, dH_in_scaled != 0, s);
-    if (rc == STC_NOT_HANDLED) return stc::fail(STC_EUNSUPPORTED, "stc_cell_gates_bwd_f32: operands not usable by the fused path (alignment)");
-    if (rc != STC_OK) return rc;
-    const int stride = nW + Ho;
-    hipLaunchKernelGGL(bdg_node_reduce_kernel, dim3((stride + RED_ELEMS - 1) / RED_ELEMS), dim3(NODE_THREADS), 0, s,
-                       partial, n_parts, stride, nW, Ho, 0, dW, db, static_cast<float*>(nullptr));
-    STC_LAUNCH_CHECK("stc_bdg_node_reduce launch");
-    return STC_OK;
+    if ((rc = stc::dispatched(__func__, rc))) return rc;
+    return stc::grad_tail_reduce(&g, 1, n_parts, s);
 }
 
 extern "C" int stc_cell_cand_bwd_f32(const float* const* Z, int32_t Ks, const float* Tc, int32_t Kc, const float* W,
@@ -463,29 +451,17 @@ extern "C" int stc_cell_cand_bwd_f32(const float* const* Z, int32_t Ks, const fl
     if (!stc_cell_fused_supported(Ks, Kc, C, L, h)) return stc::fail(STC_EUNSUPPORTED, "stc_cell_cand_bwd_f32: shape not on the fused path");
     STC_REQUIRE(Z && W && dZ && dW && (Kc == 1 || Tc), STC_EINVAL, "stc_cell_cand_bwd_f32: null Z/W/dZ/dW/Tc");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nW = Ks * Kc * Lw * h, Ho = h;
-    if (nodes == 0) {
-        if (int rc = stc::hip_status(hipMemsetAsync(dW, 0, (size_t)nW * sizeof(float), s), "memset dW")) return rc;
-        if (db) if (int rc = stc::hip_status(hipMemsetAsync(db, 0, (size_t)Ho * sizeof(float), s), "memset db")) return rc;
-        return STC_OK;
-    }
+    stc::ParamGrad g{dW, db, Ks * Kc * Lw * h, h, stc_bdg_node_bwd_workspace_bytes(Ks, Kc, C, L, h, 0)};
+    bool done;
+    if (int rc = stc::grad_tail_begin(__func__, &g, 1, nodes, workspace, workspace_bytes, STC_EALIGN, s, &done); rc || done) return rc;
     STC_REQUIRE(dHnew && U && Cand, STC_EINVAL, "stc_cell_cand_bwd_f32: null pointer");
     for (int n = 0; n < Ks; ++n) STC_REQUIRE(Z[n] && dZ[n], STC_EINVAL, "stc_cell_cand_bwd_f32: Z[%d]/dZ[%d] is null", n, n);
-    STC_REQUIRE(workspace && stc::aligned16(workspace), STC_EALIGN, "stc_cell_cand_bwd_f32: workspace null or not 16-byte aligned");
-    STC_REQUIRE(workspace_bytes >= stc_bdg_node_bwd_workspace_bytes(Ks, Kc, C, L, Ho, 0), STC_EINVAL,
-                "stc_cell_cand_bwd_f32: workspace of %zu B is too small", workspace_bytes);
     int n_parts = 0;
-    float* partial = static_cast<float*>(workspace);
     int rc = STC_NOT_HANDLED;
-    if (x3_enabled()) rc = stc_cell_cand_bwd_x3(Z, Ks, Tc, W, dHnew, U, Cand, dZ, partial, &n_parts, db != nullptr, nodes, C, L, Lw, s);
-    if (rc == STC_NOT_HANDLED) rc = stc_cell_cand_bwd_mfma(Z, Ks, Tc, W, dHnew, U, Cand, dZ, partial, &n_parts, db != nullptr, nodes, C, L, Lw, s);
-    if (rc == STC_NOT_HANDLED) return stc::fail(STC_EUNSUPPORTED, "stc_cell_cand_bwd_f32: operands not usable by the fused path (alignment)");
-    if (rc != STC_OK) return rc;
-    const int stride = nW + Ho;
-    hipLaunchKernelGGL(bdg_node_reduce_kernel, dim3((stride + RED_ELEMS - 1) / RED_ELEMS), dim3(NODE_THREADS), 0, s,
-                       partial, n_parts, stride, nW, Ho, 0, dW, db, static_cast<float*>(nullptr));
-    STC_LAUNCH_CHECK("stc_bdg_node_reduce launch");
-    return STC_OK;
+    if (x3_enabled()) rc = stc_cell_cand_bwd_x3(Z, Ks, Tc, W, dHnew, U, Cand, dZ, g.partial, &n_parts, db != nullptr, nodes, C, L, Lw, s);
+    if (rc == STC_NOT_HANDLED) rc = stc_cell_cand_bwd_mfma(Z, Ks, Tc, W, dHnew, U, Cand, dZ, g.partial, &n_parts, db != nullptr, nodes, C, L, Lw, s);
+    if ((rc = stc::dispatched(__func__, rc))) return rc;
+    return stc::grad_tail_reduce(&g, 1, n_parts, s);
 }
 
 // ---- planar cell inputs: [Xt | H] as two contiguous (nodes, C, h) planes (Ks = Kc = 2, cin = h = 16)
@@ -499,16 +475,16 @@ extern "C" int stc_cell_gates_fwd_planar_f32(const float* X, const float* H, con
                                              const float* Wc, const float* bc, float* A, float* Bm,
                                              int32_t operand_format, float* act_amax,
                                              int64_t nodes, int32_t C, int32_t Lw, int32_t h, void* stream) {
-    if (int rc = check_dims("stc_cell_gates_fwd_planar_f32", 2, 2, C, Lw == 2 * h ? 2 * h : 20, Lw, 2 * h, nodes)) return rc;
-    STC_REQUIRE(operand_format == STC_FMT_BF16X3 || operand_format == STC_FMT_F16X2, STC_EINVAL,
-                "stc_cell_gates_fwd_planar_f32: operand_format %d (STC_FMT_BF16X3 or STC_FMT_F16X2)", operand_format);
-    STC_REQUIRE(Lw == 2 * h || (Lw > h && Lw <= h + 4), STC_EINVAL, "stc_cell_gates_fwd_planar_f32: input width %d (Lw - h) must be h or 1..4", Lw - h);
+    const stc::PlanarRow row(Lw, h);
+    if (int rc = check_dims(__func__, 2, 2, C, row.L, Lw, 2 * h, nodes)) return rc;
+    if (int rc = stc::check_operand_format(__func__, operand_format)) return rc;
+    if (int rc = row.check_width(__func__, STC_EINVAL)) return rc;
     if (!stc_cell_planar_supported(2, 2, C, h)) return stc::fail(STC_EUNSUPPORTED, "stc_cell_gates_fwd_planar_f32: shape not on the planar path");
     if (nodes == 0) return STC_OK;
     STC_REQUIRE(X && H && SX && SH && Tc && W && U && Rg && (RH || A), STC_EINVAL, "stc_cell_gates_fwd_planar_f32: null pointer");
     STC_REQUIRE((A == nullptr) == (Bm == nullptr) && (!A || Wc), STC_EINVAL, "stc_cell_gates_fwd_planar_f32: A, Bm and Wc go together");
     const int rc = stc_cell_gates_fwd_planar_x3(X, H, SX, SH, Tc, W, bias, U, Rg, RH, Wc, bc, A, Bm, operand_format, act_amax, nodes, C, Lw, static_cast<hipStream_t>(stream));
-    return rc == STC_NOT_HANDLED ? stc::fail(STC_EUNSUPPORTED, "stc_cell_gates_fwd_planar_f32: operands not usable (alignment)") : rc;
+    return stc::dispatched(__func__, rc);
 }
 
 extern "C" int stc_cell_gates_bwd_planar_f32(const float* X, const float* H, const float* SX, const float* SH,
@@ -518,35 +494,24 @@ extern "C" int stc_cell_gates_bwd_planar_f32(const float* X, const float* H, con
                                              int32_t operand_format, const float* act_amax,
                                              void* workspace, size_t workspace_bytes,
                                              int64_t nodes, int32_t C, int32_t Lw, int32_t h, void* stream) {
-    const int L = Lw == 2 * h ? 2 * h : 20, Ho = 2 * h;
-    if (int rc = check_dims("stc_cell_gates_bwd_planar_f32", 2, 2, C, L, Lw, Ho, nodes)) return rc;
-    STC_REQUIRE(operand_format == STC_FMT_BF16X3 || operand_format == STC_FMT_F16X2, STC_EINVAL, "stc_cell_gates_bwd_planar_f32: operand_format %d", operand_format);
-    STC_REQUIRE(Lw == 2 * h || (Lw > h && Lw <= h + 4), STC_EINVAL, "stc_cell_gates_bwd_planar_f32: input width %d (Lw - h) must be h or 1..4", Lw - h);
+    const stc::PlanarRow row(Lw, h);
+    const int Ho = 2 * h;
+    if (int rc = check_dims(__func__, 2, 2, C, row.L, Lw, Ho, nodes)) return rc;
+    if (int rc = stc::check_operand_format(__func__, operand_format)) return rc;
+    if (int rc = row.check_width(__func__, STC_EINVAL)) return rc;
     if (!stc_cell_planar_supported(2, 2, C, h)) return stc::fail(STC_EUNSUPPORTED, "stc_cell_gates_bwd_planar_f32: shape not on the planar path");
     STC_REQUIRE(W && dZ && dW && Tc, STC_EINVAL, "stc_cell_gates_bwd_planar_f32: null W/dZ/dW/Tc");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nW = 4 * Lw * Ho;
-    if (nodes == 0) {
-        if (int rc = stc::hip_status(hipMemsetAsync(dW, 0, (size_t)nW * sizeof(float), s), "memset dW")) return rc;
-        if (db) if (int rc = stc::hip_status(hipMemsetAsync(db, 0, (size_t)Ho * sizeof(float), s), "memset db")) return rc;
-        return STC_OK;
-    }
-    STC_REQUIRE(X && H && SX && SH && dCandIn && Cand && U && Rg && dHnew && dZ[2] && dZ[3] && (Lw != 2 * h || (dZ[0] && dZ[1])), STC_EINVAL,
+    stc::ParamGrad g{dW, db, 4 * Lw * Ho, Ho, stc_bdg_node_bwd_workspace_bytes(2, 2, C, row.L, Ho, 0)};
+    bool done;
+    if (int rc = stc::grad_tail_begin(__func__, &g, 1, nodes, workspace, workspace_bytes, STC_EALIGN, s, &done); rc || done) return rc;
+    STC_REQUIRE(X && H && SX && SH && dCandIn && Cand && U && Rg && dHnew && dZ[2] && dZ[3] && (row.narrow || (dZ[0] && dZ[1])), STC_EINVAL,
                 "stc_cell_gates_bwd_planar_f32: null pointer");       // (dH may be null: its values are then folded into dZ[2])
-    STC_REQUIRE(workspace && stc::aligned16(workspace), STC_EALIGN, "stc_cell_gates_bwd_planar_f32: workspace null or not 16-byte aligned");
-    STC_REQUIRE(workspace_bytes >= stc_bdg_node_bwd_workspace_bytes(2, 2, C, L, Ho, 0), STC_EINVAL,
-                "stc_cell_gates_bwd_planar_f32: workspace of %zu B is too small", workspace_bytes);
     int n_parts = 0;
-    float* partial = static_cast<float*>(workspace);
-    const int rc = stc_cell_gates_bwd_planar_x3(X, H, SX, SH, Tc, W, dCandIn, Cand, U, Rg, dHnew, dZ, dH, partial, &n_parts, db != nullptr,
-                                                operand_format, act_amax, nodes, C, Lw, s);
-    if (rc == STC_NOT_HANDLED) return stc::fail(STC_EUNSUPPORTED, "stc_cell_gates_bwd_planar_f32: operands not usable (alignment)");
-    if (rc != STC_OK) return rc;
-    const int stride = nW + Ho;
-    hipLaunchKernelGGL(bdg_node_reduce_kernel, dim3((stride + RED_ELEMS - 1) / RED_ELEMS), dim3(NODE_THREADS), 0, s,
-                       partial, n_parts, stride, nW, Ho, 0, dW, db, static_cast<float*>(nullptr));
-    STC_LAUNCH_CHECK("stc_bdg_node_reduce launch");
-    return STC_OK;
+    if (int rc = stc::dispatched(__func__, stc_cell_gates_bwd_planar_x3(X, H, SX, SH, Tc, W, dCandIn, Cand, U, Rg, dHnew, dZ, dH, g.partial, &n_parts,
+                                                                        db != nullptr, operand_format, act_amax, nodes, C, Lw, s)))
+        return rc;
+    return stc::grad_tail_reduce(&g, 1, n_parts, s);
 }
 
 // ---- the whole backward of a planar cell step in one launch (stc_cell_bwd_x3.hip)
@@ -555,8 +520,8 @@ extern "C" int stc_cell_bwd_planar_supported(int32_t C, int32_t h) {
 }
 
 extern "C" size_t stc_cell_bwd_planar_workspace_bytes(int32_t C, int32_t Lw, int32_t h) {
-    const int L = Lw == 2 * h ? 2 * h : 20;
-    return stc_bdg_node_bwd_workspace_bytes(2, 2, C, L, 2 * h, 0) + stc_bdg_node_bwd_workspace_bytes(2, 2, C, L, h, 0);
+    const stc::PlanarRow row(Lw, h);
+    return stc_bdg_node_bwd_workspace_bytes(2, 2, C, row.L, 2 * h, 0) + stc_bdg_node_bwd_workspace_bytes(2, 2, C, row.L, h, 0);
 }
 
 extern "C" int stc_cell_bwd_planar_f32(const float* X, const float* H, const float* SX, const float* SH,
@@ -568,37 +533,26 @@ extern "C" int stc_cell_bwd_planar_f32(const float* X, const float* H, const flo
                                        int32_t operand_format, const float* act_amax,
                                        void* workspace, size_t workspace_bytes,
                                        int64_t nodes, int32_t C, int32_t Lw, int32_t h, void* stream) {
-    const int L = Lw == 2 * h ? 2 * h : 20;
-    if (int rc = check_dims("stc_cell_bwd_planar_f32", 2, 2, C, L, Lw, 2 * h, nodes)) return rc;
-    STC_REQUIRE(operand_format == STC_FMT_BF16X3 || operand_format == STC_FMT_F16X2, STC_EINVAL, "stc_cell_bwd_planar_f32: operand_format %d", operand_format);
-    STC_REQUIRE(Lw == 2 * h || (Lw > h && Lw <= h + 4), STC_EINVAL, "stc_cell_bwd_planar_f32: input width %d (Lw - h) must be h or 1..4", Lw - h);
+    const stc::PlanarRow row(Lw, h);
+    if (int rc = check_dims(__func__, 2, 2, C, row.L, Lw, 2 * h, nodes)) return rc;
+    if (int rc = stc::check_operand_format(__func__, operand_format)) return rc;
+    if (int rc = row.check_width(__func__, STC_EINVAL)) return rc;
     if (!stc_cell_bwd_planar_supported(C, h)) return stc::fail(STC_EUNSUPPORTED, "stc_cell_bwd_planar_f32: C=%d h=%d is not built (C = 32, h = 16)", C, h);
     STC_REQUIRE(Wg && Wc && dWg && dWc && Tc, STC_EINVAL, "stc_cell_bwd_planar_f32: null W/dW/Tc");
-    STC_REQUIRE(!accumulate_x || Lw == 2 * h, STC_EINVAL, "stc_cell_bwd_planar_f32: accumulate_x with a narrow input plane (it gets no gradient)");
+    STC_REQUIRE(!accumulate_x || !row.narrow, STC_EINVAL, "stc_cell_bwd_planar_f32: accumulate_x with a narrow input plane (it gets no gradient)");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nWg = 4 * Lw * 2 * h, nWc = 4 * Lw * h;
-    if (nodes == 0) {
-        if (int rc = stc::hip_status(hipMemsetAsync(dWg, 0, (size_t)nWg * sizeof(float), s), "memset dWg")) return rc;
-        if (int rc = stc::hip_status(hipMemsetAsync(dWc, 0, (size_t)nWc * sizeof(float), s), "memset dWc")) return rc;
-        if (dbg) if (int rc = stc::hip_status(hipMemsetAsync(dbg, 0, (size_t)2 * h * sizeof(float), s), "memset dbg")) return rc;
-        if (dbc) if (int rc = stc::hip_status(hipMemsetAsync(dbc, 0, (size_t)h * sizeof(float), s), "memset dbc")) return rc;
-        return STC_OK;
-    }
-    STC_REQUIRE(X && H && SX && SH && U && Rg && Cand && dHnew && dBm && dH && dSH && (Lw != 2 * h || (dX && dSX)), STC_EINVAL,
+    stc::ParamGrad g[2] = {{dWg, dbg, 4 * Lw * 2 * h, 2 * h, stc_bdg_node_bwd_workspace_bytes(2, 2, C, row.L, 2 * h, 0)},       // gates, then candidate:
+                           {dWc, dbc, 4 * Lw * h, h, stc_bdg_node_bwd_workspace_bytes(2, 2, C, row.L, h, 0)}};                 // stc_cell_bwd_planar_workspace_bytes
+    bool done;
+    if (int rc = stc::grad_tail_begin(__func__, g, 2, nodes, workspace, workspace_bytes, STC_EALIGN, s, &done); rc || done) return rc;
+    STC_REQUIRE(X && H && SX && SH && U && Rg && Cand && dHnew && dBm && dH && dSH && (row.narrow || (dX && dSX)), STC_EINVAL,
                 "stc_cell_bwd_planar_f32: null pointer");
-    STC_REQUIRE(workspace && stc::aligned16(workspace), STC_EALIGN, "stc_cell_bwd_planar_f32: workspace null or not 16-byte aligned");
-    const size_t bytes_g = stc_bdg_node_bwd_workspace_bytes(2, 2, C, L, 2 * h, 0);
-    STC_REQUIRE(workspace_bytes >= stc_cell_bwd_planar_workspace_bytes(C, Lw, h), STC_EINVAL,
-                "stc_cell_bwd_planar_f32: workspace of %zu B is too small", workspace_bytes);
-    float* partial_g = static_cast<float*>(workspace);
-    float* partial_c = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + bytes_g);
     int n_parts = 0;
-    const int rc = stc_cell_bwd_planar_x3(X, H, SX, SH, Tc, Wg, Wc, U, Rg, Cand, dHnew, dBm, dX, dSX, dH, dSH, partial_g, partial_c, &n_parts,
-                                          dbg != nullptr, dbc != nullptr, accumulate_x != 0, accumulate_h != 0, operand_format, act_amax, nodes, C, Lw, s);
-    if (rc == STC_NOT_HANDLED) return stc::fail(STC_EUNSUPPORTED, "stc_cell_bwd_planar_f32: operands not usable (alignment)");
-    if (rc != STC_OK) return rc;
-    if (int r2 = stc_node_reduce_partials(partial_g, n_parts, nWg, 2 * h, dWg, dbg, s)) return r2;
-    return stc_node_reduce_partials(partial_c, n_parts, nWc, h, dWc, dbc, s);
+    if (int rc = stc::dispatched(__func__, stc_cell_bwd_planar_x3(X, H, SX, SH, Tc, Wg, Wc, U, Rg, Cand, dHnew, dBm, dX, dSX, dH, dSH, g[0].partial, g[1].partial,
+                                                                  &n_parts, dbg != nullptr, dbc != nullptr, accumulate_x != 0, accumulate_h != 0,
+                                                                  operand_format, act_amax, nodes, C, Lw, s)))
+        return rc;
+    return stc::grad_tail_reduce(g, 2, n_parts, s);
 }
 
 // ---- planar cell convolutions of Chebyshev order K (= 3; K = 2 has the entry points above): see stc_cell_conv_*_planar_k_x3
@@ -607,8 +561,9 @@ extern "C" int stc_cell_planar_k_supported(int32_t K, int32_t C, int32_t h) {
 }
 
 static int planar_k_common(const char* who, const float* const* Zx, const float* const* Zh, int K, int C, int Lw, int h, int Ho, long long nodes) {
-    if (int rc = check_dims(who, K, K, C, Lw == 2 * h ? 2 * h : 20, Lw, Ho, nodes)) return rc;
-    STC_REQUIRE(Lw == 2 * h || (Lw > h && Lw <= h + 4), STC_EINVAL, "%s: input width %d (Lw - h) must be h or 1..4", who, Lw - h);
+    const stc::PlanarRow row(Lw, h);
+    if (int rc = check_dims(who, K, K, C, row.L, Lw, Ho, nodes)) return rc;
+    if (int rc = row.check_width(who, STC_EINVAL)) return rc;
     if (!stc_cell_planar_k_supported(K, C, h)) return stc::fail(STC_EUNSUPPORTED, "%s: K=%d C=%d h=%d is not on the order-K planar path", who, K, C, h);
     STC_REQUIRE(Zx && Zh, STC_EINVAL, "%s: null plane arrays", who);
     if (nodes > 0)
@@ -620,53 +575,44 @@ extern "C" int stc_cell_gates_fwd_planar_k_f32(const float* const* Zx, const flo
                                                float* U, float* Rg, float* RH, int32_t operand_format, float* act_amax,
                                                int64_t nodes, int32_t C, int32_t Lw, int32_t h, void* stream) {
     if (int rc = planar_k_common("stc_cell_gates_fwd_planar_k_f32", Zx, Zh, K, C, Lw, h, 2 * h, nodes)) return rc;
-    STC_REQUIRE(operand_format == STC_FMT_BF16X3 || operand_format == STC_FMT_F16X2, STC_EINVAL, "stc_cell_gates_fwd_planar_k_f32: operand_format %d", operand_format);
+    if (int rc = stc::check_operand_format(__func__, operand_format)) return rc;
     if (nodes == 0) return STC_OK;
     STC_REQUIRE(Tc && W && U && Rg && RH, STC_EINVAL, "stc_cell_gates_fwd_planar_k_f32: null pointer");
     const int rc = stc_cell_conv_fwd_planar_k_x3(Zx, Zh, K, Tc, W, bias, 1, Zh[0], nullptr, U, Rg, RH, nullptr, nullptr, operand_format, act_amax, nodes, C, Lw, static_cast<hipStream_t>(stream));
-    return rc == STC_NOT_HANDLED ? stc::fail(STC_EUNSUPPORTED, "stc_cell_gates_fwd_planar_k_f32: operands not usable (alignment)") : rc;
+    return stc::dispatched(__func__, rc);
 }
 
 extern "C" int stc_cell_cand_fwd_planar_k_f32(const float* const* Zx, const float* const* Zh, int32_t K, const float* Tc, const float* W, const float* bias,
                                               const float* U, const float* H, float* Cand, float* Hnew, int32_t operand_format, float* act_amax,
                                               int64_t nodes, int32_t C, int32_t Lw, int32_t h, void* stream) {
     if (int rc = planar_k_common("stc_cell_cand_fwd_planar_k_f32", Zx, Zh, K, C, Lw, h, h, nodes)) return rc;
-    STC_REQUIRE(operand_format == STC_FMT_BF16X3 || operand_format == STC_FMT_F16X2, STC_EINVAL, "stc_cell_cand_fwd_planar_k_f32: operand_format %d", operand_format);
+    if (int rc = stc::check_operand_format(__func__, operand_format)) return rc;
     if (nodes == 0) return STC_OK;
     STC_REQUIRE(Tc && W && U && H && Cand && Hnew, STC_EINVAL, "stc_cell_cand_fwd_planar_k_f32: null pointer");
     STC_REQUIRE(stc::aligned16(U) && stc::aligned16(H) && stc::aligned16(Cand) && stc::aligned16(Hnew), STC_EALIGN, "stc_cell_cand_fwd_planar_k_f32: misaligned operand");
     const int rc = stc_cell_conv_fwd_planar_k_x3(Zx, Zh, K, Tc, W, bias, 2, H, U, nullptr, nullptr, nullptr, Cand, Hnew, operand_format, act_amax, nodes, C, Lw, static_cast<hipStream_t>(stream));
-    return rc == STC_NOT_HANDLED ? stc::fail(STC_EUNSUPPORTED, "stc_cell_cand_fwd_planar_k_f32: operands not usable (alignment)") : rc;
+    return stc::dispatched(__func__, rc);
 }
 
 static int planar_k_bwd(const char* who, const float* const* Zx, const float* const* Zh, int K, const float* Tc, const float* W, int mode,
                         const float* dRH, const float* Cand, const float* U, const float* Rg, const float* dHnew,
                         float* const* dZx, float* const* dZh, float* dW, float* db, float* dH, void* workspace, size_t workspace_bytes,
                         long long nodes, int C, int Lw, int h, hipStream_t s, int operand_format, const float* act_amax, int accumulate_x = 0) {
-    const int L = Lw == 2 * h ? 2 * h : 20, Ho = mode == 1 ? 2 * h : h;
+    const stc::PlanarRow row(Lw, h);
+    const int Ho = mode == 1 ? 2 * h : h;
     if (int rc = planar_k_common(who, Zx, Zh, K, C, Lw, h, Ho, nodes)) return rc;
-    STC_REQUIRE(W && dW && Tc && dZh && (Lw != 2 * h || dZx), STC_EINVAL, "%s: null W/dW/Tc/dZ", who);
-    STC_REQUIRE(operand_format == STC_FMT_BF16X3 || operand_format == STC_FMT_F16X2, STC_EINVAL, "%s: operand_format %d", who, operand_format);
-    const int nW = K * K * Lw * Ho;
-    if (nodes == 0) {
-        if (int rc = stc::hip_status(hipMemsetAsync(dW, 0, (size_t)nW * sizeof(float), s), "memset dW")) return rc;
-        if (db) if (int rc = stc::hip_status(hipMemsetAsync(db, 0, (size_t)Ho * sizeof(float), s), "memset db")) return rc;
-        return STC_OK;
-    }
+    STC_REQUIRE(W && dW && Tc && dZh && (row.narrow || dZx), STC_EINVAL, "%s: null W/dW/Tc/dZ", who);
+    if (int rc = stc::check_operand_format(who, operand_format)) return rc;
+    stc::ParamGrad g{dW, db, K * K * Lw * Ho, Ho, stc_bdg_node_bwd_workspace_bytes(K, K, C, row.L, Ho, 0)};
+    bool done;
+    if (int rc = stc::grad_tail_begin(who, &g, 1, nodes, workspace, workspace_bytes, STC_EALIGN, s, &done); rc || done) return rc;
     STC_REQUIRE(Cand && U && dHnew && (mode != 1 || (dRH && Rg)), STC_EINVAL, "%s: null pointer", who);      // (dH may be null: folded into dZh[0])
-    STC_REQUIRE(workspace && stc::aligned16(workspace), STC_EALIGN, "%s: workspace null or not 16-byte aligned", who);
-    STC_REQUIRE(workspace_bytes >= stc_bdg_node_bwd_workspace_bytes(K, K, C, L, Ho, 0), STC_EINVAL, "%s: workspace of %zu B is too small", who, workspace_bytes);
     int n_parts = 0;
-    float* partial = static_cast<float*>(workspace);
-    const int rc = stc_cell_conv_bwd_planar_k_x3(Zx, Zh, K, Tc, W, mode, dRH, Cand, U, Rg, dHnew, dZx, dZh, dH, partial, &n_parts, db != nullptr, nodes, C, Lw,
-                                                 accumulate_x, operand_format, act_amax, s);
-    if (rc == STC_NOT_HANDLED) return stc::fail(STC_EUNSUPPORTED, "%s: operands not usable (alignment / null gradient plane / accumulate_x outside the wide folded form)", who);
-    if (rc != STC_OK) return rc;
-    const int stride = nW + Ho;
-    hipLaunchKernelGGL(bdg_node_reduce_kernel, dim3((stride + RED_ELEMS - 1) / RED_ELEMS), dim3(NODE_THREADS), 0, s,
-                       partial, n_parts, stride, nW, Ho, 0, dW, db, static_cast<float*>(nullptr));
-    STC_LAUNCH_CHECK("stc_bdg_node_reduce launch");
-    return STC_OK;
+    if (int rc = stc::dispatched(who, stc_cell_conv_bwd_planar_k_x3(Zx, Zh, K, Tc, W, mode, dRH, Cand, U, Rg, dHnew, dZx, dZh, dH, g.partial, &n_parts, db != nullptr,
+                                                                    nodes, C, Lw, accumulate_x, operand_format, act_amax, s),
+                                 "alignment / null gradient plane / accumulate_x outside the wide folded form"))
+        return rc;
+    return stc::grad_tail_reduce(&g, 1, n_parts, s);
 }
 
 extern "C" int stc_cell_gates_bwd_planar_k_f32(const float* const* Zx, const float* const* Zh, int32_t K, const float* Tc, const float* W,
@@ -701,7 +647,7 @@ extern "C" int stc_bdg_node_post_fwd_f32(const float* X, const float* X2, const 
     STC_REQUIRE(A != Bm && X != A && X != Bm, STC_EINVAL, "stc_bdg_node_post_fwd_f32: outputs must not alias");
     STC_REQUIRE(!X2 || L == 32 || (L == 20 && Lw > 16), STC_EINVAL, "stc_bdg_node_post_fwd_f32: planar input (X2) needs rows of 16 + 16 or 16 + cin (<= 4) columns, L = %d", L);
     const int rc = stc_node_post_fwd_x3(X, X2, Tc, W, bias, A, Bm, nodes, C, L, Lw, Ho, static_cast<hipStream_t>(stream));
-    return rc == STC_NOT_HANDLED ? stc::fail(STC_EUNSUPPORTED, "stc_bdg_node_post_fwd_f32: operands not usable (alignment)") : rc;
+    return stc::dispatched(__func__, rc);
 }
 
 extern "C" int stc_bdg_node_post_bwd_f32(const float* X, const float* X2, const float* Tc, const float* W, const float* dA, const float* dB,
@@ -710,33 +656,22 @@ extern "C" int stc_bdg_node_post_bwd_f32(const float* X, const float* X2, const 
                                          void* workspace, size_t workspace_bytes,
                                          int64_t nodes, int32_t C, int32_t L, int32_t Lw, int32_t Ho, void* stream) {
     if (int rc = check_dims("stc_bdg_node_post_bwd_f32", 2, 2, C, L, Lw, Ho, nodes)) return rc;
-    STC_REQUIRE(operand_format == STC_FMT_BF16X3 || operand_format == STC_FMT_F16X2, STC_EINVAL, "stc_bdg_node_post_bwd_f32: operand_format %d", operand_format);
+    if (int rc = stc::check_operand_format(__func__, operand_format)) return rc;
     if (!stc_bdg_node_post_supported(2, 2, C, L, Ho)) return stc::fail(STC_EUNSUPPORTED, "stc_bdg_node_post_bwd_f32: shape not on the post-aggregation path");
     STC_REQUIRE(W && dW && Tc, STC_EINVAL, "stc_bdg_node_post_bwd_f32: null W/dW/Tc");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nW = 4 * Lw * Ho;
-    if (nodes == 0) {
-        if (int rc = stc::hip_status(hipMemsetAsync(dW, 0, (size_t)nW * sizeof(float), s), "memset dW")) return rc;
-        if (db) if (int rc = stc::hip_status(hipMemsetAsync(db, 0, (size_t)Ho * sizeof(float), s), "memset db")) return rc;
-        return STC_OK;
-    }
+    stc::ParamGrad g{dW, db, 4 * Lw * Ho, Ho, stc_bdg_node_bwd_workspace_bytes(2, 2, C, L, Ho, 0)};
+    bool done;
+    if (int rc = stc::grad_tail_begin(__func__, &g, 1, nodes, workspace, workspace_bytes, STC_EALIGN, s, &done); rc || done) return rc;
     STC_REQUIRE(X && dA && dB && dX, STC_EINVAL, "stc_bdg_node_post_bwd_f32: null pointer");
-    STC_REQUIRE(workspace && stc::aligned16(workspace), STC_EALIGN, "stc_bdg_node_post_bwd_f32: workspace null or not 16-byte aligned");
-    STC_REQUIRE(workspace_bytes >= stc_bdg_node_bwd_workspace_bytes(2, 2, C, L, Ho, 0), STC_EINVAL,
-                "stc_bdg_node_post_bwd_f32: workspace of %zu B is too small", workspace_bytes);
-    int n_parts = 0;
-    float* partial = static_cast<float*>(workspace);
     STC_REQUIRE(!X2 || L == 32 || (L == 20 && Lw > 16), STC_EINVAL, "stc_bdg_node_post_bwd_f32: planar input (X2) needs rows of 16 + 16 or 16 + cin (<= 4) columns, L = %d", L);
     STC_REQUIRE(L == 20 ? dX2 == nullptr : (X2 == nullptr) == (dX2 == nullptr), STC_EINVAL,
                 "stc_bdg_node_post_bwd_f32: planar input (X2) and planar gradient (dX2) go together (the narrow input plane of L = 20 gets no gradient)");
-    const int rc = stc_node_post_bwd_x3(X, X2, Tc, W, dA, dB, dX, dX2, partial, &n_parts, db != nullptr, operand_format, act_amax_x, act_amax_x2, nodes, C, L, Lw, Ho, s);
-    if (rc == STC_NOT_HANDLED) return stc::fail(STC_EUNSUPPORTED, "stc_bdg_node_post_bwd_f32: operands not usable (alignment)");
-    if (rc != STC_OK) return rc;
-    const int stride = nW + Ho;
-    hipLaunchKernelGGL(bdg_node_reduce_kernel, dim3((stride + RED_ELEMS - 1) / RED_ELEMS), dim3(NODE_THREADS), 0, s,
-                       partial, n_parts, stride, nW, Ho, 0, dW, db, static_cast<float*>(nullptr));
-    STC_LAUNCH_CHECK("stc_bdg_node_reduce launch");
-    return STC_OK;
+    int n_parts = 0;
+    if (int rc = stc::dispatched(__func__, stc_node_post_bwd_x3(X, X2, Tc, W, dA, dB, dX, dX2, g.partial, &n_parts, db != nullptr, operand_format,
+                                                                act_amax_x, act_amax_x2, nodes, C, L, Lw, Ho, s)))
+        return rc;
+    return stc::grad_tail_reduce(&g, 1, n_parts, s);
 }
 
 extern "C" int stc_cell_blend_fwd_f32(const float* const* Z, int32_t Ks, const float* Tc, int32_t Kc,
@@ -760,7 +695,7 @@ extern "C" int stc_cell_blend_fwd_f32(const float* const* Z, int32_t Ks, const f
     int rc = STC_NOT_HANDLED;
     if (x3_enabled()) rc = stc_cell_blend_fwd_x3(Z, Ks, Tc, W, bias, U, H, Cand, Hnew, &cp, nodes, C, L, Lw, static_cast<hipStream_t>(stream));
     if (rc == STC_NOT_HANDLED) rc = stc_cell_blend_fwd_mfma(Z, Ks, Tc, W, bias, U, H, Cand, Hnew, &cp, nodes, C, L, Lw, static_cast<hipStream_t>(stream));
-    return rc == STC_NOT_HANDLED ? stc::fail(STC_EUNSUPPORTED, "stc_cell_blend_fwd_f32: operands not usable by the fused path (alignment)") : rc;
+    return stc::dispatched(__func__, rc);
 }
 
 extern "C" int stc_set_dispatch_level(int32_t level) {
@@ -785,12 +720,10 @@ extern "C" int stc_bdg_node_bwd_f32(const float* const* Z, int32_t Ks, const flo
     STC_REQUIRE(Z && W && dZ && dW && (Kc == 1 || Tc), STC_EINVAL, "stc_bdg_node_bwd_f32: null Z/W/dZ/dW/Tc");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nW = Ks * Kc * Lw * Ho, nT = Kc * C * C;
-    if (nodes == 0) {   // gradients of an empty batch are zero
-        if (int rc = stc::hip_status(hipMemsetAsync(dW, 0, (size_t)nW * sizeof(float), s), "memset dW")) return rc;
-        if (db) if (int rc = stc::hip_status(hipMemsetAsync(db, 0, (size_t)Ho * sizeof(float), s), "memset db")) return rc;
-        if (dTc) if (int rc = stc::hip_status(hipMemsetAsync(dTc, 0, (size_t)nT * sizeof(float), s), "memset dTc")) return rc;
-        return STC_OK;
-    }
+    if (nodes == 0 && dTc) if (int rc = stc::hip_status(hipMemsetAsync(dTc, 0, (size_t)nT * sizeof(float), s), "memset dTc")) return rc;
+    stc::ParamGrad g{dW, db, nW, Ho, stc_bdg_node_bwd_workspace_bytes(Ks, Kc, C, L, Ho, dTc != nullptr)};
+    bool done;
+    if (int rc = stc::grad_tail_begin(__func__, &g, 1, nodes, workspace, workspace_bytes, STC_EALIGN, s, &done); rc || done) return rc;
     STC_REQUIRE(dY, STC_EINVAL, "stc_bdg_node_bwd_f32: null dY");
     ZPtrs zp{};
     DZPtrs dzp{};
@@ -799,22 +732,12 @@ extern "C" int stc_bdg_node_bwd_f32(const float* const* Z, int32_t Ks, const flo
         zp.p[n] = Z[n];
         dzp.p[n] = dZ[n];
     }
-    STC_REQUIRE(workspace && stc::aligned16(workspace), STC_EALIGN, "stc_bdg_node_bwd_f32: workspace null or not 16-byte aligned");
-    STC_REQUIRE(workspace_bytes >= stc_bdg_node_bwd_workspace_bytes(Ks, Kc, C, L, Ho, dTc != nullptr), STC_EINVAL,
-                "stc_bdg_node_bwd_f32: workspace of %zu B is too small", workspace_bytes);
     if (mfma_enabled() && dTc == nullptr) {
         int n_parts = 0;
-        float* partial = static_cast<float*>(workspace);
         int rc = STC_NOT_HANDLED;
-        if (x3_enabled()) rc = stc_node_bwd_x3(Z, Ks, Tc, Kc, W, dY, dZ, partial, &n_parts, db != nullptr, nodes, C, L, Lw, Ho, s);
-        if (rc == STC_NOT_HANDLED) rc = stc_node_bwd_mfma(Z, Ks, Tc, Kc, W, dY, dZ, partial, &n_parts, db != nullptr, nodes, C, L, Lw, Ho, s);
-        if (rc == STC_OK) {
-            const int stride = nW + Ho;
-            hipLaunchKernelGGL(bdg_node_reduce_kernel, dim3((stride + RED_ELEMS - 1) / RED_ELEMS), dim3(NODE_THREADS), 0, s,
-                               partial, n_parts, stride, nW, Ho, 0, dW, db, static_cast<float*>(nullptr));
-            STC_LAUNCH_CHECK("stc_bdg_node_reduce launch");
-            return STC_OK;
-        }
+        if (x3_enabled()) rc = stc_node_bwd_x3(Z, Ks, Tc, Kc, W, dY, dZ, g.partial, &n_parts, db != nullptr, nodes, C, L, Lw, Ho, s);
+        if (rc == STC_NOT_HANDLED) rc = stc_node_bwd_mfma(Z, Ks, Tc, Kc, W, dY, dZ, g.partial, &n_parts, db != nullptr, nodes, C, L, Lw, Ho, s);
+        if (rc == STC_OK) return stc::grad_tail_reduce(&g, 1, n_parts, s);
         if (rc != STC_NOT_HANDLED) return rc;
     }
     const NodeDims d = make_dims(Ks, Kc, C, L, Lw, Ho);
@@ -826,11 +749,11 @@ extern "C" int stc_bdg_node_bwd_f32(const float* const* Z, int32_t Ks, const flo
     if (int rc = stc::hip_status(stc::allow_lds(bdg_node_bwd_kernel, lds), "hipFuncSetAttribute(node bwd)")) return rc;
     const long long n_tiles = (nodes + d.TN - 1) / d.TN;
     const int grid = bwd_grid(d, nodes);
-    float* partial = static_cast<float*>(workspace);
+    float* partial = g.partial;
     hipLaunchKernelGGL(bdg_node_bwd_kernel, dim3(grid), dim3(NODE_THREADS), lds, s,
                        zp, Tc, W, dY, dzp, partial, (long long)nodes * C, d, cv, (int)n_tiles, (int)want_dT, (int)(db != nullptr));
     STC_LAUNCH_CHECK("stc_bdg_node_bwd_f32 launch");
-    const int stride = nW + Ho + nT;
+    const int stride = nW + Ho + nT;      // the generic kernel's rows carry the dT columns too: reduced here, not by stc_node_reduce_partials
     hipLaunchKernelGGL(bdg_node_reduce_kernel, dim3((stride + RED_ELEMS - 1) / RED_ELEMS), dim3(NODE_THREADS), 0, s,
                        partial, grid, stride, nW, Ho, nT, dW, db, dTc);
     STC_LAUNCH_CHECK("stc_bdg_node_reduce launch");

@@ -1120,13 +1120,11 @@ template <int NB2, int HB, int K, int L>
 int launch_fwd(const void* const* Z, const float* Tc, const float* W, const float* bias, void* Y, long long nodes, int Lw, hipStream_t stream) {
     constexpr int NRB = 2 * NB2, NCB = K * HB;
     const size_t lds = (size_t)(K * NCB + K * NB2 * NRB) * 64 * 16;
-    auto kern = node_fwd_bf16_kernel<NB2, HB, K, L>;
-    if (int rc = stc::hip_status(stc::allow_lds(kern, lds), "hipFuncSetAttribute(node fwd bf16)")) return rc;
-    static const int resident = stc::resident_blocks(kern, MF_THREADS, lds, 2);   // persistent grid = what fits at once
+    constexpr auto kern = node_fwd_bf16_kernel<NB2, HB, K, L>;
+    int grid;
+    if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(node fwd bf16)", MF_THREADS, lds, 2, nodes, MF_WAVES, INT_MAX, &grid)) return rc;
     BPtrs zp{};
     for (int n = 0; n < K; ++n) zp.p[n] = static_cast<const bf16_t*>(Z[n]);
-    const long long want = (nodes + MF_WAVES - 1) / MF_WAVES;
-    const int grid = (int)(want < resident ? want : resident);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MF_THREADS), lds, stream, zp, Tc, W, bias, static_cast<bf16_t*>(Y), (int)nodes, Lw);
     STC_LAUNCH_CHECK("node_fwd_bf16 launch");
     return STC_OK;
@@ -1140,18 +1138,13 @@ int launch_bwd(const void* const* Z, const float* Tc, const float* W, const void
     const size_t slabs = (size_t)MF_WAVES * (nW + Ho) * sizeof(float);
     const size_t lds = frag > slabs ? frag : slabs;
     if (lds > stc::kMaxLdsBytes) return stc::fail(STC_EUNSUPPORTED, "stc_bdg_node_bwd_bf16: %zu B of LDS for the dW combine exceed the CU", lds);
-    auto kern = node_bwd_bf16_kernel<NB2, HB, K, L>;
-    if (int rc = stc::hip_status(stc::allow_lds(kern, lds), "hipFuncSetAttribute(node bwd bf16)")) return rc;
-    static const int resident = stc::resident_blocks(kern, MF_THREADS, lds, BwdWaves<NB2, K>::v);
+    constexpr auto kern = node_bwd_bf16_kernel<NB2, HB, K, L>;
+    if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(node bwd bf16)", MF_THREADS, lds, BwdWaves<NB2, K>::v, nodes, MF_WAVES, MF_BWD_MAX_GRID, n_partials)) return rc;
     BPtrs2 zp{};
     BDPtrs2 dzp{};
     for (int n = 0; n < K; ++n) { zp.p[n] = static_cast<const bf16_t*>(Z[n]); dzp.p[n] = static_cast<bf16_t*>(dZ[n]); }
-    const long long want = (nodes + MF_WAVES - 1) / MF_WAVES;
-    int grid = resident < MF_BWD_MAX_GRID ? resident : MF_BWD_MAX_GRID;
-    if (want < grid) grid = (int)want;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(MF_THREADS), lds, stream, zp, Tc, W, static_cast<const bf16_t*>(dY), dzp, partial, (int)nodes, want_db, Lw, GatesPro{});
+    hipLaunchKernelGGL(kern, dim3(*n_partials), dim3(MF_THREADS), lds, stream, zp, Tc, W, static_cast<const bf16_t*>(dY), dzp, partial, (int)nodes, want_db, Lw, GatesPro{});
     STC_LAUNCH_CHECK("node_bwd_bf16 launch");
-    *n_partials = grid;
     return STC_OK;
 }
 
@@ -1159,11 +1152,9 @@ template <int NB2, int NARROW, int POST>
 int launch_gates_fwd(const GatesFwd& a, const float* Tc, const float* W, const float* bias, long long nodes, int Lw, hipStream_t stream) {
     constexpr int NRB = 2 * NB2;
     const size_t lds = (size_t)(2 * 4 + 2 * NB2 * NRB + (POST ? 4 : 0)) * 64 * 16;
-    auto kern = cell_gates_fwd_bf16_kernel<NB2, NARROW, POST>;
-    if (int rc = stc::hip_status(stc::allow_lds(kern, lds), "hipFuncSetAttribute(gates fwd bf16)")) return rc;
-    static const int resident = stc::resident_blocks(kern, MF_THREADS, lds, 2);
-    const long long want = (nodes + MF_WAVES - 1) / MF_WAVES;
-    const int grid = (int)(want < resident ? want : resident);
+    constexpr auto kern = cell_gates_fwd_bf16_kernel<NB2, NARROW, POST>;
+    int grid;
+    if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(gates fwd bf16)", MF_THREADS, lds, 2, nodes, MF_WAVES, INT_MAX, &grid)) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MF_THREADS), lds, stream, a, Tc, W, bias, (int)nodes, Lw);
     STC_LAUNCH_CHECK("cell_gates_fwd_bf16 launch");
     return STC_OK;
@@ -1176,15 +1167,10 @@ int launch_gates_bwd(const BPtrs2& zp, const BDPtrs2& dzp, const GatesPro& pro, 
     const size_t frag = (size_t)(NRB * NB2 + K * LB * K) * 64 * 16 + (size_t)MF_WAVES * NRB * 256 * sizeof(float);     // tables + the dH stash
     const size_t slabs = (size_t)MF_WAVES * (nW + 32) * sizeof(float);
     const size_t lds = frag > slabs ? frag : slabs;
-    auto kern = node_bwd_bf16_kernel<NB2, 2, 2, 32, PL, 1, WAVES>;
-    if (int rc = stc::hip_status(stc::allow_lds(kern, lds), "hipFuncSetAttribute(gates bwd bf16)")) return rc;
-    static const int resident = stc::resident_blocks(kern, MF_THREADS, lds, WAVES);
-    const long long want = (nodes + MF_WAVES - 1) / MF_WAVES;
-    int grid = resident < MF_BWD_MAX_GRID ? resident : MF_BWD_MAX_GRID;
-    if (want < grid) grid = (int)want;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(MF_THREADS), lds, stream, zp, Tc, W, static_cast<const bf16_t*>(nullptr), dzp, partial, (int)nodes, want_db, Lw, pro);
+    constexpr auto kern = node_bwd_bf16_kernel<NB2, 2, 2, 32, PL, 1, WAVES>;
+    if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(gates bwd bf16)", MF_THREADS, lds, WAVES, nodes, MF_WAVES, MF_BWD_MAX_GRID, n_partials)) return rc;
+    hipLaunchKernelGGL(kern, dim3(*n_partials), dim3(MF_THREADS), lds, stream, zp, Tc, W, static_cast<const bf16_t*>(nullptr), dzp, partial, (int)nodes, want_db, Lw, pro);
     STC_LAUNCH_CHECK("cell_gates_bwd_bf16 launch");
-    *n_partials = grid;
     return STC_OK;
 }
 
@@ -1195,15 +1181,10 @@ int launch_post_bwd(const bf16_t* X, const bf16_t* X2, const float* Tc, const fl
     const size_t frag = (size_t)(NRB * NB2 + 4) * 64 * 16;
     const size_t slabs = (size_t)MF_WAVES * (nW + 16) * sizeof(float);
     const size_t lds = frag > slabs ? frag : slabs;
-    auto kern = node_post_bwd_bf16_kernel<NB2, NARROW>;
-    if (int rc = stc::hip_status(stc::allow_lds(kern, lds), "hipFuncSetAttribute(post bwd bf16)")) return rc;
-    static const int resident = stc::resident_blocks(kern, MF_THREADS, lds, NB2 == 1 ? 2 : 1);
-    const long long want = (nodes + MF_WAVES - 1) / MF_WAVES;
-    int grid = resident < MF_BWD_MAX_GRID ? resident : MF_BWD_MAX_GRID;
-    if (want < grid) grid = (int)want;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(MF_THREADS), lds, stream, X, X2, Tc, W, dA, dB, dX, dX2, partial, (int)nodes, want_db, Lw);
+    constexpr auto kern = node_post_bwd_bf16_kernel<NB2, NARROW>;
+    if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(post bwd bf16)", MF_THREADS, lds, NB2 == 1 ? 2 : 1, nodes, MF_WAVES, MF_BWD_MAX_GRID, n_partials)) return rc;
+    hipLaunchKernelGGL(kern, dim3(*n_partials), dim3(MF_THREADS), lds, stream, X, X2, Tc, W, dA, dB, dX, dX2, partial, (int)nodes, want_db, Lw);
     STC_LAUNCH_CHECK("node_post_bwd_bf16 launch");
-    *n_partials = grid;
     return STC_OK;
 }
 
@@ -1218,15 +1199,10 @@ int launch_cell_bwd(const CellBwdB16& a, int* n_partials, hipStream_t stream) {
     const size_t frag = (size_t)(NRB * NB2 + 8 + 4) * 64 * 16 + (size_t)MF_WAVES * 3 * NRB * 256 * sizeof(float);     // tables + the three per-wave tiles
     const size_t slabs = (size_t)MF_WAVES * (nW + 32) * sizeof(float);
     const size_t lds = frag > slabs ? frag : slabs;
-    auto kern = cell_bwd_bf16_kernel<NB2, NARROW>;
-    if (int rc = stc::hip_status(stc::allow_lds(kern, lds), "hipFuncSetAttribute(cell bwd bf16)")) return rc;
-    static const int resident = stc::resident_blocks(kern, MF_THREADS, lds, 1);
-    const long long want = (a.nodes + MF_WAVES - 1) / MF_WAVES;
-    int grid = resident < MF_BWD_MAX_GRID ? resident : MF_BWD_MAX_GRID;
-    if (want < grid) grid = (int)want;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(MF_THREADS), lds, stream, a);
+    constexpr auto kern = cell_bwd_bf16_kernel<NB2, NARROW>;
+    if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(cell bwd bf16)", MF_THREADS, lds, 1, a.nodes, MF_WAVES, MF_BWD_MAX_GRID, n_partials)) return rc;
+    hipLaunchKernelGGL(kern, dim3(*n_partials), dim3(MF_THREADS), lds, stream, a);
     STC_LAUNCH_CHECK("cell_bwd_bf16 launch");
-    *n_partials = grid;
     return STC_OK;
 }
 
@@ -1273,30 +1249,23 @@ extern "C" int stc_bdg_node_bwd_bf16(const void* const* Z, int32_t Ks, const flo
         return stc::fail(STC_EUNSUPPORTED, "stc_bdg_node_bwd_bf16: shape Ks=%d Kc=%d C=%d L=%d Lw=%d Ho=%d not on the bf16 path", Ks, Kc, C, L, Lw, Ho);
     STC_REQUIRE(W && dW && (Kc == 1 || Tc), STC_EINVAL, "stc_bdg_node_bwd_bf16: null W/dW/Tc");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nW = Ks * Kc * Lw * Ho;
-    if (nodes == 0) {
-        if (int rc = stc::hip_status(hipMemsetAsync(dW, 0, (size_t)nW * sizeof(float), s), "memset dW")) return rc;
-        if (db) if (int rc = stc::hip_status(hipMemsetAsync(db, 0, (size_t)Ho * sizeof(float), s), "memset db")) return rc;
-        return STC_OK;
-    }
+    stc::ParamGrad g{dW, db, Ks * Kc * Lw * Ho, Ho, stc_bdg_node_bwd_workspace_bytes(Ks, Kc, C, L, Ho, 0)};
+    bool done;
+    if (int rc = stc::grad_tail_begin(__func__, &g, 1, nodes, workspace, workspace_bytes, STC_EALIGN, s, &done); rc || done) return rc;
     STC_REQUIRE(Z && dY && dZ, STC_EINVAL, "stc_bdg_node_bwd_bf16: null Z/dY/dZ");
     for (int n = 0; n < Ks; ++n)
         STC_REQUIRE(Z[n] && dZ[n] && stc::aligned16(Z[n]) && stc::aligned16(dZ[n]), STC_EALIGN,
                     "stc_bdg_node_bwd_bf16: Z[%d] / dZ[%d] null or not 16-byte aligned", n, n);
     STC_REQUIRE(stc::aligned16(dY), STC_EALIGN, "stc_bdg_node_bwd_bf16: dY not 16-byte aligned");
-    STC_REQUIRE(workspace && stc::aligned16(workspace), STC_EALIGN, "stc_bdg_node_bwd_bf16: workspace null or not 16-byte aligned");
-    STC_REQUIRE(workspace_bytes >= stc_bdg_node_bwd_workspace_bytes(Ks, Kc, C, L, Ho, 0), STC_EINVAL,
-                "stc_bdg_node_bwd_bf16: workspace of %zu B is too small", workspace_bytes);
-    float* partial = static_cast<float*>(workspace);
     int n_parts = 0;
     auto run = [&]() -> int {
-#define BWD_CALL(a, b, c, d) launch_bwd<a, b, c, d>(Z, Tc, W, dY, dZ, partial, &n_parts, db != nullptr, nodes, Lw, s)
+#define BWD_CALL(a, b, c, d) launch_bwd<a, b, c, d>(Z, Tc, W, dY, dZ, g.partial, &n_parts, db != nullptr, nodes, Lw, s)
         STC_BF16_DISPATCH(BWD_CALL)
 #undef BWD_CALL
         return stc::fail(STC_EUNSUPPORTED, "stc_bdg_node_bwd_bf16: no kernel for this shape");
     };
     if (int rc = run()) return rc;
-    return stc_node_reduce_partials(partial, n_parts, nW, Ho, dW, db, s);
+    return stc::grad_tail_reduce(&g, 1, n_parts, s);
 }
 
 // ---- planar STC_Cell on bf16 planes (K = 2, hidden 16)
@@ -1310,19 +1279,19 @@ extern "C" int stc_cell_gates_fwd_planar_bf16(const void* X, const void* H, cons
                                               const float* Wc, const float* bc, void* A, void* Bm,
                                               int64_t nodes, int32_t C, int32_t Lw, int32_t h, void* stream) {
     STC_REQUIRE(stc_cell_planar_bf16_supported(2, 2, C, h), STC_EUNSUPPORTED, "stc_cell_gates_fwd_planar_bf16: C=%d h=%d not on the bf16 planar path", C, h);
-    const int cin = Lw - 16;
-    STC_REQUIRE(cin == 16 || (cin >= 1 && cin <= 4), STC_EUNSUPPORTED, "stc_cell_gates_fwd_planar_bf16: input plane of %d columns (16, or 1..4)", cin);
+    const stc::PlanarRow row(Lw, h);
+    if (int rc = row.check_width(__func__, STC_EUNSUPPORTED)) return rc;
     STC_REQUIRE(nodes >= 0 && nodes < (1ll << 31) / C, STC_ELIMIT, "stc_cell_gates_fwd_planar_bf16: nodes=%lld", (long long)nodes);
     if (nodes == 0) return STC_OK;
     STC_REQUIRE(X && H && SX && SH && Tc && W && U && Rg && (RH || A), STC_EINVAL, "stc_cell_gates_fwd_planar_bf16: null pointer (RH may be NULL only with the fused candidate projection)");
     STC_REQUIRE((A == nullptr) == (Bm == nullptr) && (A == nullptr) == (Wc == nullptr), STC_EINVAL, "stc_cell_gates_fwd_planar_bf16: Wc, A, Bm go together");
     STC_REQUIRE(stc::aligned16(H) && stc::aligned16(SH) && stc::aligned16(U) && stc::aligned16(Rg) && stc::aligned16(RH) &&
-                    (cin != 16 || (stc::aligned16(X) && stc::aligned16(SX))) && (!A || (stc::aligned16(A) && stc::aligned16(Bm))),
+                    (row.narrow || (stc::aligned16(X) && stc::aligned16(SX))) && (!A || (stc::aligned16(A) && stc::aligned16(Bm))),
                 STC_EALIGN, "stc_cell_gates_fwd_planar_bf16: planes must be 16-byte aligned");
     const GatesFwd a{static_cast<const bf16_t*>(X), static_cast<const bf16_t*>(H), static_cast<const bf16_t*>(SX), static_cast<const bf16_t*>(SH),
                      static_cast<bf16_t*>(U), static_cast<bf16_t*>(Rg), static_cast<bf16_t*>(RH), Wc, bc, static_cast<bf16_t*>(A), static_cast<bf16_t*>(Bm)};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool narrow = cin != 16, post = A != nullptr;
+    const bool narrow = row.narrow, post = A != nullptr;
 #define GF(NB2_) (narrow ? (post ? launch_gates_fwd<NB2_, 1, 1>(a, Tc, W, bias, nodes, Lw, s) : launch_gates_fwd<NB2_, 1, 0>(a, Tc, W, bias, nodes, Lw, s)) \
                          : (post ? launch_gates_fwd<NB2_, 0, 1>(a, Tc, W, bias, nodes, Lw, s) : launch_gates_fwd<NB2_, 0, 0>(a, Tc, W, bias, nodes, Lw, s)))
     return C == 32 ? GF(1) : GF(2);
@@ -1339,26 +1308,21 @@ extern "C" int stc_cell_gates_bwd_planar_bf16(const void* X, const void* H, cons
                                               void* workspace, size_t workspace_bytes,
                                               int64_t nodes, int32_t C, int32_t Lw, int32_t h, void* stream) {
     STC_REQUIRE(stc_cell_planar_bf16_supported(2, 2, C, h), STC_EUNSUPPORTED, "stc_cell_gates_bwd_planar_bf16: C=%d h=%d not on the bf16 planar path", C, h);
-    const int cin = Lw - 16;
-    STC_REQUIRE(cin == 16 || (cin >= 1 && cin <= 4), STC_EUNSUPPORTED, "stc_cell_gates_bwd_planar_bf16: input plane of %d columns (16, or 1..4)", cin);
+    const stc::PlanarRow row(Lw, h);
+    if (int rc = row.check_width(__func__, STC_EUNSUPPORTED)) return rc;
     STC_REQUIRE(nodes >= 0 && nodes < (1ll << 31) / C, STC_ELIMIT, "stc_cell_gates_bwd_planar_bf16: nodes=%lld", (long long)nodes);
     STC_REQUIRE(W && dW && Tc, STC_EINVAL, "stc_cell_gates_bwd_planar_bf16: null W/dW/Tc");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nW = 4 * Lw * 32;
-    if (nodes == 0) {
-        if (int rc = stc::hip_status(hipMemsetAsync(dW, 0, (size_t)nW * sizeof(float), s), "memset dW")) return rc;
-        if (db) if (int rc = stc::hip_status(hipMemsetAsync(db, 0, 32 * sizeof(float), s), "memset db")) return rc;
-        return STC_OK;
-    }
-    const bool narrow = cin != 16;
+    stc::ParamGrad g{dW, db, 4 * Lw * 32, 32, stc_bdg_node_bwd_workspace_bytes(2, 2, C, 32, 32, 0)};      // (bf16 planes: rows of 32 whatever the input width)
+    bool done;
+    if (int rc = stc::grad_tail_begin(__func__, &g, 1, nodes, workspace, workspace_bytes, STC_EINVAL, s, &done); rc || done) return rc;
+    const bool narrow = row.narrow;
     STC_REQUIRE(X && H && SX && SH && dCandIn && Cand && U && Rg && dHnew && dZ && dZ[2] && dZ[3] && (narrow || (dZ[0] && dZ[1])), STC_EINVAL,
                 "stc_cell_gates_bwd_planar_bf16: null pointer");
     for (const void* q : {H, SH, dCandIn, Cand, U, Rg, dHnew, (const void*)dH, (const void*)dZ[2], (const void*)dZ[3]})       // (null dH is aligned)
         STC_REQUIRE(stc::aligned16(q), STC_EALIGN, "stc_cell_gates_bwd_planar_bf16: planes must be 16-byte aligned");
     if (!narrow) STC_REQUIRE(stc::aligned16(X) && stc::aligned16(SX) && stc::aligned16(dZ[0]) && stc::aligned16(dZ[1]), STC_EALIGN,
                              "stc_cell_gates_bwd_planar_bf16: planes must be 16-byte aligned");
-    STC_REQUIRE(workspace && stc::aligned16(workspace) && workspace_bytes >= stc_bdg_node_bwd_workspace_bytes(2, 2, C, 32, 32, 0), STC_EINVAL,
-                "stc_cell_gates_bwd_planar_bf16: workspace null, misaligned or too small (%zu B)", workspace_bytes);
     auto B = [](const void* q) { return static_cast<const bf16_t*>(q); };
     auto M = [](void* q) { return static_cast<bf16_t*>(q); };
     BPtrs2 zp{};
@@ -1366,7 +1330,7 @@ extern "C" int stc_cell_gates_bwd_planar_bf16(const void* X, const void* H, cons
     zp.p[0] = B(X); zp.p[1] = B(SX); zp.q[0] = B(H); zp.q[1] = B(SH);
     dzp.p[0] = narrow ? nullptr : M(dZ[0]); dzp.p[1] = narrow ? nullptr : M(dZ[1]); dzp.q[0] = M(dZ[2]); dzp.q[1] = M(dZ[3]);
     const GatesPro pro{B(dCandIn), B(Cand), B(H), B(U), B(Rg), B(dHnew), M(dH)};
-    float* partial = static_cast<float*>(workspace);
+    float* partial = g.partial;
     int n_parts = 0;
     // C = 64: one wave per SIMD with software prefetch (a 256-register two-wave build spilled: 2313 vs 1840 us per launch, not kept)
     const int rc = C == 32 ? (narrow ? launch_gates_bwd<1, 2>(zp, dzp, pro, Tc, W, partial, &n_parts, db != nullptr, nodes, Lw, s)
@@ -1374,7 +1338,7 @@ extern "C" int stc_cell_gates_bwd_planar_bf16(const void* X, const void* H, cons
                            : (narrow ? launch_gates_bwd<2, 2, 1>(zp, dzp, pro, Tc, W, partial, &n_parts, db != nullptr, nodes, Lw, s)
                                      : launch_gates_bwd<2, 1, 1>(zp, dzp, pro, Tc, W, partial, &n_parts, db != nullptr, nodes, Lw, s));
     if (rc != STC_OK) return rc;
-    return stc_node_reduce_partials(partial, n_parts, nW, 32, dW, db, s);
+    return stc::grad_tail_reduce(&g, 1, n_parts, s);
 }
 
 // ---- the whole backward of a planar cell step on bf16 planes in one launch (cell_bwd_bf16_kernel)
@@ -1395,39 +1359,28 @@ extern "C" int stc_cell_bwd_planar_bf16(const void* X, const void* H, const void
                                         int64_t nodes, int32_t C, int32_t Lw, int32_t h, void* stream) {
     STC_REQUIRE(stc_cell_bwd_planar_bf16_supported(C, Lw, h), STC_EUNSUPPORTED,
                 "stc_cell_bwd_planar_bf16: C=%d h=%d input width %d is not built (C = 32: 16 or 1..4 columns; C = 64: 16)", C, h, Lw - h);
-    const int cin = Lw - 16;
     STC_REQUIRE(nodes >= 0 && nodes < (1ll << 31) / C, STC_ELIMIT, "stc_cell_bwd_planar_bf16: nodes=%lld", (long long)nodes);
     STC_REQUIRE(Wg && Wc && dWg && dWc && Tc, STC_EINVAL, "stc_cell_bwd_planar_bf16: null W/dW/Tc");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nWg = 4 * Lw * 32, nWc = 4 * Lw * 16;
-    if (nodes == 0) {
-        if (int rc = stc::hip_status(hipMemsetAsync(dWg, 0, (size_t)nWg * sizeof(float), s), "memset dWg")) return rc;
-        if (int rc = stc::hip_status(hipMemsetAsync(dWc, 0, (size_t)nWc * sizeof(float), s), "memset dWc")) return rc;
-        if (dbg) if (int rc = stc::hip_status(hipMemsetAsync(dbg, 0, 32 * sizeof(float), s), "memset dbg")) return rc;
-        if (dbc) if (int rc = stc::hip_status(hipMemsetAsync(dbc, 0, 16 * sizeof(float), s), "memset dbc")) return rc;
-        return STC_OK;
-    }
-    const bool narrow = cin != 16;
+    stc::ParamGrad g[2] = {{dWg, dbg, 4 * Lw * 32, 32, stc_bdg_node_bwd_workspace_bytes(2, 2, C, 32, 32, 0)},      // gates, then candidate
+                           {dWc, dbc, 4 * Lw * 16, 16, stc_bdg_node_bwd_workspace_bytes(2, 2, C, 32, 16, 0)}};
+    bool done;
+    if (int rc = stc::grad_tail_begin(__func__, g, 2, nodes, workspace, workspace_bytes, STC_EINVAL, s, &done); rc || done) return rc;
+    const bool narrow = stc::PlanarRow(Lw, h).narrow;       // (its width: checked by stc_cell_bwd_planar_bf16_supported)
     STC_REQUIRE(X && H && SX && SH && U && Rg && Cand && dHnew && dBm && dH && dSH && (narrow || (dX && dSX)), STC_EINVAL, "stc_cell_bwd_planar_bf16: null pointer");
     for (const void* q : {H, SH, U, Rg, Cand, dHnew, dBm, (const void*)dH, (const void*)dSH})
         STC_REQUIRE(stc::aligned16(q), STC_EALIGN, "stc_cell_bwd_planar_bf16: planes must be 16-byte aligned");
     if (!narrow) STC_REQUIRE(stc::aligned16(X) && stc::aligned16(SX) && stc::aligned16(dX) && stc::aligned16(dSX), STC_EALIGN,
                              "stc_cell_bwd_planar_bf16: planes must be 16-byte aligned");
-    const size_t bytes_g = stc_bdg_node_bwd_workspace_bytes(2, 2, C, 32, 32, 0);
-    STC_REQUIRE(workspace && stc::aligned16(workspace) && workspace_bytes >= bytes_g + stc_bdg_node_bwd_workspace_bytes(2, 2, C, 32, 16, 0), STC_EINVAL,
-                "stc_cell_bwd_planar_bf16: workspace null, misaligned or too small (%zu B)", workspace_bytes);
     auto B = [](const void* q) { return static_cast<const bf16_t*>(q); };
     auto M = [](void* q) { return static_cast<bf16_t*>(q); };
-    float* partial_g = static_cast<float*>(workspace);
-    float* partial_c = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + bytes_g);
     const CellBwdB16 a{B(X), B(H), B(SX), B(SH), B(U), B(Rg), B(Cand), B(dHnew), B(dBm), Tc, Wg, Wc, M(dX), M(dSX), M(dH), M(dSH),
-                       partial_g, partial_c, (int)nodes, dbg != nullptr, dbc != nullptr, Lw};
+                       g[0].partial, g[1].partial, (int)nodes, dbg != nullptr, dbc != nullptr, Lw};
     int n_parts = 0;
     const int rc = C == 32 ? (narrow ? launch_cell_bwd<1, 1>(a, &n_parts, s) : launch_cell_bwd<1, 0>(a, &n_parts, s))
                            : launch_cell_bwd<2, 0>(a, &n_parts, s);
     if (rc != STC_OK) return rc;
-    if (int r2 = stc_node_reduce_partials(partial_g, n_parts, nWg, 32, dWg, dbg, s)) return r2;
-    return stc_node_reduce_partials(partial_c, n_parts, nWc, 16, dWc, dbc, s);
+    return stc::grad_tail_reduce(g, 2, n_parts, s);
 }
 
 // post-aggregation backward of the candidate convolution on planes: wide -- X (columns 0..15), X2 (16..31), gradients dX, dX2;
@@ -1436,32 +1389,27 @@ extern "C" int stc_bdg_node_post_bwd_bf16(const void* X, const void* X2, const f
                                           void* dX, void* dX2, float* dW, float* db, void* workspace, size_t workspace_bytes,
                                           int64_t nodes, int32_t C, int32_t Lw, int32_t Ho, void* stream) {
     STC_REQUIRE((C == 32 || C == 64) && Ho == 16, STC_EUNSUPPORTED, "stc_bdg_node_post_bwd_bf16: C=%d Ho=%d not on the bf16 planar path", C, Ho);
-    const int cin = Lw - 16;
-    STC_REQUIRE(cin == 16 || (cin >= 1 && cin <= 4), STC_EUNSUPPORTED, "stc_bdg_node_post_bwd_bf16: second plane of %d columns (16, or 1..4)", cin);
+    const stc::PlanarRow row(Lw, 16);        // X: the 16-wide plane, X2: the second plane of the row
+    if (int rc = row.check_width(__func__, STC_EUNSUPPORTED)) return rc;
     STC_REQUIRE(nodes >= 0 && nodes < (1ll << 31) / C, STC_ELIMIT, "stc_bdg_node_post_bwd_bf16: nodes=%lld", (long long)nodes);
     STC_REQUIRE(W && dW && Tc, STC_EINVAL, "stc_bdg_node_post_bwd_bf16: null W/dW/Tc");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nW = 4 * Lw * 16;
-    if (nodes == 0) {
-        if (int rc = stc::hip_status(hipMemsetAsync(dW, 0, (size_t)nW * sizeof(float), s), "memset dW")) return rc;
-        if (db) if (int rc = stc::hip_status(hipMemsetAsync(db, 0, 16 * sizeof(float), s), "memset db")) return rc;
-        return STC_OK;
-    }
-    const bool narrow = cin != 16;
+    stc::ParamGrad g{dW, db, 4 * Lw * 16, 16, stc_bdg_node_bwd_workspace_bytes(2, 2, C, 32, 16, 0)};
+    bool done;
+    if (int rc = stc::grad_tail_begin(__func__, &g, 1, nodes, workspace, workspace_bytes, STC_EINVAL, s, &done); rc || done) return rc;
+    const bool narrow = row.narrow;
     STC_REQUIRE(X && X2 && dA && dB && dX && (narrow ? dX2 == nullptr : dX2 != nullptr), STC_EINVAL,
                 "stc_bdg_node_post_bwd_bf16: null pointer (the narrow input plane gets no gradient: dX2 must be null there)");
     STC_REQUIRE(stc::aligned16(X) && stc::aligned16(dA) && stc::aligned16(dB) && stc::aligned16(dX) && (narrow || (stc::aligned16(X2) && stc::aligned16(dX2))),
                 STC_EALIGN, "stc_bdg_node_post_bwd_bf16: planes must be 16-byte aligned");
-    STC_REQUIRE(workspace && stc::aligned16(workspace) && workspace_bytes >= stc_bdg_node_bwd_workspace_bytes(2, 2, C, 32, 16, 0), STC_EINVAL,
-                "stc_bdg_node_post_bwd_bf16: workspace null, misaligned or too small (%zu B)", workspace_bytes);
     auto B = [](const void* q) { return static_cast<const bf16_t*>(q); };
-    float* partial = static_cast<float*>(workspace);
+    float* partial = g.partial;
     int n_parts = 0;
 #define PB(NB2_, NAR_) launch_post_bwd<NB2_, NAR_>(B(X), B(X2), Tc, W, B(dA), B(dB), static_cast<bf16_t*>(dX), static_cast<bf16_t*>(dX2), partial, &n_parts, db != nullptr, nodes, Lw, s)
     const int rc = C == 32 ? (narrow ? PB(1, 1) : PB(1, 0)) : (narrow ? PB(2, 1) : PB(2, 0));
 #undef PB
     if (rc != STC_OK) return rc;
-    return stc_node_reduce_partials(partial, n_parts, nW, 16, dW, db, s);
+    return stc::grad_tail_reduce(&g, 1, n_parts, s);
 }
 
 extern "C" int stc_gru_blend_bwd_bf16(const void* dHnew, const void* U, const void* Cand, void* dCpre, int64_t n, void* stream) {

@@ -3,8 +3,7 @@
 // MFMAs of gfx950 -- lane (x = lane & 15, g = lane >> 4), register r  <->  tile row 4g + r, tile column x -- so the
 // per-node gradient fragments, the fused cell prologue / epilogue operands and the dW combine are common.
 #pragma once
-#include "stc_common.h"
-#include "stc_node_mfma.h"
+#include "stc_node_host.h"
 
 namespace {
 

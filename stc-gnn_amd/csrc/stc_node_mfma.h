@@ -1,6 +1,8 @@
-// Internal: MFMA fast path of the node kernels (stc_node_mfma.hip), tried first by the C entry
-// points in stc_node.hip.  Returns STC_OK when it launched, STC_NOT_HANDLED when the shape is
-// outside the fast path (the generic VALU kernels then run), or an error code.
+// Internal interface between the C entry points of the node / cell kernels (stc_node.hip) and the kernel files of the dispatch levels
+// (stc_set_dispatch_level) behind them: the split-operand matrix-core kernels (stc_node_x3.hip, stc_cell_bwd_x3.hip), tried first, and the
+// fp32 MFMA ones (stc_node_mfma.hip); the generic VALU kernels live in stc_node.hip itself.  Every function returns STC_OK when it launched,
+// STC_NOT_HANDLED when the shape or the operands are outside its kernels (the entry point then tries the next level, or refuses with
+// STC_EUNSUPPORTED), or an error code.  The host-side checks the entry points share are in stc_node_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

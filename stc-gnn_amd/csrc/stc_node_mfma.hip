@@ -433,13 +433,11 @@ int launch_fwd(const float* const* Z, const float* Tc, const float* W, const flo
     constexpr int NCB = K * HB;
     const size_t lds = (size_t)(K * LQ * NCB * 64 + (K - 1) * NRB * NRB * 4 * 64) * sizeof(float);
     if (lds > stc::kMaxLdsBytes) return STC_NOT_HANDLED;
-    auto kern = node_fwd_mfma_kernel<NRB, HB, K, LQ, EPI>;
-    if (int rc = stc::hip_status(stc::allow_lds(kern, lds), "hipFuncSetAttribute(node fwd mfma)")) return rc;
-    static const int resident = stc::resident_blocks(kern, MF_THREADS, lds, 2);   // persistent grid = what fits at once
+    constexpr auto kern = node_fwd_mfma_kernel<NRB, HB, K, LQ, EPI>;
+    int grid;
+    if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(node fwd mfma)", MF_THREADS, lds, 2, nodes, MF_WAVES, INT_MAX, &grid)) return rc;
     ZPtrs zp{};
     for (int n = 0; n < K; ++n) zp.p[n] = Z[n];
-    const long long want = (nodes + MF_WAVES - 1) / MF_WAVES;
-    const int grid = (int)(want < resident ? want : resident);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MF_THREADS), lds, stream, zp, Tc, W, bias, Y, (int)nodes, Lw, epi, Cr);
     STC_LAUNCH_CHECK("node_fwd_mfma launch");
     return STC_OK;
@@ -453,18 +451,13 @@ int launch_bwd(const float* const* Z, const float* Tc, const float* W, const flo
     const size_t slabs = (size_t)MF_WAVES * (nW + Ho);
     const size_t lds = (frag > slabs ? frag : slabs) * sizeof(float);
     if (lds > stc::kMaxLdsBytes) return STC_NOT_HANDLED;
-    auto kern = node_bwd_mfma_kernel<NRB, HB, K, LQ, PRO>;
-    if (int rc = stc::hip_status(stc::allow_lds(kern, lds), "hipFuncSetAttribute(node bwd mfma)")) return rc;
-    static const int resident = stc::resident_blocks(kern, MF_THREADS, lds, 1);
+    constexpr auto kern = node_bwd_mfma_kernel<NRB, HB, K, LQ, PRO>;
+    if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(node bwd mfma)", MF_THREADS, lds, 1, nodes, MF_WAVES, MF_BWD_MAX_GRID, n_partials)) return rc;
     ZPtrs zp{};
     DZPtrs dzp{};
     for (int n = 0; n < K; ++n) { zp.p[n] = Z[n]; dzp.p[n] = dZ[n]; }
-    const long long want = (nodes + MF_WAVES - 1) / MF_WAVES;
-    int grid = resident < MF_BWD_MAX_GRID ? resident : MF_BWD_MAX_GRID;
-    if (want < grid) grid = (int)want;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(MF_THREADS), lds, stream, zp, Tc, W, dY, dzp, partial, (int)nodes, want_db, Lw, pro, Cr);
+    hipLaunchKernelGGL(kern, dim3(*n_partials), dim3(MF_THREADS), lds, stream, zp, Tc, W, dY, dzp, partial, (int)nodes, want_db, Lw, pro, Cr);
     STC_LAUNCH_CHECK("node_bwd_mfma launch");
-    *n_partials = grid;
     return STC_OK;
 }
 

@@ -1282,13 +1282,11 @@ int launch_fwd(const float* const* Z, const float* Tc, const float* W, const flo
     const size_t lds = (size_t)(K * NCB + (K - 1) * NRB * NB2 + (POST ? K * K : 0)) * F::NP * 64 * 16
                        + ((POST ? 1 : 0) + (EPI == EPI_GATES && PL != 0 ? 1 : 0)) * (size_t)MF_WAVES * NRB * 16 * 20 * 4;      // R*H tile (POST), H tile (planar gates)
     if (lds > stc::kMaxLdsBytes) return STC_NOT_HANDLED;
-    auto kern = node_fwd_x3_kernel<NB2, HB, K, L, EPI, PL, POST, F>;
-    if (int rc = stc::hip_status(stc::allow_lds(kern, lds), "hipFuncSetAttribute(node fwd x3)")) return rc;
-    static const int resident = stc::resident_blocks(kern, MF_THREADS, lds, 2);   // persistent grid = what fits at once
+    constexpr auto kern = node_fwd_x3_kernel<NB2, HB, K, L, EPI, PL, POST, F>;
+    int grid;
+    if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(node fwd x3)", MF_THREADS, lds, 2, nodes, MF_WAVES, INT_MAX, &grid)) return rc;
     ZPtrs zp{};
     for (int n = 0; n < K; ++n) { zp.p[n] = Z[n]; if (PL) zp.q[n] = Z[K + n]; }      // planar: Z = {X planes, H planes}
-    const long long want = (nodes + MF_WAVES - 1) / MF_WAVES;
-    const int grid = (int)(want < resident ? want : resident);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MF_THREADS), lds, stream, zp, Tc, W, bias, Y, (int)nodes, Lw, epi, post);
     STC_LAUNCH_CHECK("node_fwd_x3 launch");
     return STC_OK;
@@ -1304,18 +1302,13 @@ int launch_bwd(const float* const* Z, const float* Tc, const float* W, const flo
     const size_t slabs = (size_t)MF_WAVES * (nW + Ho) * sizeof(float);
     const size_t lds = frag > slabs ? frag : slabs;
     if (lds > stc::kMaxLdsBytes) return STC_NOT_HANDLED;
-    auto kern = node_bwd_x3_kernel<NB2, HB, K, L, PRO, PL, FOLD, ACC, F>;
-    if (int rc = stc::hip_status(stc::allow_lds(kern, lds), "hipFuncSetAttribute(node bwd x3)")) return rc;
-    static const int resident = stc::resident_blocks(kern, MF_THREADS, lds, BwdSched<NB2, K>::waves);
+    constexpr auto kern = node_bwd_x3_kernel<NB2, HB, K, L, PRO, PL, FOLD, ACC, F>;
+    if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(node bwd x3)", MF_THREADS, lds, BwdSched<NB2, K>::waves, nodes, MF_WAVES, MF_BWD_MAX_GRID, n_partials)) return rc;
     ZPtrs zp{};
     DZPtrs dzp{};
     for (int n = 0; n < K; ++n) { zp.p[n] = Z[n]; dzp.p[n] = dZ[n]; if (PL) { zp.q[n] = Z[K + n]; dzp.q[n] = dZ[K + n]; } }
-    const long long want = (nodes + MF_WAVES - 1) / MF_WAVES;
-    int grid = resident < MF_BWD_MAX_GRID ? resident : MF_BWD_MAX_GRID;
-    if (want < grid) grid = (int)want;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(MF_THREADS), lds, stream, BwdArgs{zp, Tc, W, dY, dzp, partial, (int)nodes, want_db, Lw, pro});
+    hipLaunchKernelGGL(kern, dim3(*n_partials), dim3(MF_THREADS), lds, stream, BwdArgs{zp, Tc, W, dY, dzp, partial, (int)nodes, want_db, Lw, pro});
     STC_LAUNCH_CHECK("node_bwd_x3 launch");
-    *n_partials = grid;
     return STC_OK;
 }
 
@@ -1454,15 +1447,10 @@ static int launch_bwd2(const float* X, const float* X2, const float* Tc, const f
     const size_t slabs = (size_t)MF_WAVES * (nW + Ho) * sizeof(float);
     const size_t lds = frag > slabs ? frag : slabs;
     if (lds > stc::kMaxLdsBytes) return STC_NOT_HANDLED;
-    auto kern = node_bwd2_x3_kernel<NB2, HB, L, PL, F>;
-    if (int rc = stc::hip_status(stc::allow_lds(kern, lds), "hipFuncSetAttribute(node bwd2 x3)")) return rc;
-    static const int resident = stc::resident_blocks(kern, MF_THREADS, lds, NB2 == 1 ? 2 : 1);
-    const long long want = (nodes + MF_WAVES - 1) / MF_WAVES;
-    int grid = resident < MF_BWD_MAX_GRID ? resident : MF_BWD_MAX_GRID;
-    if (want < grid) grid = (int)want;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(MF_THREADS), lds, stream, Bwd2Args{X, X2, Tc, W, dA, dB, dX, dX2, partial, (int)nodes, want_db, Lw, zmax_x, zmax_x2});
+    constexpr auto kern = node_bwd2_x3_kernel<NB2, HB, L, PL, F>;
+    if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(node bwd2 x3)", MF_THREADS, lds, NB2 == 1 ? 2 : 1, nodes, MF_WAVES, MF_BWD_MAX_GRID, n_partials)) return rc;
+    hipLaunchKernelGGL(kern, dim3(*n_partials), dim3(MF_THREADS), lds, stream, Bwd2Args{X, X2, Tc, W, dA, dB, dX, dX2, partial, (int)nodes, want_db, Lw, zmax_x, zmax_x2});
     STC_LAUNCH_CHECK("node_bwd2_x3 launch");
-    *n_partials = grid;
     return STC_OK;
 }
 
@@ -1471,11 +1459,9 @@ static int launch_fwd2(const float* X, const float* X2, const float* Tc, const f
                        long long nodes, int Lw, hipStream_t stream) {
     constexpr int K = 2, NRB = 2 * NB2, NCB = K * HB;
     const size_t lds = (size_t)(K * NCB + NRB * NB2) * 3 * 64 * 16;
-    auto kern = node_fwd2_x3_kernel<NB2, HB, L, PL>;
-    if (int rc = stc::hip_status(stc::allow_lds(kern, lds), "hipFuncSetAttribute(node fwd2 x3)")) return rc;
-    static const int resident = stc::resident_blocks(kern, MF_THREADS, lds, NB2 == 1 ? 2 : 1);
-    const long long want = (nodes + MF_WAVES - 1) / MF_WAVES;
-    const int grid = (int)(want < resident ? want : resident);
+    constexpr auto kern = node_fwd2_x3_kernel<NB2, HB, L, PL>;
+    int grid;
+    if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(node fwd2 x3)", MF_THREADS, lds, NB2 == 1 ? 2 : 1, nodes, MF_WAVES, INT_MAX, &grid)) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MF_THREADS), lds, stream, X, X2, Tc, W, bias, A, Bm, (int)nodes, Lw);
     STC_LAUNCH_CHECK("node_fwd2_x3 launch");
     return STC_OK;
