@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define STC_ABI_VERSION 33
+#define STC_ABI_VERSION 34
 #define STC_MAX_K 4          /* highest Chebyshev order (Ks, Kc) the node kernels accept */
 
 /* Operand formats of the split-operand matrix-core kernels (C = 32 / 64, hidden 16).  Every fp32 operand is split into low-precision
@@ -164,7 +164,8 @@ int stc_ring2_sum_f32(const int32_t* l2_rows, const int32_t* l1_rows, const int3
                       int32_t batch, int32_t C, int32_t h, void* stream);
 /* The forward counterpart on the same plan format (built for Gs^T): stc_spmm_blend_fwd_f32 (without state copies) and the plain aggregation
  * of the new state that follows it, in one launch -- the new state is aggregated out of LDS instead of being read back:
- *     Cand = tanh(A + S.Bm)      Hnew = (1 - U) H + U Cand      SHnew = S.Hnew          (reference STC_GNN.py:76-78, then :37 of the next cell) */
+ *     Cand = tanh(A + S.Bm)      Hnew = (1 - U) H + U Cand      SHnew = S.Hnew          (reference STC_GNN.py:76-78, then :37 of the next cell)
+ * Cand may be NULL (ABI v34): the candidate is then not stored -- only a backward reads it; Hnew and SHnew are bit for bit the same. */
 int stc_ring2_blend_f32(const int32_t* l2_rows, const int32_t* l1_rows, const int32_t* int_rows, const int32_t* t1, const int32_t* t2,
                         int32_t n_patches, int32_t n_rows,
                         const float* Bm, const float* A, const float* U, const float* H,
@@ -346,7 +347,9 @@ int stc_bdg_node_post_fwd_f32(const float* X, const float* X2, const float* Tc, 
                               float* A, float* Bm,
                               int64_t nodes, int32_t C, int32_t L, int32_t Lw, int32_t Ho, void* stream);
 /* Y = A + S x Bm on rows of C*h floats (h = 16) with the blend as epilogue: Cand = tanh(Y), Hnew = (1-U)*H + U*Cand,
- * plus the optional state copies / side columns of stc_cell_blend_fwd_f32.  Graph as either form (see stc_spmm_bwd_*). */
+ * plus the optional state copies / side columns of stc_cell_blend_fwd_f32.  Graph as either form (see stc_spmm_bwd_*).
+ * Cand may be NULL (ABI v34), with or without state copies: the candidate is then not stored (a forward that no backward follows);
+ * Hnew and the copies are bit for bit the same. */
 int stc_spmm_blend_fwd_f32(const int32_t* rowptr, const int32_t* colidx, const float* val,
                            const int32_t* blk_ptr, const int32_t* blk_cols, const float* blk_vals,
                            int32_t n_rows, int32_t n_cols, const float* Bm, const float* A,
@@ -428,7 +431,9 @@ int stc_cell_planar_supported(int32_t Ks, int32_t Kc, int32_t C, int32_t h);
 /* A != NULL: the same launch also runs the candidate convolution's projection on [Xt | R*H], which the wave still
  * holds in registers: A, Bm (nodes, C, h) as stc_bdg_node_post_fwd_f32 would give for weights Wc (4*Lw, h) and bias bc --
  * that launch and its re-read of Xt and R*H are then not needed.  RH may then be NULL (not written): stc_cell_bwd_planar_f32
- * forms R*H itself; stc_bdg_node_post_bwd_f32 needs the plane. */
+ * forms R*H itself; stc_bdg_node_post_bwd_f32 needs the plane.  Rg may be NULL too (ABI v34), likewise ONLY with A != NULL: the reset
+ * gate then feeds R*H and the projection from registers and is not stored (a forward that no backward follows).  U, RH, A, Bm and
+ * act_amax are bit for bit what the launch with the plane gives. */
 int stc_cell_gates_fwd_planar_f32(const float* X, const float* H, const float* SX, const float* SH,
                                   const float* Tc, const float* W, const float* bias,
                                   float* U, float* Rg, float* RH,
@@ -481,8 +486,10 @@ int stc_cell_bwd_planar_f32(const float* X, const float* H, const float* SX, con
  * 2 S (S x plane) - plane, the feature-side Chebyshev recurrence -- each (nodes, C, h); a narrow input (layer 0) has Zx[n]
  * (nodes, C, Lw - h) with Lw - h in 1..4.  A state's three planes are computed once and shared by the cells that consume it.
  *   gates_fwd: U, Rg, RH = R*H as stc_cell_gates_fwd_planar_f32.            W (K*K*Lw, 2h)
+ *              Rg may be NULL (ABI v34; not stored); RH is required: the candidate's planes are aggregated from it.
  *   cand_fwd:  candidate convolution on [X | R*H] (Zh[n] = T_n(S) R*H) with the tanh + GRU blend epilogue of
  *              stc_cell_blend_fwd_f32: Cand, Hnew from U and the previous state H.      W (K*K*Lw, h)
+ *              Cand may be NULL (ABI v34; not stored).  Either way the other results are bit for bit the same.
  *   *_bwd:     gradients of all 2K planes (dZx[n], dZh[n]; dZx may be NULL for a narrow input) and of W, b; the gate /
  *              blend backward run as prologues exactly as in stc_cell_gates_bwd_planar_f32 / stc_cell_cand_bwd_f32.
  * gates_bwd with accumulate_x != 0 (wide input, dH = NULL): dZx[n] already hold the candidate convolution's gradients of the same X-side

@@ -481,7 +481,8 @@ extern "C" int stc_cell_gates_fwd_planar_f32(const float* X, const float* H, con
     if (int rc = row.check_width(__func__, STC_EINVAL)) return rc;
     if (!stc_cell_planar_supported(2, 2, C, h)) return stc::fail(STC_EUNSUPPORTED, "stc_cell_gates_fwd_planar_f32: shape not on the planar path");
     if (nodes == 0) return STC_OK;
-    STC_REQUIRE(X && H && SX && SH && Tc && W && U && Rg && (RH || A), STC_EINVAL, "stc_cell_gates_fwd_planar_f32: null pointer");
+    // (Rg and RH are optional with the fused candidate projection: a forward-only caller reads neither; the gate still feeds R*H in registers)
+    STC_REQUIRE(X && H && SX && SH && Tc && W && U && (Rg || A) && (RH || A), STC_EINVAL, "stc_cell_gates_fwd_planar_f32: null pointer");
     STC_REQUIRE((A == nullptr) == (Bm == nullptr) && (!A || Wc), STC_EINVAL, "stc_cell_gates_fwd_planar_f32: A, Bm and Wc go together");
     const int rc = stc_cell_gates_fwd_planar_x3(X, H, SX, SH, Tc, W, bias, U, Rg, RH, Wc, bc, A, Bm, operand_format, act_amax, nodes, C, Lw, static_cast<hipStream_t>(stream));
     return stc::dispatched(__func__, rc);
@@ -577,7 +578,7 @@ extern "C" int stc_cell_gates_fwd_planar_k_f32(const float* const* Zx, const flo
     if (int rc = planar_k_common("stc_cell_gates_fwd_planar_k_f32", Zx, Zh, K, C, Lw, h, 2 * h, nodes)) return rc;
     if (int rc = stc::check_operand_format(__func__, operand_format)) return rc;
     if (nodes == 0) return STC_OK;
-    STC_REQUIRE(Tc && W && U && Rg && RH, STC_EINVAL, "stc_cell_gates_fwd_planar_k_f32: null pointer");
+    STC_REQUIRE(Tc && W && U && RH, STC_EINVAL, "stc_cell_gates_fwd_planar_k_f32: null pointer");      // (Rg may be null: not stored)
     const int rc = stc_cell_conv_fwd_planar_k_x3(Zx, Zh, K, Tc, W, bias, 1, Zh[0], nullptr, U, Rg, RH, nullptr, nullptr, operand_format, act_amax, nodes, C, Lw, static_cast<hipStream_t>(stream));
     return stc::dispatched(__func__, rc);
 }
@@ -588,8 +589,8 @@ extern "C" int stc_cell_cand_fwd_planar_k_f32(const float* const* Zx, const floa
     if (int rc = planar_k_common("stc_cell_cand_fwd_planar_k_f32", Zx, Zh, K, C, Lw, h, h, nodes)) return rc;
     if (int rc = stc::check_operand_format(__func__, operand_format)) return rc;
     if (nodes == 0) return STC_OK;
-    STC_REQUIRE(Tc && W && U && H && Cand && Hnew, STC_EINVAL, "stc_cell_cand_fwd_planar_k_f32: null pointer");
-    STC_REQUIRE(stc::aligned16(U) && stc::aligned16(H) && stc::aligned16(Cand) && stc::aligned16(Hnew), STC_EALIGN, "stc_cell_cand_fwd_planar_k_f32: misaligned operand");
+    STC_REQUIRE(Tc && W && U && H && Hnew, STC_EINVAL, "stc_cell_cand_fwd_planar_k_f32: null pointer");      // (Cand may be null: not stored)
+    STC_REQUIRE(stc::aligned16(U) && stc::aligned16(H) && (!Cand || stc::aligned16(Cand)) && stc::aligned16(Hnew), STC_EALIGN, "stc_cell_cand_fwd_planar_k_f32: misaligned operand");
     const int rc = stc_cell_conv_fwd_planar_k_x3(Zx, Zh, K, Tc, W, bias, 2, H, U, nullptr, nullptr, nullptr, Cand, Hnew, operand_format, act_amax, nodes, C, Lw, static_cast<hipStream_t>(stream));
     return stc::dispatched(__func__, rc);
 }

@@ -327,7 +327,7 @@ __global__ __launch_bounds__(MF_THREADS, (NB2 == 1 ? 2 : 1)) void node_fwd_x3_ke
                 for (int rb = 0; rb < NRB; ++rb)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) gt[rb][r] = fast_sigmoid(F::SCALED ? fmaf(acc[rb][HB - 1][r], invn, bv[HB - 1]) : acc[rb][HB - 1][r] + bv[HB - 1]);
-                put_plane(epi.R_out, gt);
+                if (epi.R_out) put_plane(epi.R_out, gt);                // (optional: a forward-only caller has no use for the reset gate)
 #pragma unroll
                 for (int rb = 0; rb < NRB; ++rb)
 #pragma unroll
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(MF_THREADS, (NB2 == 1 ? 2 : 1)) void node_fwd_x3_ke
                     const float c = fast_tanh(F::SCALED ? fmaf(acc[rb][0][r], invn, bv[0]) : acc[rb][0][r] + bv[0]);
                     const float u = uv[rb][r];
                     hn[rb][r] = (1.f - u) * hv[rb][r] + u * c;
-                    epi.Cand[e] = c;
+                    if (epi.Cand) epi.Cand[e] = c;                          // (optional: only a backward reads the candidate)
                     epi.Hnew[e] = hn[rb][r];
                 }
             store_state_copies<NRB>(epi, (size_t)node * C, x, g, hn);

@@ -95,7 +95,7 @@ __device__ __forceinline__ void blend_piece(const EpiArgs& a, size_t rowg, int c
     const float4 c = make_float4(tanh_fast(v.x), tanh_fast(v.y), tanh_fast(v.z), tanh_fast(v.w));
     const float4 hn = make_float4((1.f - u.x) * hh.x + u.x * c.x, (1.f - u.y) * hh.y + u.y * c.y,
                                   (1.f - u.z) * hh.z + u.z * c.z, (1.f - u.w) * hh.w + u.w * c.w);
-    nt_store4(reinterpret_cast<float4*>(a.Cand + 4 * o), c);
+    if (a.Cand) nt_store4(reinterpret_cast<float4*>(a.Cand + 4 * o), c);     // (optional: only a backward reads the candidate)
     nt_store4(reinterpret_cast<float4*>(a.Hnew + 4 * o), hn);
     const int q4 = ch & 3;
     const size_t e = rowg * a.C + (ch >> 2);
@@ -733,8 +733,8 @@ extern "C" int stc_spmm_blend_fwd_f32(const int32_t* rowptr, const int32_t* coli
     STC_REQUIRE(h == 16, STC_EUNSUPPORTED, "stc_spmm_blend_fwd_f32: hidden width %d (the blend epilogue is built for 16)", h);
     if (int rc = check_fused("stc_spmm_blend_fwd_f32", g, n_rows, n_cols, Bm, A, batch, C, 0, h, 0)) return rc;
     if (n_rows == 0 || batch == 0) return STC_OK;
-    STC_REQUIRE(U && H && Cand && Hnew, STC_EINVAL, "stc_spmm_blend_fwd_f32: null pointer");
-    STC_REQUIRE(stc::aligned16(U) && stc::aligned16(H) && stc::aligned16(Cand) && stc::aligned16(Hnew), STC_EALIGN,
+    STC_REQUIRE(U && H && Hnew, STC_EINVAL, "stc_spmm_blend_fwd_f32: null pointer");      // (Cand may be null: not stored)
+    STC_REQUIRE(stc::aligned16(U) && stc::aligned16(H) && (!Cand || stc::aligned16(Cand)) && stc::aligned16(Hnew), STC_EALIGN,
                 "stc_spmm_blend_fwd_f32: operands must be 16-byte aligned");
     STC_REQUIRE(Bm != Cand && Bm != Hnew, STC_EINVAL, "stc_spmm_blend_fwd_f32: outputs must not alias Bm (its rows are gathered by other rows)");
     STC_REQUIRE((!copy0 || (copy0_off >= 0 && copy0_off + h <= copy0_ld)) && (!copy1 || (copy1_off >= 0 && copy1_off + h <= copy1_ld)),

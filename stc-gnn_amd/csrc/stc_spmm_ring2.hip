@@ -56,7 +56,7 @@ struct Ring2Args {
 
 // What the first ring computes from the gathered sum and the slot's own operands, and which of it the second aggregation takes:
 //   R2_SUM    dH = sum + addends (stored for interior rows);            V = dH U (1 - Cand^2)              -> Z = S.V = dBm
-//   R2_BLEND  Cand = tanh(sum + A), Hnew = (1 - U) H + U Cand (both stored: the forward of stc_spmm_blend_fwd_f32);  V = Hnew  -> Z = S.Hnew
+//   R2_BLEND  Cand = tanh(sum + A), Hnew = (1 - U) H + U Cand (both stored, Cand if Y is given: the forward of stc_spmm_blend_fwd_f32);  V = Hnew  -> Z = S.Hnew
 //   R2_CHAIN  V = alpha1 sum + addends (stored for interior rows if Y is given)   -> Z = alpha2 S.V + sum_k scale0[k] add0[k]: two chained
 //             aggregations of the order-3 feature recurrence -- forward 2 S.(S.X) - X (STC_GNN.py:24-29 applied to the feature side, :37), and
 //             its transpose in Clenshaw form, d0 - d2 + S^T (d1 + 2 S^T d2)
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(R2_THREADS, 2) void ring2_sum_kernel(Ring2Args a) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) { cand[c] = stc_tanh(dh[c]); dy[i][c] = (1.f - u[c]) * cd[c] + u[c] * cand[c]; }
                 if (interior) {
-                    __builtin_nontemporal_store(cand, a.Y + slot_at(i, chunk));
+                    if (a.Y != nullptr) __builtin_nontemporal_store(cand, a.Y + slot_at(i, chunk));      // (Cand is optional: only a backward reads it)
                     __builtin_nontemporal_store(dy[i], a.Y2 + slot_at(i, chunk));
                 }
             }
@@ -300,7 +300,7 @@ extern "C" int stc_ring2_blend_f32(const int32_t* l2_rows, const int32_t* l1_row
                                    int32_t batch, int32_t C, int32_t h, void* stream) {
     if (int rc = check_ring2("stc_ring2_blend_f32", l2_rows, l1_rows, int_rows, t1, t2, n_patches, n_rows, batch, C, h)) return rc;
     if (batch == 0 || n_rows == 0) return STC_OK;
-    STC_REQUIRE(Bm && A && U && H && Cand && Hnew && SHnew, STC_EINVAL, "stc_ring2_blend_f32: null pointer");
+    STC_REQUIRE(Bm && A && U && H && Hnew && SHnew, STC_EINVAL, "stc_ring2_blend_f32: null pointer");      // (Cand may be null: not stored)
     for (const void* q : {(const void*)Bm, (const void*)A, (const void*)U, (const void*)H, (const void*)Cand, (const void*)Hnew, (const void*)SHnew})
         STC_REQUIRE(stc::aligned16(q), STC_EALIGN, "stc_ring2_blend_f32: planes must be 16-byte aligned");
     for (const float* out : {Cand, Hnew, SHnew})

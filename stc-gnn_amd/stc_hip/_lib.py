@@ -22,7 +22,7 @@ from .graph import is_full_pattern
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, 'libstc_hip.so')
 # Mirrors of include/stc_hip.h (#define STC_<name>; tests/test_abi.py compares each, and HipKernels.ACT_AMAX_SLOTS, with the header)
-ABI_VERSION = 33
+ABI_VERSION = 34
 FMT_BF16X3, FMT_F16X2 = 0, 1          # operand formats of the split-operand matrix-core kernels
 MAX_K = 4
 SPMM_SUM_MAX_ADD = 8
@@ -233,6 +233,10 @@ class HipKernels:
     patch_spmm = os.environ.get('STC_PATCH_SPMM', '1') != '0'
     #: ... for launches of at least this many (patch, sample) workgroups with a Y0 operand (three / six times as many without, see csr_spmm)
     patch_min_items = 1000
+    #: the forward entry points take ``None`` for planes only a backward reads (ABI v34): ``Rg`` of ``cell_gates_fwd_planar`` (with ``post=``) and
+    #: ``cell_gates_fwd_planar_k``, ``Cand`` of ``spmm_blend_fwd``, ``ring2_blend`` and ``cell_cand_fwd_planar_k`` -- what the forward-only route of
+    #: ``ops.stc_cell_graph`` asks before it passes one (the bf16 set has no such attribute: its planes are all required)
+    optional_gate_stores = True
 
     def __init__(self):
         self.lib = load_library()
@@ -487,13 +491,13 @@ class HipKernels:
 
     def ring2_blend(self, rowptr, colidx, val, ring2, Bm, A, U, H, Cand, Hnew, SHnew):
         """Cand = tanh(A + S.Bm), Hnew = (1 - U) H + U Cand and SHnew = S.Hnew in one launch (stc_ring2_blend_f32): ``spmm_blend_fwd`` without state
-        copies + the plain aggregation of the new state, which is summed out of LDS instead of being read back.  ``ring2``: the plan for S."""
+        copies + the plain aggregation of the new state, which is summed out of LDS instead of being read back.  ``ring2``: the plan for S.  ``Cand`` may be None (not stored)."""
         B, n, Cc, h = H.shape
-        for name, t in (('Bm', Bm), ('A', A), ('U', U), ('H', H), ('Cand', Cand), ('Hnew', Hnew), ('SHnew', SHnew)):
-            _tensor('ring2_blend.' + name, t, (B, n, Cc, h))
+        for name, t in (('Bm', Bm), ('A', A), ('U', U), ('H', H), ('Hnew', Hnew), ('SHnew', SHnew)) + ((('Cand', Cand),) if Cand is not None else ()):
+            _tensor('ring2_blend.' + name, t, (B, n, Cc, h))           # Cand None: not stored
         self._same_device(Bm, A, U, H, Cand, Hnew, SHnew)
         self._launch('stc_ring2_blend_f32', H, *self._ring2_ptrs('ring2_blend', ring2, H), n, _ptr(Bm), _ptr(A), _ptr(U), _ptr(H), _ptr(Cand), _ptr(Hnew), _ptr(SHnew),
-                     B, Cc, h, nbytes=colidx.numel() * 8 + 4 * (n + 1) + 4 * B * n * Cc * h * 7)
+                     B, Cc, h, nbytes=colidx.numel() * 8 + 4 * (n + 1) + 4 * B * n * Cc * h * (6 + (Cand is not None)))
 
     def ring2_chain(self, rowptr, colidx, val, ring2, X, X2, alpha1, add1, V, alpha2, add0, Z):
         """V = alpha1 S.(X [+ X2]) + sum(add1) and Z = alpha2 S.V + sum(scale * t for (t, scale) in add0) in one launch (stc_ring2_chain_f32): the
@@ -714,16 +718,18 @@ class HipKernels:
         return [_ptr(cp[0][0]), cp[0][1], cp[0][2], _ptr(side), side_cin, _ptr(cp[1][0]), cp[1][1], cp[1][2]]
 
     def _spmm_blend_checked(self, dt, rowptr, colidx, val, Bm, A, U, H, Cand, Hnew, n_copies=0):
-        """The checks of ``spmm_blend_fwd`` on planes of type ``dt``; returns (B, n, C, h, algorithmic bytes)."""
+        """The checks of ``spmm_blend_fwd`` on planes of type ``dt``; returns (B, n, C, h, algorithmic bytes).  ``Cand`` None (fp32 planes): not stored."""
         B, n, Cc, h = H.shape
-        for name, t in (('Bm', Bm), ('A', A), ('U', U), ('H', H), ('Cand', Cand), ('Hnew', Hnew)):
+        if Cand is None and dt != torch.float32:
+            raise StcError('spmm_blend (bf16): the Cand plane is required')
+        for name, t in (('Bm', Bm), ('A', A), ('U', U), ('H', H), ('Hnew', Hnew)) + ((('Cand', Cand),) if Cand is not None else ()):
             _tensor('spmm_blend.' + name, t, (B, n, Cc, h), dt)
         self._same_device(rowptr, colidx, val, Bm, A, U, H, Cand, Hnew)
-        return B, n, Cc, h, colidx.numel() * 8 + 4 * (n + 1) + dt.itemsize * B * n * Cc * h * (6 + n_copies)
+        return B, n, Cc, h, colidx.numel() * 8 + 4 * (n + 1) + dt.itemsize * B * n * Cc * h * (5 + (Cand is not None) + n_copies)
 
     def spmm_blend_fwd(self, rowptr, colidx, val, plan, Bm, A, U, H, Cand, Hnew, copies=(), side=None):
         """Y = A + S.Bm with the GRU blend in the epilogue (stc_spmm_blend_fwd_f32).  Bm/A/U/H/Cand/Hnew (B, n, C, h);
-        ``copies`` / ``side`` as in ``cell_blend_fwd`` (buffers (B*n, C, ld))."""
+        ``copies`` / ``side`` as in ``cell_blend_fwd`` (buffers (B*n, C, ld)).  ``Cand`` may be None (not stored)."""
         B, n, Cc, h, nbytes = self._spmm_blend_checked(torch.float32, rowptr, colidx, val, Bm, A, U, H, Cand, Hnew, len(copies))
         cp = self._state_copies('spmm_blend', copies, side, B * n, Cc, h, H)
         g = self._graph_ptrs(rowptr, colidx, val, plan, n)
@@ -792,13 +798,15 @@ class HipKernels:
     def _gates_fwd_planar_checked(self, dt, X, H, SX, SH, Tc, W, bias, U, Rg, RH, post):
         """The checks of ``cell_gates_fwd_planar`` on planes of type ``dt``; returns (R, C, h, cin, (Wc, bc, A, Bm) or four Nones, algorithmic bytes)."""
         R, Cc, h, cin = self._planes('planar', X, H, SX, SH, dt)
-        if RH is None and post is None:
-            raise StcError('planar gates: the R*H plane is optional only with the fused candidate projection (post=)')
+        if (RH is None or Rg is None) and post is None:
+            raise StcError('planar gates: the Rg and R*H planes are optional only with the fused candidate projection (post=)')
+        if Rg is None and dt != torch.float32:
+            raise StcError('planar gates (bf16): the Rg plane is required')
         _tensor('planar.Tc', Tc, (2, Cc, Cc))
         _tensor('planar.W', W, (4 * (cin + h), 2 * h))
         if bias is not None:
             _tensor('planar.bias', bias, (2 * h,))
-        for name, t in (('U', U), ('Rg', Rg)) + ((('RH', RH),) if RH is not None else ()):
+        for name, t in (('U', U),) + ((('Rg', Rg),) if Rg is not None else ()) + ((('RH', RH),) if RH is not None else ()):
             _tensor('planar.' + name, t, (R, Cc, h), dt)
         Wc = bc = A = Bm = None
         if post is not None:
@@ -809,13 +817,13 @@ class HipKernels:
             for name, t in (('A', A), ('Bm', Bm)):
                 _tensor('planar.' + name, t, (R, Cc, h), dt)
         self._same_device(X, H, SX, SH, Tc, W, bias, U, Rg, RH, Wc, bc, A, Bm)
-        # algorithmic bytes: X, SX (cin wide), H, SH in; U, Rg (+ RH, + A, Bm) out -- every plane once
-        return R, Cc, h, cin, (Wc, bc, A, Bm), dt.itemsize * R * Cc * (2 * cin + 2 * h + h * (2 + (RH is not None) + (2 if post is not None else 0)))
+        # algorithmic bytes: X, SX (cin wide), H, SH in; U (+ Rg, + RH, + A, Bm) out -- every plane once
+        return R, Cc, h, cin, (Wc, bc, A, Bm), dt.itemsize * R * Cc * (2 * cin + 2 * h + h * (1 + (Rg is not None) + (RH is not None) + (2 if post is not None else 0)))
 
     def cell_gates_fwd_planar(self, X, H, SX, SH, Tc, W, bias, U, Rg, RH, post=None, act_amax=None):
         """Gates convolution on planar inputs; writes U, Rg and the R*H plane (the candidate's input is (X, RH)).
         ``post`` = (Wc, bc, A, Bm): the same launch also writes the candidate's post-aggregation pair A, Bm; ``RH`` may then be
-        None (not written: ``cell_bwd_planar`` forms R*H itself).  ``act_amax`` (fp16 x 2 format): (4, 256) zero floats that receive the
+        None (not written: ``cell_bwd_planar`` forms R*H itself), and so may ``Rg`` (a forward that no backward follows).  ``act_amax`` (fp16 x 2 format): (4, 256) zero floats that receive the
         maxima of the four input planes -- what the backward launches scale their activation operands by (``act_amax_buffer``)."""
         R, Cc, h, cin, (Wc, bc, A, Bm), nbytes = self._gates_fwd_planar_checked(torch.float32, X, H, SX, SH, Tc, W, bias, U, Rg, RH, post)
         self._launch('stc_cell_gates_fwd_planar_f32', H, _ptr(X), _ptr(H), _ptr(SX), _ptr(SH), _ptr(Tc), _ptr(W), _ptr(bias),
@@ -1209,24 +1217,24 @@ class HipKernels:
         K, R, Cc, h, cin = self._planes_k('planar_k gates', Zx, Zh, Tc, W, 2 * Zh[0].shape[-1])
         if bias is not None:
             _tensor('planar_k.bias', bias, (2 * h,))
-        for name, t in (('U', U), ('Rg', Rg), ('RH', RH)):
+        for name, t in (('U', U), ('RH', RH)) + ((('Rg', Rg),) if Rg is not None else ()):      # Rg None: not stored
             _tensor('planar_k.' + name, t, (R, Cc, h))
         self._same_device(*Zx, *Zh, Tc, W, bias, U, Rg, RH)
         self._launch('stc_cell_gates_fwd_planar_k_f32', U, self._ptr_array(Zx), self._ptr_array(Zh), K, _ptr(Tc), _ptr(W), _ptr(bias),
                      _ptr(U), _ptr(Rg), _ptr(RH), self.operand_format, self._act_amax('planar_k', act_amax, 2 * K, U), R, Cc, cin + h, h,
-                     nbytes=4 * R * Cc * (K * (cin + h) + 3 * h))
+                     nbytes=4 * R * Cc * (K * (cin + h) + (2 + (Rg is not None)) * h))
 
     def cell_cand_fwd_planar_k(self, Zx, Zh, Tc, W, bias, U, H, Cand, Hnew, act_amax=None):
-        """Candidate convolution on [X | R*H] (Zh = the T_n(S) planes of R*H) + tanh + GRU blend: Cand, Hnew."""
+        """Candidate convolution on [X | R*H] (Zh = the T_n(S) planes of R*H) + tanh + GRU blend: Cand (None: not stored), Hnew."""
         K, R, Cc, h, cin = self._planes_k('planar_k cand', Zx, Zh, Tc, W, Zh[0].shape[-1])
         if bias is not None:
             _tensor('planar_k.bias', bias, (h,))
-        for name, t in (('U', U), ('H', H), ('Cand', Cand), ('Hnew', Hnew)):
+        for name, t in (('U', U), ('H', H), ('Hnew', Hnew)) + ((('Cand', Cand),) if Cand is not None else ()):
             _tensor('planar_k.' + name, t, (R, Cc, h))
         self._same_device(*Zx, *Zh, Tc, W, bias, U, H, Cand, Hnew)
         self._launch('stc_cell_cand_fwd_planar_k_f32', U, self._ptr_array(Zx), self._ptr_array(Zh), K, _ptr(Tc), _ptr(W), _ptr(bias),
                      _ptr(U), _ptr(H), _ptr(Cand), _ptr(Hnew), self.operand_format, self._act_amax('planar_k', act_amax, 2 * K, U), R, Cc, cin + h, h,
-                     nbytes=4 * R * Cc * (K * (cin + h) + 4 * h))
+                     nbytes=4 * R * Cc * (K * (cin + h) + (3 + (Cand is not None)) * h))
 
     def _grad_planes_k(self, what, dZx, dZh, K, R, Cc, h, cin):
         if len(dZh) != K or len(dZx) != K:

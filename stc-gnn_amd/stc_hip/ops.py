@@ -619,8 +619,9 @@ class _ForwardPass(_Pass):
     """... and, in the forward, the new states, the input rows of the interleaved cells and the aggregations of every source tensor (formed
     once for all the planar cells that consume it)."""
 
-    def __init__(self, k, op: SpatialOperand, Ks: int, Tc, fwd_val, schedule, ext, cin, forms, bf16: bool):
-        zmax_all = k.act_amax_buffer(ext[0], len(schedule), 2, 2 * Ks) if (not bf16 and any(f.planar for f in forms)) else None   # (one zero fill)
+    def __init__(self, k, op: SpatialOperand, Ks: int, Tc, fwd_val, schedule, ext, cin, forms, bf16: bool, forward_only: bool = False):
+        # (forward only: no backward will read the maxima -- no buffer, and the launches get no slots to fill)
+        zmax_all = k.act_amax_buffer(ext[0], len(schedule), 2, 2 * Ks) if (not forward_only and not bf16 and any(f.planar for f in forms)) else None   # (one zero fill)
         super().__init__(k, op, Ks, Tc, schedule, cin, forms, ext[0].shape[:3], bf16, zmax_all, (op.fwd_rowptr, op.fwd_colidx, fwd_val, op.fwd_plan))
         self.fwd_val, self.ext = fwd_val, ext
         self.state = [None] * len(schedule)                         # plain (B,N,C,h) new state of every cell
@@ -632,6 +633,8 @@ class _ForwardPass(_Pass):
                     self.consumers[src[1]].append((j, role))
         # two aggregations in one launch where the graph has a two-ring plan (stc_ring2_chain_f32 / stc_ring2_blend_f32; fp32 planes only)
         self.ring2 = _RING2_FWD and not bf16 and op.fwd_ring2 is not None and k.ring2_fits(self.B, self.N, self.C, self.h)
+        # forward only, on a kernel set that takes None for them: the planes only a backward reads (R, Cand, R*H at order 2) are not stored
+        self.lean = forward_only and bool(getattr(k, 'optional_gate_stores', False))
 
     def source(self, src):
         return self.ext[src[1]] if src[0] == 'ext' else self.state[src[1]]
@@ -708,7 +711,7 @@ class _ForwardPass(_Pass):
         """PLANAR_ONE_BWD and PLANAR: the candidate's projection rides in the gates launch; only PLANAR stores the R*H plane."""
         k, op, rows, (_, x, hs) = self.k, self.op, self.rows, self.schedule[j]
         Xp, SXp, SHp = self.source(x), self.aggregated(x), self.aggregated(hs)
-        RH = None if self.forms[j] is _Form.PLANAR_ONE_BWD else torch.empty_like(Hprev)
+        RH = None if (self.forms[j] is _Form.PLANAR_ONE_BWD or self.lean) else torch.empty_like(Hprev)
         A, Bm = torch.empty_like(Hprev), torch.empty_like(Hprev)
         k.cell_gates_fwd_planar(*rows((Xp, Hprev, SXp, SHp)), self.Tc, Wg, bg, *rows((U, Rg, RH)), post=(Wc, bc, *rows((A, Bm))), **self.act_slots(j))
         # the blend and the aggregation of the new state in one launch where the graph has a two-ring plan and some planar cell will
@@ -747,6 +750,48 @@ class _ForwardPass(_Pass):
         Zc = _spatial_slabs(CandIn, self.fwd_val, op, self.Ks)
         k.cell_blend_fwd(rows(Zc), Tc, Wc, bc, *rows((U, Hprev, Cand, Hnew)), copies=copies, side=side)
         return [*Zg, *Zc]
+
+    def cell(self, j, stack, out=None):
+        """Every launch of cell j, in its form; the new state goes to ``out`` (a slot of the output stack) or to a tensor of its own.  Returns
+        what the cell saves for backward: [H, U, R, Cand, *the form's planes]."""
+        Hprev = self.source(self.schedule[j][2])
+        copies, side, late_copies, late_rows = self.copy_plan(j)
+        form = self.forms[j]
+        U = torch.empty_like(Hprev)
+        Rg, Cand = (None, None) if (self.lean and form.planar) else (torch.empty_like(Hprev), torch.empty_like(Hprev))
+        Hnew = torch.empty_like(Hprev) if out is None else out
+        run = self.planar3 if form is _Form.PLANAR3 else self.planar if form.planar else self.rows_cell
+        more = run(j, *stack, Hprev, U, Rg, Cand, Hnew, copies, side)
+        self.finish(j, Hnew, late_copies, late_rows)
+        return [Hprev, U, Rg, Cand, *more]
+
+    # ---- forward only: the order the cells run in and what is dropped after each
+    def wavefront(self):
+        """The cells by level (longest path from the external tensors), schedule order inside a level: a topological order of the same graph in
+        which a state's consumers follow it closely -- the encoder's schedule is layer-major, so in ITS order every state of a layer lives until
+        the next layer has run (one state and one aggregation per observed step); by level, a constant number of them.  A cell's launches read
+        the same operands in either order: same bits."""
+        level = []
+        for _, x, hs in self.schedule:
+            level.append(1 + max([level[src[1]] for src in (x, hs) if src[0] == 'cell'], default=0))
+        return sorted(range(len(self.schedule)), key=lambda j: (level[j], j))
+
+    def last_uses(self, order):
+        """source -> the cell after whose launches nothing in ``order`` reads it any more."""
+        last = {}
+        for j in order:
+            last[self.schedule[j][1]] = last[self.schedule[j][2]] = j
+        return last
+
+    def release(self, j, last, keep):
+        """After cell j: its input rows, and every source it was the last consumer of -- the state (unless it is in ``keep``: the outputs live in
+        the output stack) and its aggregation or Chebyshev planes; its own state at once if nothing consumes it."""
+        self.XH.pop(j, None)
+        for src in set(self.schedule[j][1:]) | {('cell', j)}:
+            if last.get(src, j) == j:
+                self.agg.pop(src, None)
+                if src[0] == 'cell' and src[1] not in keep:
+                    self.state[src[1]] = None
 
 
 class _BackwardPass(_Pass):
@@ -981,6 +1026,41 @@ class _BackwardPass(_Pass):
         return dWg, dbg, dWc, dbc
 
 
+def _begin_forward(op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, tensors, forward_only: bool = False):
+    """What both routes of ``stc_cell_graph`` do before the first launch: kernel set, contiguous operands, one form per cell, the output stack.
+    Returns (pass, parameter sets, output stack, output cell -> slot)."""
+    k = kernels().for_graph(_amplification(op, Ks))              # (a heavy graph: the 24-bit operand format, _lib.HEAVY_ROW_SUM)
+    ext, stacks, Tc, fwd_val = _unpack(n_ext, Tc, fwd_val, tensors)
+    bf16 = ext[0].dtype == torch.bfloat16                       # bf16 state planes: the all-planar bf16 kernel set
+    if bf16:
+        k = k.bf16
+    h = 16
+    B, N, C = ext[0].shape[:3]
+    cin = [ext[x[1]].shape[-1] if x[0] == 'ext' else h for _, x, _ in schedule]
+    forms = _cell_forms(k, Ks, Tc.shape[0], C, h, cin, bf16)
+    if bf16 and not all(f.planar for f in forms):
+        raise ValueError('stc_cell_graph: bfloat16 states need an all-planar schedule (Ks = 2, inputs 16 or 1..4 columns wide)')
+    p = _ForwardPass(k, op, Ks, Tc, fwd_val, schedule, ext, cin, forms, bf16, forward_only)
+    out_stack = ext[0].new_empty(len(outputs), B, N, C, h)      # the requested states are produced in place, stacked
+    return p, stacks, out_stack, _out_slots(outputs)
+
+
+def _forward_only(op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, tensors):
+    """``_StcCellGraph.forward`` for a pass that no backward follows (evaluation, forecasting): the same launches per cell
+    (``_ForwardPass.cell``), but nothing is saved -- every state, aggregation, input row and temporary goes back to the allocator after its
+    last consumer has launched (``release``; the cells run by level, ``wavefront``), no activation maxima are collected, and on the fp32 kernel
+    set the planes only a backward reads are not written: R and Cand of the planar cells, and R*H at order 2 whichever backward the form has
+    (``_ForwardPass.lean``; stc_hip.h, ABI v34).  Interleaved cells, the bf16 set and kernel sets without ``optional_gate_stores`` get the
+    liveness only.  The states are bit for bit those of the autograd node."""
+    p, stacks, out_stack, out_slot = _begin_forward(op, Ks, schedule, outputs, n_ext, Tc, fwd_val, tensors, forward_only=True)
+    order = p.wavefront()
+    last = p.last_uses(order)
+    for j in order:
+        p.cell(j, stacks[schedule[j][0]], out_stack[out_slot[j]] if j in out_slot else None)
+        p.release(j, last, out_slot)
+    return out_stack
+
+
 class _StcCellGraph(Function):
     """Encoder + decoder (any DAG of STC_Cells whose inputs are other cells' states) as one autograd node.
 
@@ -1001,31 +1081,12 @@ class _StcCellGraph(Function):
 
     @staticmethod
     def forward(ctx, op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, *tensors):
-        k = kernels().for_graph(_amplification(op, Ks))              # (a heavy graph: the 24-bit operand format, _lib.HEAVY_ROW_SUM)
-        ext, stacks, Tc, fwd_val = _unpack(n_ext, Tc, fwd_val, tensors)
-        bf16 = ext[0].dtype == torch.bfloat16                       # bf16 state planes: the all-planar bf16 kernel set
-        if bf16:
-            k = k.bf16
-        h = 16
-        B, N, C = ext[0].shape[:3]
-        cin = [ext[x[1]].shape[-1] if x[0] == 'ext' else h for _, x, _ in schedule]
-        forms = _cell_forms(k, Ks, Tc.shape[0], C, h, cin, bf16)
-        if bf16 and not all(f.planar for f in forms):
-            raise ValueError('stc_cell_graph: bfloat16 states need an all-planar schedule (Ks = 2, inputs 16 or 1..4 columns wide)')
-        p = _ForwardPass(k, op, Ks, Tc, fwd_val, schedule, ext, cin, forms, bf16)
-        out_stack = ext[0].new_empty(len(outputs), B, N, C, h)      # the requested states are produced in place, stacked
-        out_slot = _out_slots(outputs)
+        p, stacks, out_stack, out_slot = _begin_forward(op, Ks, schedule, outputs, n_ext, Tc, fwd_val, tensors)
         saved = []
-        for j, (s_id, x, hs) in enumerate(schedule):
-            Hprev = p.source(hs)
-            copies, side, late_copies, late_rows = p.copy_plan(j)
-            U, Rg, Cand = torch.empty_like(Hprev), torch.empty_like(Hprev), torch.empty_like(Hprev)
-            Hnew = _alias(out_stack, out_slot[j]) if j in out_slot else torch.empty_like(Hprev)
-            run = p.planar3 if forms[j] is _Form.PLANAR3 else p.planar if forms[j].planar else p.rows_cell
-            saved += [Hprev, U, Rg, Cand, *run(j, *stacks[s_id], Hprev, U, Rg, Cand, Hnew, copies, side)]
-            p.finish(j, Hnew, late_copies, late_rows)
-        ctx.save_for_backward(Tc, *[t for st in stacks for t in st], *saved)
-        ctx.meta = (op, Ks, schedule, tuple(outputs), cin, len(stacks), (B, N, C), forms)
+        for j, (s_id, _, _) in enumerate(schedule):
+            saved += p.cell(j, stacks[s_id], _alias(out_stack, out_slot[j]) if j in out_slot else None)
+        ctx.save_for_backward(p.Tc, *[t for st in stacks for t in st], *saved)
+        ctx.meta = (op, Ks, schedule, tuple(outputs), p.cin, len(stacks), (p.B, p.N, p.C), p.forms)
         ctx.zmax_all = p.zmax_all
         _guard(ctx, out_stack)
         return out_stack
@@ -1077,6 +1138,9 @@ def stc_cell_graph(op: SpatialOperand, Tc, Ks: int, schedule, outputs, ext, stac
                                         ext[0].dtype):
         return stc_small_graph(k, op, Tc, Ks, schedule, outputs, ext, stacks)
     flat = [p for st in stacks for p in st]
+    if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (Tc, op.fwd_val, *ext, *flat)):
+        with torch.no_grad():                                        # no backward will follow: nothing saved, nothing stored for one (``_forward_only``)
+            return _forward_only(op, Ks, list(schedule), list(outputs), len(ext), Tc, op.fwd_val, (*ext, *flat))
     return _StcCellGraph.apply(op, Ks, list(schedule), list(outputs), len(ext), Tc, op.fwd_val, *ext, *flat)
 
 

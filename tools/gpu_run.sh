@@ -4,6 +4,7 @@
 #   tests:<expr>     pytest -k <expr>
 #   bench            default bench line (driver form, 20 steps) -> gpurun_out/bench_default.json
 #   quick            2-step bench without the CPU baseline, per-kernel table printed
+#   infer            forward-only (no_grad) step of the metric configuration (tools/bench_infer.py): its one JSON line on stdout
 #   presets          --preset cfg2 (K = 2, 3) / cfg4 / cfg5 / sf / sf-learned lines -> gpurun_out/preset_*.json
 #   stats            rocprofv3 --kernel-trace --stats of the bench command -> gpurun_out/kernel_stats.csv
 #   traffic          FETCH_SIZE / WRITE_SIZE PMC passes (tools/gpu_pmc_bench.sh) -> gpurun_out/spmm_traffic_bench.json
@@ -28,6 +29,7 @@ for k, v in d['kernels'].items():
     print(f"   {k:32s} {int(v['launches']):4d} {v['ms_per_step']:8.2f} ms  {1e3 * v['ms_per_step'] * d['steps'] / v['launches']:8.1f} us/launch  {v.get('GBps', 0):7.0f} GB/s")
 PY
            ;;
+    infer) timeout -k 10 600 python tools/bench_infer.py --steps ${INFER_STEPS:-10} --warmup 3; rc=$? ;;
     presets) rc=0
            for p in "cfg2 --order 2" "cfg2 --order 3" "cfg4" "cfg5" "sf" "sf-learned"; do
              n=$(echo $p | tr -d ' -'); timeout -k 10 900 python bench.py --preset $p --steps 5 --warmup 2 > gpurun_out/preset_$n.json 2> gpurun_out/preset_$n.err || rc=1
