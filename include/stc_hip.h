@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define STC_ABI_VERSION 34
+#define STC_ABI_VERSION 35
 #define STC_MAX_K 4          /* highest Chebyshev order (Ks, Kc) the node kernels accept */
 
 /* Operand formats of the split-operand matrix-core kernels (C = 32 / 64, hidden 16).  Every fp32 operand is split into low-precision
@@ -589,8 +589,16 @@ int stc_head_bwd_f32(const float* H, const float* w, const float* y, const float
  * third spatial slab is Z_2 = T_2(S) Z with T_2(S) = 2 S^2 - I formed on the MATRIX side, as the reference's cheby_poly forms it (STC_GNN.py:24-29):
  * (rowptr2, colidx2, val2, nnz2) is the CSR of T_2 in the orientation of the launch -- forward: 2 (Gs^T)^2 - I, backward: 2 Gs^2 - I -- built by the
  * caller (stc_hip/graph.py CsrGraph.second_order; 25 entries per row on an 8-neighbour grid).  Z_2 aggregates the same input rows as Z_1, so the
- * phases and the split forms are those of order 2.  Zg2 (like Zg) and Zc2 (like Zc) hold T_2.[H | Xt | 0] and T_2.(R*H) for the backward.  Fixed CSR
- * graphs only (graph_is_dense = 0, no learned-graph operands), nothing staged in LDS; order 2: pass NULL / 0 for the new pointers. */
+ * phases and the split forms are those of order 2.  Zg2 (like Zg) and Zc2 (like Zc) hold T_2.[H | Xt | 0] and T_2.(R*H) for the backward.  Nothing
+ * is staged in LDS; order 2: pass NULL / 0 for the new pointers.  A fixed CSR graph leaves no learned-graph operands.
+ * Order 3 with a DENSE learned graph (ABI v35; graph_is_dense != 0): val2 is T_2 as a dense row-major n x n matrix in the launch's orientation
+ * (nnz2 = n*n, else STC_EINVAL; rowptr2 / colidx2: the full pattern, not read), formed by the caller -- its gradient chain to Gs stays on the
+ * caller's side.  Split form only: phase = 0 returns STC_EUNSUPPORTED (two n x n matrices and the staged planes exceed a workgroup's LDS at
+ * the SF shape); splits may be 1.  Forward: Zg / Zg2 and Zc / Zc2 come from ONE pass over the source rows with two matrix operand streams
+ * (phases 5, 6 as they are); backward: dZ_0 + S^T dZ_1 + T_2^T dZ_2 likewise in phases 7 and 4 (sequence 1, 7, 4).  Learned-graph operands
+ * as at order 2, plus (new trailing pointers, NULL = not wanted, order 3 with a dense graph only) Z2c (forward, like Zg): the candidate's
+ * third slab [T_2 x (R*H) | T_2 x Xt | 0] -- the gates' third slab is Zg2 itself -- and dZ2c / dZ2g (backward, like Zg): the gradients of
+ * the candidate's / gates' third slab, so that dT_2 = sum dZ2 x Z0 is one more stc_graph_grad_f32 product and dT_c runs over three slabs. */
 int stc_cell_small_supported(int32_t Ks, int32_t Kc, int32_t C, int32_t cin, int32_t h);
 size_t stc_cell_small_workspace_bytes(int32_t n_nodes, int32_t C, int32_t cin, int32_t batch, int32_t Ks);
 int stc_cell_small_param_rows(void);
@@ -599,7 +607,7 @@ int stc_cell_small_fwd_f32(const int32_t* rowptr, const int32_t* colidx, const f
                            const float* X, int32_t cin, const float* H, const float* Tc, int32_t Ks, int32_t Kc,
                            const float* Wg, const float* bg, const float* Wc, const float* bc,
                            float* U, float* R, float* Cand, float* Hnew, float* RH, float* Zg, float* Zc, float* Zg2, float* Zc2, float* Z0,
-                           float* Z0c, float* Z1c, int32_t phase, int32_t splits, int32_t batch, int32_t C, void* stream);
+                           float* Z0c, float* Z1c, float* Z2c, int32_t phase, int32_t splits, int32_t batch, int32_t C, void* stream);
 int stc_cell_small_bwd_f32(const int32_t* rowptr, const int32_t* colidx, const float* val, int32_t n_nodes, int32_t nnz,
                            int32_t graph_is_dense, const int32_t* rowptr2, const int32_t* colidx2, const float* val2, int32_t nnz2,
                            const float* X, int32_t cin, const float* H, const float* Tc, int32_t Ks, int32_t Kc,
@@ -607,7 +615,7 @@ int stc_cell_small_bwd_f32(const int32_t* rowptr, const int32_t* colidx, const f
                            const float* RH, const float* Zg, const float* Zc, const float* Zg2, const float* Zc2, const float* dHnew,
                            float* dX, int32_t accumulate_x, float* dH, int32_t accumulate_h,
                            float* dparams, int64_t params_ld, int32_t has_bg, int32_t has_bc,
-                           float* dZ1c, float* dZ1g, float* dYg, float* dYc,
+                           float* dZ1c, float* dZ1g, float* dYg, float* dYc, float* dZ2c, float* dZ2g,
                            void* workspace, size_t workspace_bytes, int32_t phase, int32_t splits, int32_t batch, int32_t C, void* stream);
 
 /* Gradients of learned graphs from the planes the cell launches left (ABI v20): sums over every selected cell step and sample, g = sel * batch

@@ -43,8 +43,14 @@ constexpr int SC_H = 16, SC_MAXC = 16;
 // row on an 8-neighbour grid), handed over as a SECOND CSR graph.  Z_2 is then an aggregation of the same input rows as Z_1, not of Z_1's: no
 // phase is added, no dependency crosses workgroups that order 2 does not have, and the split forms (5, 6 / 1, 7, 4) are the same launches.
 // What changes: three slabs per convolution (nine W blocks, two category mixes), workgroups of 8 waves forward (the nine W blocks are 72
-// registers per lane: 256 instead of 128 available) and 12 waves backward (six per row tile: slab x role), nothing staged in LDS (MODE 0),
-// fixed CSR graphs only (a learned dense Gs at order 3 stays on the general path).
+// registers per lane: 256 instead of 128 available) and 12 waves backward (six per row tile: slab x role), nothing staged in LDS (MODE 0).
+// A learned DENSE Gs at order 3 (MODE 3 with KS = 3): the host forms T_2 as a dense row-major N x N matrix too (its gradient chain back to Gs
+// stays outside: stc_hip/small.py) and hands it over as `val2`; split form only (phases 5, 6 / 1, 7, 4 -- two N x N matrices plus the staged
+// planes do not fit the LDS at the SF shape, so phase 0 is refused).  The own-tile product then runs TWO S operand streams over one pass of the
+// source rows (aggregate_dense_own2): Z_1 and Z_2 from the same A operands in the forward, S^T dZ_1 + T_2^T dZ_2 into one result in the
+// backward.  The workgroup shapes stay 8 / 12 waves and a workgroup's own-tile range is unchanged: the second stream costs four registers
+// of S values and two accumulators per lane (forward 172 / 149 registers wide / narrow of the 256 that eight waves allow, backward 157 of the
+// 168 that twelve allow; no scratch; LDS: none forward, the waves' dV tiles -- 76 032 bytes -- backward, as for CSR graphs).
 template <int KS> struct WgShape {                                     // workgroup shapes per order
 #ifndef STC_SC_FWD_THREADS             // (probe builds: tools/gpu_ab.sh sf)
 #define STC_SC_FWD_THREADS SF_THREADS
@@ -295,6 +301,102 @@ __device__ __forceinline__ void aggregate_dense_own(const float* __restrict__ S,
     }
 }
 
+// ... with TWO dense matrices (order 3 with a learned graph: S and T_2(S) = 2 S^2 - I, both row-major N x N), in ONE pass over the source rows:
+//   forward  (SUM = false): out[node] = S.src and out2[node] = S2.src -- one source, read once; two S operand streams, two results
+//            (store / store2, both added to base(row, quad));
+//   backward (SUM = true):  out[node] = base + S.src + S2.src2 -- two sources (the slabs dZ_1, dZ_2), one result (store).
+// Either way a lane carries four accumulators -- four independent chains on the matrix pipe -- and the same requests one block ahead.
+template <int THREADS, int QUADS, bool SUM, class Base, class Store, class Store2>
+__device__ __forceinline__ void aggregate_dense_own2(const float* __restrict__ S, const float* __restrict__ S2, int N, int C, const float* src,
+                                                     const float* src2, int stride, int ncols, int n_lo, int n_hi, int row_lo, int row_hi, Base base,
+                                                     Store store, Store2 store2) {
+    constexpr int CT = (QUADS + 3) / 4, NX = SUM ? 2 : 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, kq = lane >> 4;
+    const int rtiles = (N + 15) >> 4, per_rt = C * CT, pairs = (per_rt + 1) >> 1;
+    const int rt_lo = n_lo >> 4, rt_hi = (n_hi + 15) >> 4, items = (rt_hi - rt_lo) * pairs;
+    const bool vec = (N & 3) == 0;
+    for (int item = wave; item < items; item += THREADS / 64) {
+        const int rt = rt_lo + item / pairs, t0 = 2 * (item - (rt - rt_lo) * pairs), t1 = min(t0 + 1, per_rt - 1);
+        const bool two = t0 + 1 < per_rt;
+        const int c0 = t0 / CT, lb0 = t0 - c0 * CT, c1 = t1 / CT, lb1 = t1 - c1 * CT;
+        const int node = 16 * rt + j;
+        const bool node_ok = node < N;
+        const unsigned srow = (unsigned)(node_ok ? node : 0) * N;
+        const int col0 = 16 * lb0 + j, col1 = 16 * lb1 + j;
+        const bool ok0 = col0 < ncols, ok1 = col1 < ncols;
+        const unsigned a0 = (unsigned)c0 * stride + (ok0 ? col0 : 0), a1 = (unsigned)c1 * stride + (ok1 ? col1 : 0);
+        auto load_s = [&](const float* __restrict__ Sm, int kb) {  // Sm[node][16 kb + 4 kq .. + 3], unmasked (clamped); masked where consumed
+            const int k0 = 16 * kb + 4 * kq;
+            if (vec) return ld4(Sm + (k0 < N ? srow + k0 : srow));
+            f32x4 v;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = Sm[srow + min(k0 + i, N - 1)];
+            return v;
+        };
+        auto load_a = [&](int kb, float (&x)[NX][2][4]) {          // the lane's source values of four steps (clamped rows; masked where consumed)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const unsigned mrow = (unsigned)(min(16 * kb + 4 * kq + i, N - 1) * C) * stride;
+                x[0][0][i] = src[mrow + a0];
+                x[0][1][i] = src[mrow + a1];
+                if constexpr (SUM) {
+                    x[1][0][i] = src2[mrow + a0];
+                    x[1][1][i] = src2[mrow + a1];
+                }
+            }
+        };
+        f32x4 acc[2][2] = {{zero4(), zero4()}, {zero4(), zero4()}};         // [matrix][column tile of the pair]
+        f32x4 bn = load_s(S, 0), bn2 = load_s(S2, 0);
+        float xn[NX][2][4];
+        load_a(0, xn);
+        for (int kb = 0; kb < rtiles; ++kb) {
+            const f32x4 b = bn, b2 = bn2;
+            float x[NX][2][4];
+#pragma unroll
+            for (int s = 0; s < NX; ++s)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { x[s][0][i] = xn[s][0][i]; x[s][1][i] = xn[s][1][i]; }
+            if (kb + 1 < rtiles) {                                       // the next block's operands are requested before this block's products
+                bn = load_s(S, kb + 1);
+                bn2 = load_s(S2, kb + 1);
+                load_a(kb + 1, xn);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int m = 16 * kb + 4 * kq + i;
+                const bool live = node_ok && m < N;
+                const float bv = live ? b[i] : 0.f, bv2 = live ? b2[i] : 0.f;
+                acc[0][0] = mfma4(ok0 ? x[0][0][i] : 0.f, bv, acc[0][0]);
+                acc[0][1] = mfma4(ok1 ? x[0][1][i] : 0.f, bv, acc[0][1]);
+                acc[1][0] = mfma4(ok0 ? x[NX - 1][0][i] : 0.f, bv2, acc[1][0]);
+                acc[1][1] = mfma4(ok1 ? x[NX - 1][1][i] : 0.f, bv2, acc[1][1]);
+            }
+        }
+        if (node_ok) {
+            const int q[2] = {4 * lb0 + kq, 4 * lb1 + kq}, r[2] = {node * C + c0, node * C + c1};
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                if ((p == 1 && !two) || q[p] >= QUADS || r[p] < row_lo || r[p] >= row_hi) continue;
+                f32x4 s = base(r[p], q[p]);
+                if constexpr (SUM) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) s[i] += acc[0][p][i] + acc[1][p][i];
+                    store(r[p], q[p], s);
+                } else {
+                    f32x4 s2 = s;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        s[i] += acc[0][p][i];
+                        s2[i] += acc[1][p][i];
+                    }
+                    store(r[p], q[p], s);
+                    store2(r[p], q[p], s2);
+                }
+            }
+        }
+    }
+}
+
 template <int THREADS>
 __device__ __forceinline__ void stage_graph(const SmallGraph& g, int N, int* gp, int* gc, float* gv) {
     for (int i = threadIdx.x; i <= N; i += THREADS) gp[i] = g.rowptr[i];
@@ -439,19 +541,21 @@ struct SmallFwd {
                                                  // rows split over gridDim.y workgroups -- the launch boundary is the barrier between phases
     SmallGraph g2;                               // order 3: CSR of T_2(S)^T = 2 (S^T)^2 - I in the forward's orientation
     float *Zg2, *Zc2;                            // order 3: T_2 . [H | X] (rows of LP floats) and T_2 . (R*H) (rows of 16)
+    float *Z2c;                                  // optional (order 3, learned graphs): the candidate's third slab [T_2.(R*H) | T_2.X | 0]
 };
 
 template <int KC>
 __host__ __device__ constexpr int fwd_lds_fixed() { return 0; }                                         // floats of LDS every launch needs
 
 // MODE 0: graph and planes read from global memory; 1: CSR graph + planes staged in LDS; 2: dense graph (matrix-product aggregation), planes staged;
-// 3: dense graph in the split form (phase != 0): nothing staged, a workgroup aggregates the node tiles that cover its own rows (aggregate_dense_own)
+// 3: dense graph in the split form (phase != 0): nothing staged, a workgroup aggregates the node tiles that cover its own rows (aggregate_dense_own;
+//    order 3: both matrices in one pass, aggregate_dense_own2)
 template <int KS, int KC, int XQ, int MODE>
 __global__ __launch_bounds__(WgShape<KS>::FWD_THREADS) void small_fwd_kernel(SmallFwd a) {
     constexpr int LP = 16 + 4 * XQ, XS = XQ == 4 ? 4 : XQ, SP = plane_stride(XQ);
     constexpr bool STAGED = MODE == 1 || MODE == 2, DENSE = MODE >= 2;
     constexpr int SF_THREADS = WgShape<KS>::FWD_THREADS, SF_WAVES = WgShape<KS>::FWD_WAVES;      // (shadow the order-2 constants of the file)
-    static_assert(KS == 2 || (KS == 3 && KC == 3 && MODE == 0), "order 3: Ks = Kc = 3, CSR graph, nothing staged");
+    static_assert(KS == 2 || (KS == 3 && KC == 3 && (MODE == 0 || MODE == 3)), "order 3: Ks = Kc = 3, nothing staged (CSR graphs, or dense in the split form)");
     extern __shared__ __align__(16) float lds[];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, j = lane & 15, kq = lane >> 4;
     const int C = a.C, N = a.N, NC = N * C, cin = a.cin;
@@ -539,6 +643,12 @@ __global__ __launch_bounds__(WgShape<KS>::FWD_THREADS) void small_fwd_kernel(Sma
         auto put = [&](int row, int q, f32x4 s) { st4(Zgb + (unsigned)row * LP + 4 * q, s); };
         if (DENSE && STAGED) {
             aggregate_dense<SF_THREADS, LP / 4>(a.g.val, N, C, P, SP, 0, 1, none, put);
+        } else if (DENSE && KS == 3) {                       // Zg and Zg2 = T_2(S) . [H | X] from one pass over the source rows (g2.val: T_2, dense)
+            aggregate_dense_own2<SF_THREADS, 4, false>(a.g.val, a.g2.val, N, C, Hb, Hb, SC_H, SC_H, n_lo, n_hi, row_lo, row_hi, none, put,
+                                                       [&](int row, int q, f32x4 s) { st4(Zg2b + (unsigned)row * LP + 4 * q, s); });
+            aggregate_dense_own2<SF_THREADS, XQ, false>(a.g.val, a.g2.val, N, C, Xb, Xb, cin, cin, n_lo, n_hi, row_lo, row_hi, none,
+                                                        [&](int row, int q, f32x4 s) { st4(Zgb + (unsigned)row * LP + SC_H + 4 * q, s); },
+                                                        [&](int row, int q, f32x4 s) { st4(Zg2b + (unsigned)row * LP + SC_H + 4 * q, s); });
         } else if (DENSE) {                                  // the H block and the X block of the slab from their own planes
             aggregate_dense_own<SF_THREADS, 4>(a.g.val, N, C, Hb, SC_H, SC_H, n_lo, n_hi, row_lo, row_hi, none, put);
             aggregate_dense_own<SF_THREADS, XQ>(a.g.val, N, C, Xb, cin, cin, n_lo, n_hi, row_lo, row_hi, none,
@@ -594,6 +704,9 @@ __global__ __launch_bounds__(WgShape<KS>::FWD_THREADS) void small_fwd_kernel(Sma
         auto put = [&](int row, int q, f32x4 s) { st4(Zcb + (unsigned)row * SC_H + 4 * q, s); };
         if (DENSE && STAGED)
             aggregate_dense<SF_THREADS, 4>(a.g.val, N, C, Q, SQ, 0, 1, none, put);
+        else if (DENSE && KS == 3)                           // Zc and Zc2 = T_2(S) . (R*H), one pass
+            aggregate_dense_own2<SF_THREADS, 4, false>(a.g.val, a.g2.val, N, C, RHb, RHb, SC_H, SC_H, n_lo, n_hi, row_lo, row_hi, none, put,
+                                                       [&](int row, int q, f32x4 s) { st4(Zc2b + (unsigned)row * SC_H + 4 * q, s); });
         else if (DENSE)
             aggregate_dense_own<SF_THREADS, 4>(a.g.val, N, C, RHb, SC_H, SC_H, n_lo, n_hi, row_lo, row_hi, none, put);
         else {
@@ -615,6 +728,15 @@ __global__ __launch_bounds__(WgShape<KS>::FWD_THREADS) void small_fwd_kernel(Sma
             const int row = row_lo + item / (LP / 4), q = item - (row - row_lo) * (LP / 4);
             st4(Z0cb + (unsigned)row * LP + 4 * q, q < 4 ? ld4(RHb + (unsigned)row * SC_H + 4 * q) : ld4(Z0b + (unsigned)row * LP + 4 * q));
             st4(Z1cb + (unsigned)row * LP + 4 * q, q < 4 ? ld4(Zcb + (unsigned)row * SC_H + 4 * q) : ld4(Zgb + (unsigned)row * LP + 4 * q));
+        }
+    }
+    if constexpr (KS == 3) {
+        if (a.Z2c != nullptr && runs(4)) {                   // (Zc2 and Zg2 of the own rows are complete, like Zc and Zg)
+            float* Z2cb = a.Z2c + r0 * LP;
+            for (int item = t; item < (row_hi - row_lo) * (LP / 4); item += SF_THREADS) {
+                const int row = row_lo + item / (LP / 4), q = item - (row - row_lo) * (LP / 4);
+                st4(Z2cb + (unsigned)row * LP + 4 * q, q < 4 ? ld4(Zc2b + (unsigned)row * SC_H + 4 * q) : ld4(Zg2b + (unsigned)row * LP + 4 * q));
+            }
         }
     }
 
@@ -862,6 +984,7 @@ struct SmallBwd {
     long long P;                                 // floats per row of dP: [dWg | dbg (32) | dWc | dbc (16)]; SB_WAVES / 4 rows per sample
     SmallGraph g2;                               // order 3: CSR of T_2(S) = 2 S^2 - I (the transpose of the forward's second graph)
     const float *Zg2, *Zc2;                      // order 3: the forward's third slabs
+    float *dZ2c, *dZ2g;                          // optional (order 3, learned graphs): gradients of the third slabs, candidate / gates convolution
 };
 
 struct Raw3 {
@@ -880,7 +1003,7 @@ __global__ __launch_bounds__(WgShape<KS>::BWD_THREADS) void small_bwd_kernel(Sma
     constexpr int LP = 16 + 4 * XQ;
     constexpr bool STAGED = MODE == 1 || MODE == 2, DENSE = MODE >= 2;
     constexpr int SB_THREADS = WgShape<KS>::BWD_THREADS;
-    static_assert(KS == 2 || (KS == 3 && KC == 3 && MODE == 0), "order 3: Ks = Kc = 3, CSR graph, nothing staged");
+    static_assert(KS == 2 || (KS == 3 && KC == 3 && (MODE == 0 || MODE == 3)), "order 3: Ks = Kc = 3, nothing staged (CSR graphs, or dense in the split form)");
     extern __shared__ __align__(16) float lds[];
     const int t = threadIdx.x, wave = t >> 6;
     const int C = a.C, N = a.N, NC = N * C, cin = a.cin, L = cin + SC_H;
@@ -941,7 +1064,7 @@ __global__ __launch_bounds__(WgShape<KS>::BWD_THREADS) void small_bwd_kernel(Sma
     // 1: candidate convolution
     if (runs(1)) conv_bwd_phase<KC, XQ, 1, Raw3>(ks == 0 ? Slab{RHb, SC_H, Xb, cin} : (ks == 1 ? Slab{Zcb, SC_H, Zgb + SC_H, LP} : Slab{Zc2b, SC_H, Zg2b + SC_H, LP}),
         a.Wc, ks, role, M, dv, ks == 0 ? dZ0 : (ks == 1 ? dZ1 : dZ2),
-        ks == 1 && a.dZ1c ? a.dZ1c + r0 * LP : nullptr, dWc,
+        ks == 1 && a.dZ1c ? a.dZ1c + r0 * LP : (KS == 3 && ks == 2 && a.dZ2c ? a.dZ2c + r0 * LP : nullptr), dWc,
         a.has_bc ? dbc : nullptr, a.rpt, min(t_hi, SC_MAX_TILES), tile0, tstep, NC, cin,
         [&](int grow, int col) {
             const size_t e = (unsigned)grow * SC_H + col;
@@ -994,7 +1117,10 @@ __global__ __launch_bounds__(WgShape<KS>::BWD_THREADS) void small_bwd_kernel(Sma
                 }
             }
         };
-        if (DENSE && !STAGED)
+        if (DENSE && KS == 3)                        // dZ_0 + S^T dZ_1 + T_2(S)^T dZ_2 as one pass of two matrix products (g2.val: T_2(S), dense)
+            aggregate_dense_own2<SB_THREADS, LP / 4, true>(a.g.val, a.g2.val, N, C, dZ1, dZ2, LP, LP, n_lo, n_hi, row_lo, row_hi, from_dz0, gate_bwd,
+                                                           gate_bwd);
+        else if (DENSE && !STAGED)
             aggregate_dense_own<SB_THREADS, LP / 4>(a.g.val, N, C, dZ1, LP, LP, n_lo, n_hi, row_lo, row_hi, from_dz0, gate_bwd);
         else if (DENSE)
             aggregate_dense<SB_THREADS, LP / 4>(a.g.val, N, C, dZ1, LP, split, splits, from_dz0, gate_bwd);
@@ -1010,7 +1136,7 @@ __global__ __launch_bounds__(WgShape<KS>::BWD_THREADS) void small_bwd_kernel(Sma
     // 3: gates convolution
     if (runs(3)) conv_bwd_phase<KC, XQ, 2, Raw2>(ks == 0 ? Slab{Hb, SC_H, Xb, cin} : (ks == 1 ? Slab{Zgb, LP, Zgb + SC_H, LP} : Slab{Zg2b, LP, Zg2b + SC_H, LP}),
         a.Wg, ks, role, M, dv, ks == 0 ? dZ0 : (ks == 1 ? dZ1s : dZ2s),
-        ks == 1 && a.dZ1g ? a.dZ1g + r0 * LP : nullptr, dWg,
+        ks == 1 && a.dZ1g ? a.dZ1g + r0 * LP : (KS == 3 && ks == 2 && a.dZ2g ? a.dZ2g + r0 * LP : nullptr), dWg,
         a.has_bg ? dbg : nullptr, a.rpt, min(t_hi, SC_MAX_TILES), tile0, tstep, NC, cin,
         [&](int grow, int col) { return Raw2{dYg[(unsigned)grow * 32 + col], dYg[(unsigned)grow * 32 + 16 + col]}; },
         [](const Raw2& w, int ot) { return ot == 0 ? w.a : w.b; });
@@ -1039,7 +1165,9 @@ __global__ __launch_bounds__(WgShape<KS>::BWD_THREADS) void small_bwd_kernel(Sma
                     }
                 }
             };
-        if (DENSE && !STAGED)
+        if (DENSE && KS == 3)
+            aggregate_dense_own2<SB_THREADS, LP / 4, true>(a.g.val, a.g2.val, N, C, dZ1s, dZ2s, LP, LP, n_lo, n_hi, row_lo, row_hi, from_dz0, add_in, add_in);
+        else if (DENSE && !STAGED)
             aggregate_dense_own<SB_THREADS, LP / 4>(a.g.val, N, C, dZ1s, LP, LP, n_lo, n_hi, row_lo, row_hi, from_dz0, add_in);
         else if (DENSE)
             aggregate_dense<SB_THREADS, LP / 4>(a.g.val, N, C, dZ1s, LP, split, splits, from_dz0, add_in);
@@ -1071,7 +1199,7 @@ hipError_t allow_lds_once(K kern, size_t bytes, Grants& grants) {
     return e;
 }
 Grants g_granted[2][2][4];                       // [direction][wide input][mode]
-Grants g_granted3[2];                            // order 3, backward: [wide input]
+Grants g_granted3[2][2];                         // order 3, backward: [wide input][dense graph]
 
 }  // namespace
 
@@ -1093,15 +1221,21 @@ extern "C" size_t stc_cell_small_workspace_bytes(int32_t n_nodes, int32_t C, int
     STC_REQUIRE((long long)n_nodes * C < 65536 && (long long)n_nodes * C * batch < (1ll << 26), STC_ELIMIT,                             \
                 name ": %lld rows per sample, %d samples: not a small graph", (long long)n_nodes * C, batch);                           \
     if (n_nodes == 0 || batch == 0) return STC_OK;                                                                                       \
-    STC_REQUIRE(Ks == 2 || (rowptr2 && (nnz2 == 0 || (colidx2 && val2)) && nnz2 >= 0 && !graph_is_dense), STC_EINVAL,                    \
-                name ": order 3 takes the CSR of T_2(S) = 2 S^2 - I as a second graph (and no dense graph)");
+    STC_REQUIRE(Ks == 2 || (rowptr2 && (nnz2 == 0 || (colidx2 && val2)) && nnz2 >= 0), STC_EINVAL,                                       \
+                name ": order 3 takes T_2(S) = 2 S^2 - I as a second graph");                                                            \
+    STC_REQUIRE(Ks == 2 || !graph_is_dense || (nnz == (long long)n_nodes * n_nodes && nnz2 == (long long)n_nodes * n_nodes), STC_EINVAL,  \
+                name ": order 3 with a dense graph takes both S and T_2(S) as row-major %d x %d matrices (nnz=%d nnz2=%d)", n_nodes,     \
+                n_nodes, nnz, nnz2);                                                                                                     \
+    STC_REQUIRE(Ks == 2 || !graph_is_dense || phase != 0, STC_EUNSUPPORTED,                                                              \
+                name ": order 3 with a dense graph runs in the split form only (phase != 0; splits may be 1): two dense matrices and "   \
+                     "the staged planes do not fit one workgroup's LDS");
 
 extern "C" int stc_cell_small_fwd_f32(const int32_t* rowptr, const int32_t* colidx, const float* val, int32_t n_nodes, int32_t nnz,
                                       int32_t graph_is_dense, const int32_t* rowptr2, const int32_t* colidx2, const float* val2, int32_t nnz2,
                                       const float* X, int32_t cin, const float* H, const float* Tc, int32_t Ks, int32_t Kc, const float* Wg,
                                       const float* bg, const float* Wc, const float* bc, float* U, float* R, float* Cand, float* Hnew, float* RH,
-                                      float* Zg, float* Zc, float* Zg2, float* Zc2, float* Z0, float* Z0c, float* Z1c, int32_t phase, int32_t splits,
-                                      int32_t batch, int32_t C, void* stream) {
+                                      float* Zg, float* Zc, float* Zg2, float* Zc2, float* Z0, float* Z0c, float* Z1c, float* Z2c, int32_t phase,
+                                      int32_t splits, int32_t batch, int32_t C, void* stream) {
     SC_COMMON_CHECKS("stc_cell_small_fwd_f32")
     STC_REQUIRE(rowptr && (nnz == 0 || (colidx && val)) && X && H && Tc && Wg && Wc && U && R && Cand && Hnew && RH && Zg && Zc, STC_EINVAL,
                 "stc_cell_small_fwd_f32: null operand");
@@ -1116,11 +1250,14 @@ extern "C" int stc_cell_small_fwd_f32(const int32_t* rowptr, const int32_t* coli
     STC_REQUIRE((Z0c == nullptr) == (Z1c == nullptr) && (Z0c == nullptr || Z0 != nullptr) && stc::aligned16(Z0c) && stc::aligned16(Z1c), STC_EINVAL,
                 "stc_cell_small_fwd_f32: Z0c and Z1c come together, with Z0, 16-byte aligned");
     SmallFwd a{{rowptr, colidx, val, nnz}, X, H, Tc, Wg, bg, Wc, bc, U, R, Cand, Hnew, RH, Zg, Zc, Z0, Z0c, Z1c, n_nodes, C, cin, rpt,
-               (n_nodes + npt - 1) / npt, phase, {rowptr2, colidx2, val2, nnz2}, Zg2, Zc2};
-    if (Ks == 3) {                                           // order 3: global-memory form only (MODE 0), eight waves
-        STC_REQUIRE(Zg2 && Zc2 && stc::aligned16(Zg2) && stc::aligned16(Zc2) && !Z0 && !Z0c, STC_EINVAL,
-                    "stc_cell_small_fwd_f32: order 3 wants the planes Zg2, Zc2 (16-byte aligned) and has no learned-graph outputs");
-        auto kern3 = xq == 4 ? small_fwd_kernel<3, 3, 4, 0> : small_fwd_kernel<3, 3, 1, 0>;
+               (n_nodes + npt - 1) / npt, phase, {rowptr2, colidx2, val2, nnz2}, Zg2, Zc2, Z2c};
+    STC_REQUIRE(Z2c == nullptr || (Ks == 3 && graph_is_dense && stc::aligned16(Z2c)), STC_EINVAL,
+                "stc_cell_small_fwd_f32: Z2c (16-byte aligned) is an output of order 3 with a dense graph");
+    if (Ks == 3) {                                           // order 3: nothing staged (MODE 0; a dense graph: MODE 3, split form), eight waves
+        STC_REQUIRE(Zg2 && Zc2 && stc::aligned16(Zg2) && stc::aligned16(Zc2) && (graph_is_dense || (!Z0 && !Z0c)), STC_EINVAL,
+                    "stc_cell_small_fwd_f32: order 3 wants the planes Zg2, Zc2 (16-byte aligned) and has learned-graph outputs for a dense graph only");
+        auto kern3 = graph_is_dense ? (xq == 4 ? small_fwd_kernel<3, 3, 4, 3> : small_fwd_kernel<3, 3, 1, 3>)
+                                    : (xq == 4 ? small_fwd_kernel<3, 3, 4, 0> : small_fwd_kernel<3, 3, 1, 0>);
         hipLaunchKernelGGL(kern3, dim3((unsigned)batch, (unsigned)splits), dim3(WgShape<3>::FWD_THREADS), 0, static_cast<hipStream_t>(stream), a);
         STC_LAUNCH_CHECK("stc_cell_small_fwd_f32 (order 3) launch");
         return STC_OK;
@@ -1148,8 +1285,9 @@ extern "C" int stc_cell_small_bwd_f32(const int32_t* rowptr, const int32_t* coli
                                       const float* Wc, const float* U, const float* R, const float* Cand, const float* RH, const float* Zg,
                                       const float* Zc, const float* Zg2, const float* Zc2, const float* dHnew,
                                       float* dX, int32_t accumulate_x, float* dH, int32_t accumulate_h, float* dparams, int64_t params_ld,
-                                      int32_t has_bg, int32_t has_bc, float* dZ1c, float* dZ1g, float* dYg, float* dYc, void* workspace,
-                                      size_t workspace_bytes, int32_t phase, int32_t splits, int32_t batch, int32_t C, void* stream) {
+                                      int32_t has_bg, int32_t has_bc, float* dZ1c, float* dZ1g, float* dYg, float* dYc, float* dZ2c, float* dZ2g,
+                                      void* workspace, size_t workspace_bytes, int32_t phase, int32_t splits, int32_t batch, int32_t C,
+                                      void* stream) {
     SC_COMMON_CHECKS("stc_cell_small_bwd_f32")
     STC_REQUIRE(rowptr && (nnz == 0 || (colidx && val)) && X && H && Tc && Wg && Wc && U && R && Cand && RH && Zg && Zc && dHnew && dparams && workspace,
                 STC_EINVAL, "stc_cell_small_bwd_f32: null operand");
@@ -1166,15 +1304,18 @@ extern "C" int stc_cell_small_bwd_f32(const int32_t* rowptr, const int32_t* coli
     const int npt = 16 / C, rpt = npt * C;
     SmallBwd a{{rowptr, colidx, val, nnz}, X, H, Tc, Wg, Wc, U, R, Cand, RH, Zg, Zc, dHnew, dX, dH, dparams, static_cast<float*>(workspace),
                dZ1c, dZ1g, dYg, dYc, n_nodes, C, cin, rpt, (n_nodes + npt - 1) / npt, accumulate_x, accumulate_h, has_bg, has_bc, phase, params_ld,
-               {rowptr2, colidx2, val2, nnz2}, Zg2, Zc2};
+               {rowptr2, colidx2, val2, nnz2}, Zg2, Zc2, dZ2c, dZ2g};
+    STC_REQUIRE((dZ2c == nullptr && dZ2g == nullptr) || (Ks == 3 && graph_is_dense), STC_EINVAL,
+                "stc_cell_small_bwd_f32: dZ2c / dZ2g are outputs of order 3 with a dense graph");
     STC_REQUIRE(((phase >= 0 && phase <= 4) || phase == 7) && splits >= 1 && splits <= 64 && (phase != 0 || splits == 1), STC_EINVAL,
                 "stc_cell_small_bwd_f32: phase %d / splits %d (0 = the whole cell; 1..4 = one phase; 7 = 2 + 3)", phase, splits);
-    if (Ks == 3) {                                           // order 3: global-memory form only (MODE 0), twelve waves
-        STC_REQUIRE(Zg2 && Zc2 && stc::aligned16(Zg2) && stc::aligned16(Zc2) && !dZ1c && !dZ1g && !dYc, STC_EINVAL,
-                    "stc_cell_small_bwd_f32: order 3 wants the planes Zg2, Zc2 (16-byte aligned) and leaves no learned-graph operands");
-        auto kern3 = xq == 4 ? small_bwd_kernel<3, 3, 4, 0> : small_bwd_kernel<3, 3, 1, 0>;
+    if (Ks == 3) {                                           // order 3: nothing staged (MODE 0; a dense graph: MODE 3, split form), twelve waves
+        STC_REQUIRE(Zg2 && Zc2 && stc::aligned16(Zg2) && stc::aligned16(Zc2) && (graph_is_dense || (!dZ1c && !dZ1g && !dYc)), STC_EINVAL,
+                    "stc_cell_small_bwd_f32: order 3 wants the planes Zg2, Zc2 (16-byte aligned) and leaves learned-graph operands for a dense graph only");
+        auto kern3 = graph_is_dense ? (xq == 4 ? small_bwd_kernel<3, 3, 4, 3> : small_bwd_kernel<3, 3, 1, 3>)
+                                    : (xq == 4 ? small_bwd_kernel<3, 3, 4, 0> : small_bwd_kernel<3, 3, 1, 0>);
         const size_t lds3 = (size_t)bwd_lds_fixed<3, 3>() * 4;
-        const hipError_t e3 = allow_lds_once(kern3, lds3, g_granted3[xq == 4]);
+        const hipError_t e3 = allow_lds_once(kern3, lds3, g_granted3[xq == 4][graph_is_dense != 0]);
         if (e3 != hipSuccess) return stc::hip_status(e3, "stc_cell_small_bwd_f32 LDS attribute");
         hipLaunchKernelGGL(kern3, dim3((unsigned)batch, (unsigned)splits), dim3(WgShape<3>::BWD_THREADS), lds3, static_cast<hipStream_t>(stream), a);
         STC_LAUNCH_CHECK("stc_cell_small_bwd_f32 (order 3) launch");

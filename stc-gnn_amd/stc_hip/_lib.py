@@ -22,7 +22,7 @@ from .graph import is_full_pattern
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, 'libstc_hip.so')
 # Mirrors of include/stc_hip.h (#define STC_<name>; tests/test_abi.py compares each, and HipKernels.ACT_AMAX_SLOTS, with the header)
-ABI_VERSION = 34
+ABI_VERSION = 35
 FMT_BF16X3, FMT_F16X2 = 0, 1          # operand formats of the split-operand matrix-core kernels
 MAX_K = 4
 SPMM_SUM_MAX_ADD = 8
@@ -106,9 +106,9 @@ _ABI = {
     'stc_cell_small_supported': (_int, [_i32, _i32, _i32, _i32, _i32]),
     'stc_cell_small_workspace_bytes': (_size, [_i32, _i32, _i32, _i32, _i32]),
     'stc_cell_small_param_rows': (_int, []),
-    'stc_cell_small_fwd_f32': (_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _i32, _p, _p, _i32, _i32] + [_p] * 16 + [_i32, _i32, _i32, _i32, _p]),
+    'stc_cell_small_fwd_f32': (_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _i32, _p, _p, _i32, _i32] + [_p] * 17 + [_i32, _i32, _i32, _i32, _p]),
     'stc_cell_small_bwd_f32': (_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _i32, _p, _p, _i32, _i32] + [_p] * 12
-                               + [_i32, _p, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _size, _i32, _i32, _i32, _i32, _p]),
+                               + [_i32, _p, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _size, _i32, _i32, _i32, _i32, _p]),
     'stc_graph_grad_f32': (_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _p]),
     'stc_mix_grad_f32': (_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _p]),
     'stc_mixed_fusion_workspace_bytes': (_size, [_i32, _i32]),
@@ -904,6 +904,9 @@ class HipKernels:
     #: C = 16: 18.3 | 13.4 (the general path's fp32-MFMA node kernels take C = 16) -- hence the extra rule in small.small_graph_supported.
     SMALL_PREFERRED_ROWS = 65535
     SMALL_STAGED_ROWS = 640      # N*C rows per sample that a compute unit's LDS stages (above: every gather from L2; dense graphs go to the general path)
+    #: Chebyshev order 3 with a learned dense graph on these kernels (``graph2`` = T_2(S) as a dense matrix; split form only).  A kernel set
+    #: without the attribute keeps that combination on the general path (``small.small_graph_supported``).
+    small_dense_order3 = True
 
     def cell_small_supported(self, Ks, Kc, Cc, cin, h, n_nodes=0) -> bool:
         return n_nodes * Cc <= self.SMALL_MAX_ROWS and bool(self.lib.stc_cell_small_supported(Ks, Kc, Cc, cin, h))
@@ -952,9 +955,12 @@ class HipKernels:
         """Arguments of the order-3 form: the second graph's CSR (T_2(S) in the launch's orientation) and the third-slab planes; order 2: nulls."""
         if Tc.shape[0] != 3:
             return (None, None, None, 0), (None, None)
-        if graph2 is None or planes2 is None or any(t is None for t in planes2) or dense:
-            raise StcError(f'{what}: Chebyshev order 3 takes graph2 = the CSR of T_2(S) = 2 S^2 - I (CsrGraph.second_order), the planes Zg2 / Zc2, and a fixed CSR graph')
+        if graph2 is None or planes2 is None or any(t is None for t in planes2):
+            raise StcError(f'{what}: Chebyshev order 3 takes graph2 = T_2(S) = 2 S^2 - I (CsrGraph.second_order; beside a dense graph: the full pattern '
+                           'with T_2 as a dense matrix) and the planes Zg2 / Zc2')
         rp2, ci2, v2 = graph2
+        if dense and (v2.numel() != N * N or not is_full_pattern(ci2, N, N)):
+            raise StcError(f'{what}: beside a dense graph, graph2 is the cached full pattern with T_2(S) as a dense ({N}, {N}) matrix; got {v2.numel()} values')
         self._i32(what + '.rowptr2', rp2, N + 1)
         self._i32(what + '.colidx2', ci2, v2.numel())
         _tensor(what + '.val2', v2)
@@ -964,9 +970,11 @@ class HipKernels:
         return (rp2.data_ptr(), ci2.data_ptr(), v2.data_ptr(), v2.numel()), (planes2[0].data_ptr(), planes2[1].data_ptr())
 
     def cell_small_fwd(self, rowptr, colidx, val, X, H, Tc, Wg, bg, Wc, bc, U, R, Cand, Hnew, RH, Zg, Zc, checked=True, Z0=None, splits=1, Z0c=None,
-                       Z1c=None, graph2=None, Zg2=None, Zc2=None):
+                       Z1c=None, graph2=None, Zg2=None, Zc2=None, Z2c=None):
         """One STC_Cell step (reference STC_GNN.py:65-79) in one launch: ``stc_cell_small_fwd_f32``.  (rowptr, colidx, val): CSR of Gs^T.
         Chebyshev order 3 (``Tc`` of three matrices): ``graph2`` = (rowptr, colidx, val) of 2 (Gs^T)^2 - I and the planes ``Zg2`` (like Zg), ``Zc2`` (like Zc).
+        Beside a dense graph (the cached full pattern) ``graph2`` is that pattern with T_2 as a dense matrix; the step then always runs as the
+        split launches (with ``splits`` = 1 too), and ``Z2c`` (optional, like Zg) receives the candidate's third slab.
         ``checked=False``: the caller built every buffer itself from shapes it already validated (the cell-graph executor).
         ``Z0`` (optional, like Zg): receives the slab [H | Xt | 0] (learned graphs: operand of the graph-gradient product).
         ``splits`` = G > 1: the cell as TWO launches (phases 1 + 2, then 3 + 4: R*H of the neighbours is the one dependency that crosses
@@ -974,7 +982,7 @@ class HipKernels:
         with one workgroup per sample (``cell_small_splits``)."""
         if checked:
             B, N, Cc, cin, Kc = self._small_shapes('cell_small_fwd', rowptr, colidx, val, X, H, Tc, Wg, Wc, dict(U=U, R=R, Cand=Cand, Hnew=Hnew, RH=RH), Zg, Zc)
-            for name, t_ in (('Z0', Z0), ('Z0c', Z0c), ('Z1c', Z1c)):
+            for name, t_ in (('Z0', Z0), ('Z0c', Z0c), ('Z1c', Z1c), ('Z2c', Z2c)):
                 if t_ is not None:
                     _tensor('cell_small_fwd.' + name, t_, tuple(Zg.shape))
                     self._same_device(H, t_)
@@ -985,11 +993,12 @@ class HipKernels:
             (B, N, Cc, _), cin, Kc = H.shape, X.shape[-1], Tc.shape[0]
         dense = int(is_full_pattern(colidx, N, N))
         g2, p2 = self._small_order3('cell_small_fwd', Tc, graph2, (Zg2, Zc2), Zg, Zc, dense, N)
-        for phase in ((0,) if splits == 1 else self.SMALL_FWD_PHASES):
+        phases = (0,) if splits == 1 and not (dense and Kc == 3) else self.SMALL_FWD_PHASES
+        for phase in phases:
             self._launch('stc_cell_small_fwd_f32', H, rowptr.data_ptr(), colidx.data_ptr(), val.data_ptr(), N, val.numel(), dense, *g2, X.data_ptr(), cin,
                          H.data_ptr(), Tc.data_ptr(), Kc, Kc, Wg.data_ptr(), _ptr(bg), Wc.data_ptr(), _ptr(bc), U.data_ptr(), R.data_ptr(), Cand.data_ptr(),
-                         Hnew.data_ptr(), RH.data_ptr(), Zg.data_ptr(), Zc.data_ptr(), *p2, _ptr(Z0), _ptr(Z0c), _ptr(Z1c), phase, splits, B, Cc,
-                         nbytes=(4 * B * N * Cc * (cin + 16 * 8 + 2 * self.cell_small_zg_width(cin))) // (1 if splits == 1 else len(self.SMALL_FWD_PHASES)))
+                         Hnew.data_ptr(), RH.data_ptr(), Zg.data_ptr(), Zc.data_ptr(), *p2, _ptr(Z0), _ptr(Z0c), _ptr(Z1c), _ptr(Z2c), phase, splits, B, Cc,
+                         nbytes=(4 * B * N * Cc * (cin + 16 * 8 + 2 * self.cell_small_zg_width(cin))) // len(phases))
 
     # Launches of a split cell step (phase codes of stc_cell_small_*_f32; 5 = 1 + 2, 6 = 3 + 4, 7 = 2 + 3), CSR and dense graphs alike
     SMALL_FWD_PHASES = (5, 6)
@@ -1008,9 +1017,10 @@ class HipKernels:
         return g
 
     def cell_small_bwd(self, rowptr, colidx, val, X, H, Tc, Wg, Wc, U, R, Cand, RH, Zg, Zc, dHnew, dX, accumulate_x, dH, accumulate_h,
-                       dparams, has_bg, has_bc, checked=True, dZ1c=None, dZ1g=None, dYg=None, splits=1, dYc=None, graph2=None, Zg2=None, Zc2=None):
+                       dparams, has_bg, has_bc, checked=True, dZ1c=None, dZ1g=None, dYg=None, splits=1, dYc=None, graph2=None, Zg2=None, Zc2=None, dZ2c=None, dZ2g=None):
         """Autograd of ``cell_small_fwd`` in one launch (``stc_cell_small_bwd_f32``).  (rowptr, colidx, val): CSR of Gs (order 3: ``graph2`` =
-        the CSR of 2 Gs^2 - I, ``Zg2`` / ``Zc2`` as the forward left them).  dX / dH may be
+        the CSR of 2 Gs^2 - I -- beside a dense graph: as a dense matrix; ``dZ2c`` / ``dZ2g`` then receive the third slabs' gradients --, ``Zg2`` /
+        ``Zc2`` as the forward left them).  dX / dH may be
         None; ``accumulate_*``: add to what the buffer holds.  ``dparams`` (B * cell_small_param_rows, P >= cell_small_params):
         parameter-gradient partials (one row per sample and wave), ADDED to."""
         if checked:
@@ -1022,22 +1032,23 @@ class HipKernels:
             if dparams.dim() != 2 or dparams.shape[0] != B * splits * self.cell_small_param_rows or dparams.shape[1] < self.cell_small_params(Kc, Kc, cin):
                 raise StcError(f'cell_small_bwd: dparams {tuple(dparams.shape)}, expected ({B * splits * self.cell_small_param_rows}, '
                                f'>= {self.cell_small_params(Kc, Kc, cin)})')
-            for name, t_, shape in (('dZ1c', dZ1c, tuple(Zg.shape)), ('dZ1g', dZ1g, tuple(Zg.shape)), ('dYg', dYg, (B, N * Cc, 32)), ('dYc', dYc, (B, N * Cc, 16))):
+            for name, t_, shape in (('dZ1c', dZ1c, tuple(Zg.shape)), ('dZ1g', dZ1g, tuple(Zg.shape)), ('dYg', dYg, (B, N * Cc, 32)), ('dYc', dYc, (B, N * Cc, 16)),
+                                    ('dZ2c', dZ2c, tuple(Zg.shape)), ('dZ2g', dZ2g, tuple(Zg.shape))):
                 if t_ is not None:
                     _tensor('cell_small_bwd.' + name, t_, shape)
-            self._same_device(H, dHnew, dparams, dZ1c, dZ1g, dYg, *([dX] if dX is not None else []))
+            self._same_device(H, dHnew, dparams, dZ1c, dZ1g, dYg, dZ2c, dZ2g, *([dX] if dX is not None else []))
         else:
             (B, N, Cc, _), cin, Kc = H.shape, X.shape[-1], Tc.shape[0]
         nbytes = self.lib.stc_cell_small_workspace_bytes(N, Cc, cin, B, Kc)
         ws = self._get_workspace(H.device, nbytes)
         dense = int(is_full_pattern(colidx, N, N))
         g2, p2 = self._small_order3('cell_small_bwd', Tc, graph2, (Zg2, Zc2), Zg, Zc, dense, N)
-        phases = (0,) if splits == 1 else self.SMALL_BWD_PHASES
+        phases = (0,) if splits == 1 and not (dense and Kc == 3) else self.SMALL_BWD_PHASES
         for phase in phases:
             self._launch('stc_cell_small_bwd_f32', H, rowptr.data_ptr(), colidx.data_ptr(), val.data_ptr(), N, val.numel(), dense, *g2, X.data_ptr(), cin,
                          H.data_ptr(), Tc.data_ptr(), Kc, Kc, Wg.data_ptr(), Wc.data_ptr(), U.data_ptr(), R.data_ptr(), Cand.data_ptr(), RH.data_ptr(),
                          Zg.data_ptr(), Zc.data_ptr(), *p2, dHnew.data_ptr(), _ptr(dX), int(bool(accumulate_x)), _ptr(dH), int(bool(accumulate_h)),
-                         dparams.data_ptr(), dparams.shape[1], int(bool(has_bg)), int(bool(has_bc)), _ptr(dZ1c), _ptr(dZ1g), _ptr(dYg), _ptr(dYc),
+                         dparams.data_ptr(), dparams.shape[1], int(bool(has_bg)), int(bool(has_bc)), _ptr(dZ1c), _ptr(dZ1g), _ptr(dYg), _ptr(dYc), _ptr(dZ2c), _ptr(dZ2g),
                          ws.data_ptr(), ws.numel(), phase, splits, B, Cc,
                          nbytes=(4 * B * N * Cc * (2 * cin + 16 * 9 + 5 * self.cell_small_zg_width(cin) + 64)) // len(phases))
 

@@ -13,7 +13,9 @@ with the same interface as ``ops.stc_cell_graph``:
 Learned graphs (the reference's own mode: dense Gs from MGP_Gen, Gc through its Chebyshev stack): the gradients of Gs and Gc are sums over
 ALL cells of a step, so the launches only leave their operands (the slab [H | X | 0], the gradients of the two aggregated slabs, the gate
 pre-activation gradients) and the backward forms  dGs^T = sum_cells dZ_1 x Z_0  and  dT_c = sum_cells V_c x dY  as a few stacked
-products per parameter set at the end -- not per cell.
+products per parameter set at the end -- not per cell.  At Chebyshev order 3 the second matrix T_2 = 2 V V - I (V = Gs^T) is formed OUTSIDE the
+node with differentiable torch ops and handed in as a second values tensor: the node returns  dT_2 = sum_cells dZ_2 x Z_0  beside d fwd_val,
+and torch's autograd carries it through the N x N product to Gs.
 """
 from __future__ import annotations
 
@@ -37,8 +39,12 @@ def small_graph_supported(k, op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_
     ``graph.dense_operand`` builds it) -- its gradient is formed as a dense product."""
     if dtype != torch.float32 or not hasattr(k, 'cell_small_supported') or (op.fwd_val.requires_grad and op.nnz != op.n * op.n):
         return False
-    if Ks == 3 and (op.source is None or op.fwd_val.requires_grad or op.nnz == op.n * op.n):
-        return False                                                # order 3: T_2(S) as a second CSR graph -- fixed sparse graphs only
+    if Ks == 3:                                                     # order 3: T_2(S) as a second graph --
+        if op.fwd_val.requires_grad:                                # a learned full-pattern graph (T_2 dense, split launches) where the kernel set takes one
+            if not getattr(k, 'small_dense_order3', False) or op.n * C > k.SMALL_STAGED_ROWS:
+                return False
+        elif op.source is None or op.nnz == op.n * op.n:            # else fixed sparse graphs (CsrGraph.second_order)
+            return False
     if op.nnz == op.n * op.n and op.n * C > k.SMALL_STAGED_ROWS:
         return False                                                # a dense graph aggregates as a matrix product on the STAGED plane: the sample must fit the LDS
     if op.n * C > k.SMALL_PREFERRED_ROWS or (C == 16 and op.n * C > 4096):
@@ -109,7 +115,9 @@ class _StcSmallGraph(Function):
     """schedule[j] = (stack, ('ext', i) | ('cell', k), ('ext', i) | ('cell', k)): parameter set, source of Xt, source of H."""
 
     @staticmethod
-    def forward(ctx, k, op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, *tensors):
+    def forward(ctx, k, op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, t2f, *tensors):
+        # t2f (order 3 with a dense learned graph, else None): T_2 = 2 V V - I, V = fwd_val as (N, N), flattened -- formed by the caller with
+        # differentiable ops; its gradient is this node's second graph output
         ext, stacks, Tc, fwd_val = _unpack(n_ext, Tc, fwd_val, tensors)
         n_cells = len(schedule)
         ref = ext[0]
@@ -130,13 +138,23 @@ class _StcSmallGraph(Function):
         inner = ref.new_empty(max(1, n_cells - len(outputs)), B, N, C, H16)
         planes = ref.new_empty(6 if Ks == 3 else 5, n_cells, B, N, C, H16)   # U, R, Cand, R*H, S.(R*H) of every cell (order 3: + T_2(S).(R*H))
         learned = bool(ctx.needs_input_grad[6] or ctx.needs_input_grad[7])
+        dense3 = Ks == 3 and t2f is not None
         # per width group: the aggregate Zg of every cell and, for learned graphs, the slabs Z0, Z0c, Z1c the graph-gradient products read
         widths = (k.cell_small_zg_width(1), k.cell_small_zg_width(H16))
-        if Ks == 3 and learned:
-            raise ValueError('stc_cell_graph: the small-graph cell kernels take learned graphs at Chebyshev order 2 only')
-        # (order 3: slot 1 holds the third slab T_2(S).[H | Xt | 0]; learned graphs -- order 2 only -- keep Z0, Z0c, Z1c in slots 1..3)
-        slabs = [ref.new_empty(4 if learned else (2 if Ks == 3 else 1), max(1, counts[w]), B, N * C, widths[w]) for w in (0, 1)]
-        g2 = op.source.second_order(ref.device) if Ks == 3 else None
+        if Ks == 3 and learned and not dense3:
+            raise ValueError('stc_cell_graph: at Chebyshev order 3 the small-graph cell kernels take learned graphs as a dense Gs only')
+        # (fixed graphs at order 3: slot 1 holds the third slab T_2(S).[H | Xt | 0]; learned graphs keep Z0, Z0c, Z1c in slots 1..3 and, at
+        #  order 3, the third slabs of the gates / the candidate in slots 4, 5)
+        zg2 = 4 if learned else 1
+        slabs = [ref.new_empty((6 if Ks == 3 else 4) if learned else (2 if Ks == 3 else 1), max(1, counts[w]), B, N * C, widths[w]) for w in (0, 1)]
+        t2b = None
+        if dense3:                                                   # the backward's orientation, T_2^T = 2 Gs^2 - I: formed once per forward
+            t2f = _c(t2f.detach())
+            t2b = t2f.view(N, N).t().contiguous().view(-1)
+            graph2 = (op.fwd_rowptr, op.fwd_colidx, t2f)
+        elif Ks == 3:
+            g2 = op.source.second_order(ref.device)
+            graph2 = (g2['fwd2_rowptr'], g2['fwd2_colidx'], g2['fwd2_val'])
         out_alias = _alias(out_stack)
         state = [out_alias[out_slot[j]] if j in out_slot else inner[inner_slot[j]] for j in range(n_cells)]
         U, R, Cand, RH, Zc, *Zc2 = (p.unbind(0) for p in planes.unbind(0))
@@ -152,11 +170,14 @@ class _StcSmallGraph(Function):
             w, i = pos[j]
             extra = dict(Z0=slabs[w][1, i], Z0c=slabs[w][2, i], Z1c=slabs[w][3, i]) if learned else {}
             if Ks == 3:
-                extra = dict(graph2=(g2['fwd2_rowptr'], g2['fwd2_colidx'], g2['fwd2_val']), Zg2=slabs[w][1, i], Zc2=Zc2[0][j].view(B, N * C, H16))
+                extra.update(graph2=graph2, Zg2=slabs[w][zg2, i], Zc2=Zc2[0][j].view(B, N * C, H16))
+                if learned:
+                    extra.update(Z2c=slabs[w][5, i])
             k.cell_small_fwd(op.fwd_rowptr, op.fwd_colidx, fwd_val, source(x), source(hs), Tc, Wg, bg, Wc, bc, U[j], R[j], Cand[j], state[j], RH[j],
                              slabs[w][0, i], Zc[j].view(B, N * C, H16), checked=False, splits=fwd_splits, **extra)
         ctx.save_for_backward(Tc, out_alias, inner, planes, slabs[0], slabs[1], *ext, *[p for st in stacks for p in st])
         ctx.meta = (k, op, Ks, list(schedule), tuple(outputs), cin, (B, N, C), len(ext), splits)
+        ctx.t2b = t2b                                                # (detached, never an input or output of the node: kept as it is)
         _guard(ctx, out_stack)
         return out_stack
 
@@ -169,19 +190,27 @@ class _StcSmallGraph(Function):
         slabs = (slabs_n, slabs_w)
         need_Tc, need_val = ctx.needs_input_grad[6], ctx.needs_input_grad[7]
         learned = bool(need_Tc or need_val)
+        dense3 = Ks == 3 and ctx.t2b is not None
+        need_t2 = dense3 and ctx.needs_input_grad[8]
+        zg2 = 4 if learned else 1
         ext, stacks = rest[:n_ext], _stacks(rest[n_ext:])
         n_cells = len(schedule)
         out_slot, inner_slot, pos, counts = _layout(schedule, cin, n_cells, outputs)
         state = [out_alias[out_slot[j]] if j in out_slot else inner[inner_slot[j]] for j in range(n_cells)]
         # learned graphs: what the launches leave for the graph-gradient products, per width group (zeros where a cell is never reached):
         # the gradients of the two aggregated slabs, the gate and candidate pre-activation gradients
-        dslab = [Tc.new_zeros(2, max(1, counts[w]), B, N * C, slabs[w].shape[-1]) for w in (0, 1)] if learned else None
+        # (order 3: + those of the two third slabs)
+        dslab = [Tc.new_zeros(4 if Ks == 3 else 2, max(1, counts[w]), B, N * C, slabs[w].shape[-1]) for w in (0, 1)] if learned else None
         dyg = [Tc.new_zeros(max(1, counts[w]), B, N * C, 2 * H16) for w in (0, 1)] if learned else None
         dyc = [Tc.new_zeros(max(1, counts[w]), B, N * C, H16) for w in (0, 1)] if learned else None
         U, R, Cand, RH, Zc, *Zc2 = (p.unbind(0) for p in planes.unbind(0))
         source = lambda src: ext[src[1]] if src[0] == 'ext' else state[src[1]]
         Kc = Tc.shape[0]
-        g2 = op.source.second_order(Tc.device) if Ks == 3 else None
+        if dense3:
+            graph2 = (op.bwd_rowptr, op.bwd_colidx, ctx.t2b)
+        elif Ks == 3:
+            g2 = op.source.second_order(Tc.device)
+            graph2 = (g2['bwd2_rowptr'], g2['bwd2_colidx'], g2['bwd2_val'])
         P = max(k.cell_small_params(Ks, Kc, w) for w in cin)
         dP = Tc.new_zeros(len(stacks), B * splits * k.cell_small_param_rows, P)   # parameter-gradient partials, every cell adds to its set's rows
         G = Tc.new_empty(n_cells, B, N, C, H16)                      # gradient owed to every cell's state
@@ -211,7 +240,9 @@ class _StcSmallGraph(Function):
             w, i = pos[j]
             extra = dict(dZ1c=dslab[w][0, i], dZ1g=dslab[w][1, i], dYg=dyg[w][i], dYc=dyc[w][i]) if learned else {}
             if Ks == 3:
-                extra = dict(graph2=(g2['bwd2_rowptr'], g2['bwd2_colidx'], g2['bwd2_val']), Zg2=slabs[w][1, i], Zc2=Zc2[0][j].view(B, N * C, H16))
+                extra.update(graph2=graph2, Zg2=slabs[w][zg2, i], Zc2=Zc2[0][j].view(B, N * C, H16))
+                if learned:
+                    extra.update(dZ2c=dslab[w][2, i], dZ2g=dslab[w][3, i])
             k.cell_small_bwd(op.bwd_rowptr, op.bwd_colidx, op.bwd_val, source(x), source(hs), Tc, Wg, Wc, U[j], R[j], Cand[j], RH[j], slabs[w][0, i],
                              Zc[j].view(B, N * C, H16), Gv[j], dX, acc_x, dH, acc_h, dPv[s_id], bg is not None, bc is not None, checked=False,
                              splits=splits, **extra)
@@ -228,16 +259,17 @@ class _StcSmallGraph(Function):
             dWg, dbg = row[:nW * 32].view(nW, 32), row[nW * 32:nW * 32 + 32]
             dWc, dbc = row[nW * 32 + 32:nW * 48 + 32].view(nW, H16), row[nW * 48 + 32:nW * 48 + 48]
             flat += [dWg, dbg if st[1] is not None else None, dWc, dbc if st[3] is not None else None]
-        dT = dS = None
+        dT = dS = dT2 = None
         if learned:
-            dT, dS = _graph_gradients(k, Tc, Ks, stacks, schedule, cin, pos, counts, (B, N, C), slabs, dslab, dyg, dyc, need_Tc, need_val)
-        return (None,) * 6 + (dT, dS) + (None,) * n_ext + tuple(flat)
+            dT, dS, dT2 = _graph_gradients(k, Tc, Ks, stacks, schedule, cin, pos, counts, (B, N, C), slabs, dslab, dyg, dyc, need_Tc, need_val, need_t2)
+        return (None,) * 6 + (dT, dS, dT2) + (None,) * n_ext + tuple(flat)
 
 
-def _graph_gradients(k, Tc, Ks, stacks, schedule, cin, pos, counts, dims, slabs, dslab, dyg, dyc, need_Tc, need_val):
-    """(dT_c, d fwd_val) of a learned-graph backward pass from what the cell launches left (module docstring), per width group (index 0:
-    narrow inputs, 1: 16-column inputs).  slabs[w] = (Zg, Z0, Z0c, Z1c), dslab[w] = (dZ1c, dZ1g) of every cell of the group, in the kernels'
-    column order [H (16) | X (cin) | 0]; W's rows are re-ordered to match.  The sums over cells and samples run in ``graph_grad`` /
+def _graph_gradients(k, Tc, Ks, stacks, schedule, cin, pos, counts, dims, slabs, dslab, dyg, dyc, need_Tc, need_val, need_t2=False):
+    """(dT_c, d fwd_val, d T_2) of a learned-graph backward pass from what the cell launches left (module docstring), per width group (index 0:
+    narrow inputs, 1: 16-column inputs).  slabs[w] = (Zg, Z0, Z0c, Z1c[, Zg2, Z2c]), dslab[w] = (dZ1c, dZ1g[, dZ2c, dZ2g]) of every cell of the
+    group (the bracketed ones at order 3), in the kernels' column order [H (16) | X (cin) | 0]; W's rows are re-ordered to match.  d T_2 (order 3)
+    is the same product as d fwd_val on the third slabs' gradients, its partials in the same buffer.  The sums over cells and samples run in ``graph_grad`` /
     ``mix_grad`` (stc_graph_grad_f32 / stc_mix_grad_f32: fp32 matrix products per plane, float64 accumulation):
       d fwd_val = sum_cells [dZ1g x Z0 + dZ1c x Z0c]                                      (every cell of a width at once)
       dT_c[c, d] = < W[(ks, c)], Q_ks[c, :, d, :] >,  Q_ks = Z_ks^T . dY                  (per parameter set and convolution)."""
@@ -246,11 +278,12 @@ def _graph_gradients(k, Tc, Ks, stacks, schedule, cin, pos, counts, dims, slabs,
     # every product of the pass leaves its float64 partials in ONE (chunks, total) buffer, side by side, and one sum adds them all: per
     # product that was an allocation, a reduction and -- for dT_c -- a stack, three weight copies and an einsum of its own (~100 launches of a
     # few microseconds per step at the SF shape)
-    graph_jobs = []                                               # (A, B, cells): dGs^T pieces
-    if need_val:
-        for w in (0, 1):
-            if counts[w]:
-                graph_jobs += [(dslab[w][1], slabs[w][1], counts[w]), (dslab[w][0], slabs[w][2], counts[w])]
+    graph_jobs = []                                               # (A, B, cells): dGs^T pieces, then (order 3) as many d T_2 pieces
+    for want, g, c in ((need_val, 1, 0), (need_t2, 3, 2)):
+        if want:
+            for w in (0, 1):
+                if counts[w]:
+                    graph_jobs += [(dslab[w][g], slabs[w][1], counts[w]), (dslab[w][c], slabs[w][2], counts[w])]
     classes = {}                                                  # (width group, convolution) -> [(slab 0, slab 1, W, dY, first cell, step, cells)]
     dT_direct = []                                                # dT_c pieces formed directly on the matrix cores (stc_mix_dt_f32)
     if need_Tc:
@@ -261,15 +294,18 @@ def _graph_gradients(k, Tc, Ks, stacks, schedule, cin, pos, counts, dims, slabs,
             w, first = pos[cells[0]]
             where = [pos[j][1] for j in cells]
             step = where[1] - where[0] if len(where) > 1 else 1
-            operands = ((slabs[w][1], slabs[w][0], Wg, dyg[w]), (slabs[w][2], slabs[w][3], Wc, dyc[w]))
+            # per convolution: (its Ks slabs, W, dY)
+            operands = (((slabs[w][1], slabs[w][0]) + ((slabs[w][4],) if Ks == 3 else ()), Wg, dyg[w]),
+                        ((slabs[w][2], slabs[w][3]) + ((slabs[w][5],) if Ks == 3 else ()), Wc, dyc[w]))
             if step < 1 or any(b_ - a_ != step for a_, b_ in zip(where, where[1:])):
                 # (a schedule STCGNN never builds: the set's cells are not evenly spaced inside their width group -- gather them)
                 pick = lambda t: torch.stack([t[i] for i in where])
-                operands = tuple((pick(s0), pick(s1), W, pick(dY)) for s0, s1, W, dY in operands)
+                operands = tuple((tuple(pick(s) for s in ss), W, pick(dY)) for ss, W, dY in operands)
                 first, step = 0, 1
-            for conv, (s0, s1, W, dY) in enumerate(operands):
+            for conv, (ss, W, dY) in enumerate(operands):
+                s0 = ss[0]
                 LP, Ho, cw = s0.shape[-1], W.shape[1], cin[cells[0]]
-                if Ks == 2 and step == 1 and hasattr(k, 'mix_dT') and k.mix_dT_supported(Ks, Kc, C, LP, Ho):
+                if step == 1 and hasattr(k, 'mix_dT') and k.mix_dT_supported(Ks, Kc, C, LP, Ho):
                     # the set's cells are consecutive planes of their slabs: dT_c = sum over their rows of U_c . dY^T in ONE launch on tiles of
                     # floor(16 / C) nodes (U_c = [Z_0 | Z_1] . W_c re-formed inside) -- instead of Ks products Q = Z^T . dY with float64
                     # partials, their sum and a contraction with W per class (0.44 + ~0.2 ms of the 4.65 ms learned-graph SF step)
@@ -280,48 +316,61 @@ def _graph_gradients(k, Tc, Ks, stacks, schedule, cin, pos, counts, dims, slabs,
                     Wp[:, :, H16:H16 + cw] = Wv[:, :, :cw]
                     rows = n * B * N
                     piece = Tc.new_empty(Kc, C, C)
-                    k.mix_dT([s0[first:first + n].view(rows, C, LP), s1[first:first + n].view(rows, C, LP)], Wp.view(Ks * Kc * LP, Ho),
+                    k.mix_dT([s[first:first + n].view(rows, C, LP) for s in ss], Wp.view(Ks * Kc * LP, Ho),
                              dY[first:first + n].view(rows, C, Ho), piece)
                     dT_direct.append(piece)
                     continue
-                classes.setdefault((w, cin[cells[0]], conv), []).append((s0, s1, W, dY, first, step, len(cells)))
+                classes.setdefault((w, cin[cells[0]], conv), []).append((ss, W, dY, first, step, len(cells)))
     block = lambda s0, dY: C * s0.shape[-1] * C * dY.shape[-1]
-    total = sum(Ks * block(e[0], e[3]) for es in classes.values() for e in es)
-    dS = None
-    if need_val:                                                  # (N x N blocks are small: more, shorter workgroups -- a buffer of their own)
-        dS = torch.zeros(N, N, dtype=torch.float64, device=Tc.device)
+    total = sum(Ks * block(e[0][0], e[2]) for es in classes.values() for e in es)
+    dS = dT2 = None
+    if need_val or need_t2:                                       # (N x N blocks are small: more, shorter workgroups -- a buffer of their own)
+        kinds = int(bool(need_val)) + int(bool(need_t2))
+        both = torch.zeros(kinds, N, N, dtype=torch.float64, device=Tc.device)
         if graph_jobs:
             gpart = k.grad_partials(Tc, len(graph_jobs) * N * N, chunks=max(1, min(256, min(n for _, _, n in graph_jobs) * B)))
             for i, (A, Bm, n_sel) in enumerate(graph_jobs):
                 k.graph_grad(A, Bm, 0, 1, n_sel, N, into=(gpart, i * N * N))
-            dS = gpart.view(-1, len(graph_jobs), N, N).sum((0, 1))
+            both = gpart.view(-1, kinds, len(graph_jobs) // kinds, N, N).sum((0, 2))       # ONE sum for the partials of both gradients
+        dS = both[0] if need_val else None
+        dT2 = both[kinds - 1] if need_t2 else None
     sums = None
     if total:
         part, off = k.grad_partials(Tc, total), 0
         for es in classes.values():
-            for s0, s1, W, dY, first, step, n_sel in es:
-                for slab in (s0, s1)[:Ks]:
+            for ss, W, dY, first, step, n_sel in es:
+                for slab in ss:
                     k.mix_grad(slab, dY, first, step, n_sel, N, into=(part, off))
-                    off += block(s0, dY)
+                    off += block(ss[0], dY)
         sums = part.sum(0)
     dT = torch.zeros(Tc.shape, dtype=torch.float64, device=Tc.device) if need_Tc else None
     if dT_direct:
         dT += torch.stack(dT_direct).sum(0)
     off = 0
     for (w, cw, conv), es in classes.items():
-        LP, Ho, L = es[0][0].shape[-1], es[0][2].shape[1], cw + H16
-        size = len(es) * Ks * block(es[0][0], es[0][3])
+        LP, Ho, L = es[0][0][0].shape[-1], es[0][1].shape[1], cw + H16
+        size = len(es) * Ks * block(es[0][0][0], es[0][2])
         Q = sums[off:off + size].view(len(es), Ks, C, LP, C, Ho)
         off += size
-        Wv = torch.stack([e[2] for e in es]).view(len(es), Ks, Kc, L, Ho)
+        Wv = torch.stack([e[1] for e in es]).view(len(es), Ks, Kc, L, Ho)
         Wp = Wv.new_zeros(len(es), Ks, Kc, LP, Ho)              # W's rows in the slabs' column order [H (16) | X (cin) | 0]
         Wp[..., :H16, :] = Wv[..., cw:, :]
         Wp[..., H16:H16 + cw, :] = Wv[..., :cw, :]
         # sum_{p,s,l,o} Q[p,s,c,l,d,o] W[p,s,k,l,o] as a product and a sum (as an einsum: a float64 GEMM with a 50-element result, 190 us)
         dT += (Q[:, :, None] * Wp.double()[:, :, :, None, :, None, :]).sum((0, 1, 4, 6))
-    return (None if dT is None else dT.to(Tc.dtype)), (None if dS is None else dS.to(Tc.dtype).reshape(-1))
+    flat32 = lambda g: None if g is None else g.to(Tc.dtype).reshape(-1)
+    return (None if dT is None else dT.to(Tc.dtype)), flat32(dS), flat32(dT2)
+
+
+def dense_second_order(op: SpatialOperand) -> torch.Tensor:
+    """T_2 = 2 V V - I of a dense learned Gs in the forward's orientation (V = ``op.fwd_val`` as (N, N) = Gs^T), flattened like ``fwd_val``: formed
+    by differentiable torch ops, so that autograd carries the node's d T_2 through the product back to Gs -- the node holds no hand-written
+    chain (the reference forms T_2 on the matrix side too: cheby_poly, STC_GNN.py:24-29)."""
+    V = op.fwd_val.view(op.n, op.n)
+    return (2.0 * (V @ V) - torch.eye(op.n, dtype=V.dtype, device=V.device)).reshape(-1)
 
 
 def stc_small_graph(k, op: SpatialOperand, Tc, Ks: int, schedule, outputs, ext, stacks):
     flat = [p for st in stacks for p in st]
-    return _StcSmallGraph.apply(k, op, Ks, list(schedule), list(outputs), len(ext), Tc, op.fwd_val, *ext, *flat)
+    t2f = dense_second_order(op) if Ks == 3 and op.nnz == op.n * op.n and op.source is None else None
+    return _StcSmallGraph.apply(k, op, Ks, list(schedule), list(outputs), len(ext), Tc, op.fwd_val, t2f, *ext, *flat)

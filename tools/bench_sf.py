@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """SF-shape train step (config 3 of BASELINE.json: B=32, T=9+3, N=100, C=5, h=16, K=2, 2 layers) on one MI355X.
+--order 3: the same model at Chebyshev order 3 (the reference's ``Main.py -K 3``); with --mode dense-learned --graph: learned dense graphs
+on the few-category cell kernels' order-3 dense form where the kernel set has it.  --repeats R times the step loop R times (their spread is
+the run-to-run noise of one process); --json adds one JSON line with every repeat.
 --mode dense-learned: the reference's full model incl. MGP_Gen/MixedFusion (2e8 parameters, Adam over 800 MB);
 --mode csr-fixed: encoder/decoder/head only on the fixed 10x10 queen grid (22 033 parameters).
 Prints ms/step and samples/s (reference on 8 CPU cores: 67 samples/s fwd+bwd, ~30 with Adam)."""
 import argparse
+import json
 import os
 import sys
 import time
@@ -12,19 +16,22 @@ for p in (REPO, os.path.join(REPO, 'stc-gnn_amd')):
     sys.path.insert(0, p)
 import torch
 import STC_GNN as M
-from stc_hip import CsrGraph
+from stc_hip import CsrGraph, ops
 from stc_hip.loss import ComboLoss
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--mode', default='csr-fixed')
 ap.add_argument('--steps', type=int, default=10)
+ap.add_argument('--order', type=int, default=2, help='Chebyshev order of both graphs (Main.py -K)')
+ap.add_argument('--repeats', type=int, default=1, help='time the loop of --steps steps this many times')
+ap.add_argument('--json', action='store_true', help='also print one JSON line (ms per step of every repeat, their median and spread)')
 ap.add_argument('--graph', action='store_true', help='capture the whole train step in a HIP graph and replay it')
 ap.add_argument('--fused-adam', action='store_true', help='torch.optim.Adam(fused=True): one multi-tensor kernel per step instead of ~10 passes')
 ap.add_argument('--profile', action='store_true', help='print the kernels of 3 steps by GPU time (torch.profiler)')
 a = ap.parse_args()
 dev = torch.device('cuda')
 torch.manual_seed(0)
-B, T, N, C, h, K, layers, hor = 32, 9, 100, 5, 16, 2, 2, 3
+B, T, N, C, h, K, layers, hor = 32, 9, 100, 5, 16, a.order, 2, 3
 model = M.STCGNN(N, C, K, K, 1, h, layers, hor, graph_mode=a.mode).to(dev)
 X = (torch.rand(B, T, N, C, device=dev) < 0.1635).float()
 Y = (torch.rand(B, hor, N, C, device=dev) < 0.1635).float()
@@ -45,6 +52,9 @@ def step():
     return loss
 
 
+small_calls = []                             # whether the cells run on the few-category kernels (stc_hip/small.py) or the general path
+_small_graph = ops.stc_small_graph
+ops.stc_small_graph = lambda *args, **kw: (small_calls.append(1), _small_graph(*args, **kw))[1]
 for _ in range(3):
     step()
 torch.cuda.synchronize()
@@ -61,13 +71,20 @@ if a.graph:
         static_loss = step()
     eager_step, step = step, (lambda: (graph.replay(), static_loss)[1])
     torch.cuda.synchronize()
-t0 = time.perf_counter()
-for _ in range(a.steps):
-    loss = step()
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t0) / a.steps
-print(f'SF shape {a.mode}{" hipGraph" if a.graph else ""}{" fused-adam" if a.fused_adam else ""}: {1e3 * dt:.2f} ms/step, {B / dt:.1f} samples/s, loss {float(loss.detach()):.4f}, '
+times = []
+for _ in range(max(1, a.repeats)):
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        loss = step()
+    torch.cuda.synchronize()
+    times.append((time.perf_counter() - t0) / a.steps)
+dt = sorted(times)[len(times) // 2]
+print(f'SF shape {a.mode}{" K=3" if K == 3 else ""}{" hipGraph" if a.graph else ""}{" fused-adam" if a.fused_adam else ""}: {1e3 * dt:.2f} ms/step, {B / dt:.1f} samples/s, loss {float(loss.detach()):.4f}, '
       f'{sum(p.numel() for p in model.parameters())} parameters', flush=True)
+if a.json:
+    print(json.dumps(dict(shape='sf', mode=a.mode, order=K, batch=B, hip_graph=a.graph, fused_adam=a.fused_adam, steps=a.steps, ms_per_step=1e3 * dt,
+                          repeats_ms=[1e3 * t for t in times], spread_ms=1e3 * (max(times) - min(times)), samples_per_s=B / dt,
+                          cells_on_small_graph_kernels=bool(small_calls), loss=float(loss.detach()))), flush=True)
 if a.profile:
     from torch.profiler import ProfilerActivity, profile
     with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
