@@ -47,7 +47,7 @@ constexpr int SC_H = 16, SC_MAXC = 16;
 // A learned DENSE Gs at order 3 (MODE 3 with KS = 3): the host forms T_2 as a dense row-major N x N matrix too (its gradient chain back to Gs
 // stays outside: stc_hip/small.py) and hands it over as `val2`; split form only (phases 5, 6 / 1, 7, 4 -- two N x N matrices plus the staged
 // planes do not fit the LDS at the SF shape, so phase 0 is refused).  The own-tile product then runs TWO S operand streams over one pass of the
-// source rows (aggregate_dense_own2): Z_1 and Z_2 from the same A operands in the forward, S^T dZ_1 + T_2^T dZ_2 into one result in the
+// source rows (aggregate_dense, NS = 2): Z_1 and Z_2 from the same A operands in the forward, S^T dZ_1 + T_2^T dZ_2 into one result in the
 // backward.  The workgroup shapes stay 8 / 12 waves and a workgroup's own-tile range is unchanged: the second stream costs four registers
 // of S values and two accumulators per lane (forward 172 / 149 registers wide / narrow of the 256 that eight waves allow, backward 157 of the
 // 168 that twelve allow; no scratch; LDS: none forward, the waves' dV tiles -- 76 032 bytes -- backward, as for CSR graphs).
@@ -115,216 +115,83 @@ __host__ __device__ constexpr int plane_stride(int xq) { return xq == 4 ? 36 : 2
 constexpr int SQ = 20;                                                                     // 16 consecutive rows fall on distinct banks
 
 // out[row][quad] = base + sum_e val[e] * fetch(colidx[e] * C + c, quad)  for the rows of one sample; fetch returns 4 columns of a source row.
-template <int THREADS, int QUADS, class Fetch, class Base, class Store>
-__device__ __forceinline__ void aggregate_rows(const int* __restrict__ gp, const int* __restrict__ gc, const float* __restrict__ gv, int NC, int C,
-                                               unsigned invC, int row_lo, int row_hi, Fetch fetch, Base base, Store store) {
-    (void)NC;
+// TWO: ... over two graphs with a source each (order 3's transposed aggregation  d[in] = dZ_0 + S^T dZ_1 + T_2(S)^T dZ_2).
+template <int THREADS, int QUADS, bool TWO, class Fetch, class Fetch2, class Base, class Store>
+__device__ __forceinline__ void aggregate_rows2(const int* __restrict__ gp, const int* __restrict__ gc, const float* __restrict__ gv,
+                                                const int* __restrict__ gp2, const int* __restrict__ gc2, const float* __restrict__ gv2, int C,
+                                                unsigned invC, int row_lo, int row_hi, Fetch fetch, Fetch2 fetch2, Base base, Store store) {
     for (int item = threadIdx.x; item < (row_hi - row_lo) * QUADS; item += THREADS) {       // the workgroup's own rows [row_lo, row_hi)
         const int row = row_lo + item / QUADS, q = item - (row - row_lo) * QUADS;
         const int n = div_c(row, invC), c = row - n * C;
         f32x4 s = base(row, q);
-        const int e1 = gp[n + 1];
-        for (int e = gp[n]; e < e1; ++e) {
-            const float v = gv[e];
-            const f32x4 x = fetch(gc[e] * C + c, q);
+        auto gather = [&](const int* p, const int* ci, const float* val, auto& from) {
+            const int e1 = p[n + 1];
+            for (int e = p[n]; e < e1; ++e) {
+                const float v = val[e];
+                const f32x4 x = from(ci[e] * C + c, q);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) s[i] = fmaf(v, x[i], s[i]);
-        }
+                for (int i = 0; i < 4; ++i) s[i] = fmaf(v, x[i], s[i]);
+            }
+        };
+        gather(gp, gc, gv, fetch);
+        if constexpr (TWO) gather(gp2, gc2, gv2, fetch2);
         store(row, q, s);
     }
+}
+template <int THREADS, int QUADS, class Fetch, class Base, class Store>
+__device__ __forceinline__ void aggregate_rows(const int* gp, const int* gc, const float* gv, int C, unsigned invC, int row_lo, int row_hi, Fetch fetch,
+                                               Base base, Store store) {
+    aggregate_rows2<THREADS, QUADS, false>(gp, gc, gv, gp, gc, gv, C, invC, row_lo, row_hi, fetch, fetch, base, store);   // (TWO = false: the second graph is never read)
 }
 
-// ... over TWO graphs with a source each (order 3's transposed aggregation  d[in] = dZ_0 + S^T dZ_1 + T_2(S)^T dZ_2):
-template <int THREADS, int QUADS, class Fetch, class Fetch2, class Base, class Store>
-__device__ __forceinline__ void aggregate_rows2(const int* __restrict__ gp, const int* __restrict__ gc, const float* __restrict__ gv,
-                                                const int* __restrict__ gp2, const int* __restrict__ gc2, const float* __restrict__ gv2, int C,
-                                                unsigned invC, int row_lo, int row_hi, Fetch fetch, Fetch2 fetch2, Base base, Store store) {
-    for (int item = threadIdx.x; item < (row_hi - row_lo) * QUADS; item += THREADS) {
-        const int row = row_lo + item / QUADS, q = item - (row - row_lo) * QUADS;
-        const int n = div_c(row, invC), c = row - n * C;
-        f32x4 s = base(row, q);
-        const int e1 = gp[n + 1];
-        for (int e = gp[n]; e < e1; ++e) {
-            const float v = gv[e];
-            const f32x4 x = fetch(gc[e] * C + c, q);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) s[i] = fmaf(v, x[i], s[i]);
-        }
-        const int f1 = gp2[n + 1];
-        for (int e = gp2[n]; e < f1; ++e) {
-            const float v = gv2[e];
-            const f32x4 x = fetch2(gc2[e] * C + c, q);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) s[i] = fmaf(v, x[i], s[i]);
-        }
-        store(row, q, s);
-    }
-}
+// What a workgroup walks and stores in aggregate_dense:
+struct WholeSample { static constexpr bool own = false; int split, splits; };      // every node tile of the sample, the items strided by split / splits
+struct OwnRows { static constexpr bool own = true; int n_lo, n_hi, row_lo, row_hi; };   // the node tiles covering the nodes [n_lo, n_hi), stores for [row_lo, row_hi)
 
 // The same aggregation for a DENSE graph (the reference's learned Gs: the CSR is the full N x N pattern, `S` its values as a row-major matrix)
-// as a matrix product on the staged plane: out^T tile = src^T . S^T, i.e. A = 16 columns of the source rows (LDS), B = 16 nodes' rows of S
-// (one 16-byte global load = the lane's B operands of four steps), so that a lane ends up with 4 consecutive COLUMNS of one output row --
-// the quad the CSR form's base / store callbacks take.  (Gathering 100 neighbour rows per output row from L2 instead costs ~100 us per phase.)
-template <int THREADS, int QUADS, class Base, class Store>
-__device__ __forceinline__ void aggregate_dense(const float* __restrict__ S, int N, int C, const float* src, int stride, int split, int splits, Base base,
-                                                Store store) {
-    constexpr int CT = (QUADS + 3) / 4;                          // 16-column tiles per (node, category) row
+// as a matrix product: out^T tile = src^T . S^T, i.e. A = 16 columns of the source rows, B = 16 nodes' rows of S (one 16-byte global load = the
+// lane's B operands of four steps), so that a lane ends up with 4 consecutive COLUMNS of one output row -- the quad the CSR form's base / store
+// callbacks take.  (Gathering 100 neighbour rows per output row from L2 instead costs ~100 us per phase.)
+//   WholeSample: on the staged plane (src in LDS: read where consumed; columns beyond 4 QUADS are clamped -- not stored; `ncols` is not read).
+//   OwnRows (split form, nothing staged): out[node][c][0 .. 4 QUADS) = sum_m S[node][m] src[m][c][.] for the rows a workgroup OWNS, the source rows
+//     read from global memory one block ahead (src: rows of `stride` floats per (node, category), `ncols` of them meaningful -- columns beyond read
+//     as zero).  Neighbouring workgroups share a boundary node tile and both compute it (what they do not own they drop), so a store callback may
+//     accumulate in place and a phase that needs the aggregate of its own rows only can follow in the same launch.
+//   NS = 2: TWO dense matrices (order 3 with a learned graph: S and T_2(S) = 2 S^2 - I, both row-major N x N), in ONE pass over the source rows:
+//     NX = 1 (forward):  out[node] = S.src and out2[node] = S2.src -- one source, read once; two results (store / store2, both added to base);
+//     NX = 2 (backward): out[node] = base + S.src + S2.src2 -- two sources (the slabs dZ_1, dZ_2), one result (store).
+template <int THREADS, int QUADS, int NS, int NX, class Walk, class Base, class Store, class Store2>
+__device__ __forceinline__ void aggregate_dense(const float* __restrict__ S, const float* __restrict__ S2, int N, int C, const float* src,
+                                                const float* src2, int stride, int ncols, Walk w, Base base, Store store, Store2 store2) {
+    constexpr int CT = (QUADS + 3) / 4, WAVES = THREADS / 64;    // 16-column tiles per (node, category) row
+    constexpr bool OWN = Walk::own;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, kq = lane >> 4;
-    const int rtiles = (N + 15) >> 4, per_rt = C * CT, pairs = (per_rt + 1) >> 1, items = rtiles * pairs;
+    const int rtiles = (N + 15) >> 4, per_rt = C * CT, pairs = (per_rt + 1) >> 1;
+    int rt_lo = 0, rt_hi = rtiles, first = wave, step = WAVES;
+    if constexpr (OWN) {
+        rt_lo = w.n_lo >> 4, rt_hi = (w.n_hi + 15) >> 4;
+    } else {
+        first += WAVES * w.split, step *= w.splits;
+    }
+    const int items = (rt_hi - rt_lo) * pairs;
     const bool vec = (N & 3) == 0;
     // a wave takes TWO column tiles of one row tile at a time: they share the B operand (the rows of S) and give the matrix pipe two
-    // independent accumulators (one accumulator = a chain of dependent instructions, 40 cycles each instead of 32)
-    for (int item = wave + (THREADS / 64) * split; item < items; item += (THREADS / 64) * splits) {
-        const int rt = item / pairs, t0 = 2 * (item - rt * pairs), t1 = min(t0 + 1, per_rt - 1);
-        const bool two = t0 + 1 < per_rt;
-        const int c0 = t0 / CT, lb0 = t0 - c0 * CT, c1 = t1 / CT, lb1 = t1 - c1 * CT;
-        const int node = 16 * rt + j;
-        const bool node_ok = node < N;
-        const unsigned srow = (unsigned)(node_ok ? node : 0) * N;
-        // the source column this lane feeds as A operand (clamped: extra columns are not stored)
-        const unsigned a0 = (unsigned)c0 * stride + min(16 * lb0 + j, 4 * QUADS - 1), a1 = (unsigned)c1 * stride + min(16 * lb1 + j, 4 * QUADS - 1);
-        auto load_s = [&](int kb) {                              // S[node][16 kb + 4 kq .. + 3], unmasked (clamped); the mask is applied when it is consumed
-            const int k0 = 16 * kb + 4 * kq;
-            if (vec) return ld4(S + (k0 < N ? srow + k0 : srow));
-            f32x4 v;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = S[srow + min(k0 + i, N - 1)];
-            return v;
-        };
-        f32x4 acc0 = zero4(), acc1 = zero4(), bn = load_s(0);
-        for (int kb = 0; kb < rtiles; ++kb) {
-            f32x4 b = bn;
-            if (kb + 1 < rtiles) bn = load_s(kb + 1);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int m = 16 * kb + 4 * kq + i;
-                const float bv = node_ok && m < N ? b[i] : 0.f;
-                const unsigned mrow = (unsigned)(min(m, N - 1) * C) * stride;
-                acc0 = mfma4(src[mrow + a0], bv, acc0);
-                acc1 = mfma4(src[mrow + a1], bv, acc1);
-            }
-        }
-        if (node_ok) {
-            const int q0 = 4 * lb0 + kq, q1 = 4 * lb1 + kq;
-            if (q0 < QUADS) {
-                const int row = node * C + c0;
-                f32x4 s = base(row, q0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) s[i] += acc0[i];
-                store(row, q0, s);
-            }
-            if (two && q1 < QUADS) {
-                const int row = node * C + c1;
-                f32x4 s = base(row, q1);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) s[i] += acc1[i];
-                store(row, q1, s);
-            }
-        }
-    }
-}
-
-// The dense aggregation for the rows a workgroup OWNS (split form, nothing staged): out[node][c][0 .. 4 QUADS) = sum_m S[node][m] src[m][c][.] for the
-// node tiles that cover the nodes [n_lo, n_hi), the source rows read from global memory (src: rows of `stride` floats per (node, category), `ncols`
-// of them meaningful -- columns beyond read as zero), store(row, quad, base(row, quad) + sum) for the OWN rows [row_lo, row_hi) only.  Neighbouring
-// workgroups share a boundary node tile and both compute it (what they do not own they drop), so a store callback may accumulate in place and a
-// phase that needs the aggregate of its own rows only can follow in the same launch.
-template <int THREADS, int QUADS, class Base, class Store>
-__device__ __forceinline__ void aggregate_dense_own(const float* __restrict__ S, int N, int C, const float* src, int stride, int ncols, int n_lo, int n_hi,
-                                                    int row_lo, int row_hi, Base base, Store store) {
-    constexpr int CT = (QUADS + 3) / 4;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, kq = lane >> 4;
-    const int rtiles = (N + 15) >> 4, per_rt = C * CT, pairs = (per_rt + 1) >> 1;
-    const int rt_lo = n_lo >> 4, rt_hi = (n_hi + 15) >> 4, items = (rt_hi - rt_lo) * pairs;
-    const bool vec = (N & 3) == 0;
-    for (int item = wave; item < items; item += THREADS / 64) {
+    // independent accumulators per matrix (one accumulator = a chain of dependent instructions, 40 cycles each instead of 32)
+    for (int item = first; item < items; item += step) {
         const int rt = rt_lo + item / pairs, t0 = 2 * (item - (rt - rt_lo) * pairs), t1 = min(t0 + 1, per_rt - 1);
         const bool two = t0 + 1 < per_rt;
-        const int c0 = t0 / CT, lb0 = t0 - c0 * CT, c1 = t1 / CT, lb1 = t1 - c1 * CT;
+        const int cat[2] = {t0 / CT, t1 / CT}, lb[2] = {t0 - cat[0] * CT, t1 - cat[1] * CT};
         const int node = 16 * rt + j;
         const bool node_ok = node < N;
         const unsigned srow = (unsigned)(node_ok ? node : 0) * N;
-        const int col0 = 16 * lb0 + j, col1 = 16 * lb1 + j;
-        const bool ok0 = col0 < ncols, ok1 = col1 < ncols;
-        const unsigned a0 = (unsigned)c0 * stride + (ok0 ? col0 : 0), a1 = (unsigned)c1 * stride + (ok1 ? col1 : 0);
-        auto load_s = [&](int kb) {
-            const int k0 = 16 * kb + 4 * kq;
-            if (vec) return ld4(S + (k0 < N ? srow + k0 : srow));
-            f32x4 v;
+        bool ok[2];                                              // the source column this lane feeds as A operand: masked beyond ncols / clamped
+        unsigned a[2];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = S[srow + min(k0 + i, N - 1)];
-            return v;
-        };
-        auto load_a = [&](int kb, float (&x0)[4], float (&x1)[4]) {         // the lane's source values of four steps (clamped rows; masked where consumed)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const unsigned mrow = (unsigned)(min(16 * kb + 4 * kq + i, N - 1) * C) * stride;
-                x0[i] = src[mrow + a0];
-                x1[i] = src[mrow + a1];
-            }
-        };
-        f32x4 acc0 = zero4(), acc1 = zero4(), bn = load_s(0);
-        float xn0[4], xn1[4];
-        load_a(0, xn0, xn1);
-        for (int kb = 0; kb < rtiles; ++kb) {
-            const f32x4 b = bn;
-            float x0[4], x1[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { x0[i] = xn0[i]; x1[i] = xn1[i]; }
-            if (kb + 1 < rtiles) {                                       // the next block's operands are requested before this block's products
-                bn = load_s(kb + 1);
-                load_a(kb + 1, xn0, xn1);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int m = 16 * kb + 4 * kq + i;
-                const float bv = node_ok && m < N ? b[i] : 0.f;
-                acc0 = mfma4(ok0 ? x0[i] : 0.f, bv, acc0);
-                acc1 = mfma4(ok1 ? x1[i] : 0.f, bv, acc1);
-            }
+        for (int p = 0; p < 2; ++p) {
+            const int col = 16 * lb[p] + j;
+            ok[p] = !OWN || col < ncols;
+            a[p] = (unsigned)cat[p] * stride + (OWN ? (ok[p] ? col : 0) : min(col, 4 * QUADS - 1));
         }
-        if (node_ok) {
-            const int q0 = 4 * lb0 + kq, q1 = 4 * lb1 + kq, r0 = node * C + c0, r1 = node * C + c1;
-            if (q0 < QUADS && r0 >= row_lo && r0 < row_hi) {
-                f32x4 s = base(r0, q0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) s[i] += acc0[i];
-                store(r0, q0, s);
-            }
-            if (two && q1 < QUADS && r1 >= row_lo && r1 < row_hi) {
-                f32x4 s = base(r1, q1);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) s[i] += acc1[i];
-                store(r1, q1, s);
-            }
-        }
-    }
-}
-
-// ... with TWO dense matrices (order 3 with a learned graph: S and T_2(S) = 2 S^2 - I, both row-major N x N), in ONE pass over the source rows:
-//   forward  (SUM = false): out[node] = S.src and out2[node] = S2.src -- one source, read once; two S operand streams, two results
-//            (store / store2, both added to base(row, quad));
-//   backward (SUM = true):  out[node] = base + S.src + S2.src2 -- two sources (the slabs dZ_1, dZ_2), one result (store).
-// Either way a lane carries four accumulators -- four independent chains on the matrix pipe -- and the same requests one block ahead.
-template <int THREADS, int QUADS, bool SUM, class Base, class Store, class Store2>
-__device__ __forceinline__ void aggregate_dense_own2(const float* __restrict__ S, const float* __restrict__ S2, int N, int C, const float* src,
-                                                     const float* src2, int stride, int ncols, int n_lo, int n_hi, int row_lo, int row_hi, Base base,
-                                                     Store store, Store2 store2) {
-    constexpr int CT = (QUADS + 3) / 4, NX = SUM ? 2 : 1;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, kq = lane >> 4;
-    const int rtiles = (N + 15) >> 4, per_rt = C * CT, pairs = (per_rt + 1) >> 1;
-    const int rt_lo = n_lo >> 4, rt_hi = (n_hi + 15) >> 4, items = (rt_hi - rt_lo) * pairs;
-    const bool vec = (N & 3) == 0;
-    for (int item = wave; item < items; item += THREADS / 64) {
-        const int rt = rt_lo + item / pairs, t0 = 2 * (item - (rt - rt_lo) * pairs), t1 = min(t0 + 1, per_rt - 1);
-        const bool two = t0 + 1 < per_rt;
-        const int c0 = t0 / CT, lb0 = t0 - c0 * CT, c1 = t1 / CT, lb1 = t1 - c1 * CT;
-        const int node = 16 * rt + j;
-        const bool node_ok = node < N;
-        const unsigned srow = (unsigned)(node_ok ? node : 0) * N;
-        const int col0 = 16 * lb0 + j, col1 = 16 * lb1 + j;
-        const bool ok0 = col0 < ncols, ok1 = col1 < ncols;
-        const unsigned a0 = (unsigned)c0 * stride + (ok0 ? col0 : 0), a1 = (unsigned)c1 * stride + (ok1 ? col1 : 0);
         auto load_s = [&](const float* __restrict__ Sm, int kb) {  // Sm[node][16 kb + 4 kq .. + 3], unmasked (clamped); masked where consumed
             const int k0 = 16 * kb + 4 * kq;
             if (vec) return ld4(Sm + (k0 < N ? srow + k0 : srow));
@@ -333,68 +200,77 @@ __device__ __forceinline__ void aggregate_dense_own2(const float* __restrict__ S
             for (int i = 0; i < 4; ++i) v[i] = Sm[srow + min(k0 + i, N - 1)];
             return v;
         };
-        auto load_a = [&](int kb, float (&x)[NX][2][4]) {          // the lane's source values of four steps (clamped rows; masked where consumed)
+        auto load_a = [&](int m, float (&x)[NX][2]) {              // the lane's source values of one step (clamped row; masked where consumed)
+            const unsigned mrow = (unsigned)(min(m, N - 1) * C) * stride;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const unsigned mrow = (unsigned)(min(16 * kb + 4 * kq + i, N - 1) * C) * stride;
-                x[0][0][i] = src[mrow + a0];
-                x[0][1][i] = src[mrow + a1];
-                if constexpr (SUM) {
-                    x[1][0][i] = src2[mrow + a0];
-                    x[1][1][i] = src2[mrow + a1];
-                }
+            for (int p = 0; p < 2; ++p) {
+                x[0][p] = src[mrow + a[p]];
+                if constexpr (NX == 2) x[1][p] = src2[mrow + a[p]];
             }
         };
-        f32x4 acc[2][2] = {{zero4(), zero4()}, {zero4(), zero4()}};         // [matrix][column tile of the pair]
-        f32x4 bn = load_s(S, 0), bn2 = load_s(S2, 0);
-        float xn[NX][2][4];
-        load_a(0, xn);
+        f32x4 acc[NS][2], bn[NS];                                  // [matrix][column tile of the pair]
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            acc[s][0] = acc[s][1] = zero4();
+            bn[s] = load_s(s == 0 ? S : S2, 0);
+        }
+        float x[4][NX][2], xn[4][NX][2];
+        if constexpr (OWN) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) load_a(4 * kq + i, xn[i]);
+        }
         for (int kb = 0; kb < rtiles; ++kb) {
-            const f32x4 b = bn, b2 = bn2;
-            float x[NX][2][4];
+            f32x4 b[NS];
 #pragma unroll
-            for (int s = 0; s < NX; ++s)
+            for (int s = 0; s < NS; ++s) b[s] = bn[s];
+            if constexpr (OWN) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) { x[s][0][i] = xn[s][0][i]; x[s][1][i] = xn[s][1][i]; }
-            if (kb + 1 < rtiles) {                                       // the next block's operands are requested before this block's products
-                bn = load_s(S, kb + 1);
-                bn2 = load_s(S2, kb + 1);
-                load_a(kb + 1, xn);
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int s = 0; s < NX; ++s) { x[i][s][0] = xn[i][s][0]; x[i][s][1] = xn[i][s][1]; }
+            }
+            if (kb + 1 < rtiles) {                                   // the next block's operands are requested before this block's products
+#pragma unroll
+                for (int s = 0; s < NS; ++s) bn[s] = load_s(s == 0 ? S : S2, kb + 1);
+                if constexpr (OWN) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) load_a(16 * (kb + 1) + 4 * kq + i, xn[i]);
+                }
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int m = 16 * kb + 4 * kq + i;
                 const bool live = node_ok && m < N;
-                const float bv = live ? b[i] : 0.f, bv2 = live ? b2[i] : 0.f;
-                acc[0][0] = mfma4(ok0 ? x[0][0][i] : 0.f, bv, acc[0][0]);
-                acc[0][1] = mfma4(ok1 ? x[0][1][i] : 0.f, bv, acc[0][1]);
-                acc[1][0] = mfma4(ok0 ? x[NX - 1][0][i] : 0.f, bv2, acc[1][0]);
-                acc[1][1] = mfma4(ok1 ? x[NX - 1][1][i] : 0.f, bv2, acc[1][1]);
+                if constexpr (!OWN) load_a(m, x[i]);
+#pragma unroll
+                for (int s = 0; s < NS; ++s)
+#pragma unroll
+                    for (int p = 0; p < 2; ++p) acc[s][p] = mfma4(ok[p] ? x[i][s < NX ? s : 0][p] : 0.f, live ? b[s][i] : 0.f, acc[s][p]);
             }
         }
         if (node_ok) {
-            const int q[2] = {4 * lb0 + kq, 4 * lb1 + kq}, r[2] = {node * C + c0, node * C + c1};
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-                if ((p == 1 && !two) || q[p] >= QUADS || r[p] < row_lo || r[p] >= row_hi) continue;
-                f32x4 s = base(r[p], q[p]);
-                if constexpr (SUM) {
+                const int q = 4 * lb[p] + kq, row = node * C + cat[p];
+                if ((p == 1 && !two) || q >= QUADS) continue;
+                if constexpr (OWN)
+                    if (row < w.row_lo || row >= w.row_hi) continue;
+                f32x4 s = base(row, q), s2 = s;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) s[i] += acc[0][p][i] + acc[1][p][i];
-                    store(r[p], q[p], s);
-                } else {
-                    f32x4 s2 = s;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        s[i] += acc[0][p][i];
-                        s2[i] += acc[1][p][i];
-                    }
-                    store(r[p], q[p], s);
-                    store2(r[p], q[p], s2);
+                for (int i = 0; i < 4; ++i) {
+                    if constexpr (NS == 2 && NX == 2) s[i] += acc[0][p][i] + acc[NS - 1][p][i];
+                    else s[i] += acc[0][p][i];
+                    if constexpr (NS == 2 && NX == 1) s2[i] += acc[NS - 1][p][i];
                 }
+                store(row, q, s);
+                if constexpr (NS == 2 && NX == 1) store2(row, q, s2);
             }
         }
     }
+}
+template <int THREADS, int QUADS, class Walk, class Base, class Store>
+__device__ __forceinline__ void aggregate_dense(const float* S, int N, int C, const float* src, int stride, int ncols, Walk w, Base base, Store store) {
+    aggregate_dense<THREADS, QUADS, 1, 1>(S, S, N, C, src, src, stride, ncols, w, base, store, store);   // (NS = 1: S2, src2, store2 are never used)
 }
 
 template <int THREADS>
@@ -548,8 +424,8 @@ template <int KC>
 __host__ __device__ constexpr int fwd_lds_fixed() { return 0; }                                         // floats of LDS every launch needs
 
 // MODE 0: graph and planes read from global memory; 1: CSR graph + planes staged in LDS; 2: dense graph (matrix-product aggregation), planes staged;
-// 3: dense graph in the split form (phase != 0): nothing staged, a workgroup aggregates the node tiles that cover its own rows (aggregate_dense_own;
-//    order 3: both matrices in one pass, aggregate_dense_own2)
+// 3: dense graph in the split form (phase != 0): nothing staged, a workgroup aggregates the node tiles that cover its own rows (aggregate_dense
+//    over OwnRows; order 3: both matrices in one pass, NS = 2)
 template <int KS, int KC, int XQ, int MODE>
 __global__ __launch_bounds__(WgShape<KS>::FWD_THREADS) void small_fwd_kernel(SmallFwd a) {
     constexpr int LP = 16 + 4 * XQ, XS = XQ == 4 ? 4 : XQ, SP = plane_stride(XQ);
@@ -589,7 +465,7 @@ __global__ __launch_bounds__(WgShape<KS>::FWD_THREADS) void small_fwd_kernel(Sma
     auto sync = [&](int after) { if (phase == 0 || (phase == 5 && after == 1) || (phase == 6 && after == 3)) __syncthreads(); };
     const int t_lo = (int)((long long)a.tiles * split / splits), t_hi = (int)((long long)a.tiles * (split + 1) / splits);
     const int row_lo = min(t_lo * a.rpt, NC), row_hi = min(t_hi * a.rpt, NC);
-    const int n_lo = div_c(row_lo, invC), n_hi = div_c(row_hi + C - 1, invC);      // the nodes of the workgroup's own rows (whole nodes: rpt = a multiple of C)
+    const OwnRows own{div_c(row_lo, invC), div_c(row_hi + C - 1, invC), row_lo, row_hi};      // the nodes of the workgroup's own rows (whole nodes: rpt = a multiple of C)
 
     // 0: tables, graph and the sample's rows into LDS (the gates' W operands are requested first: in flight during phases 0 and 1)
     const int ct = wave & 1;                                 // gates: wave w owns column tile w % 2 (0: update, 1: reset)
@@ -642,16 +518,16 @@ __global__ __launch_bounds__(WgShape<KS>::FWD_THREADS) void small_fwd_kernel(Sma
         auto none = [](int, int) -> f32x4 { return zero4(); };
         auto put = [&](int row, int q, f32x4 s) { st4(Zgb + (unsigned)row * LP + 4 * q, s); };
         if (DENSE && STAGED) {
-            aggregate_dense<SF_THREADS, LP / 4>(a.g.val, N, C, P, SP, 0, 1, none, put);
+            aggregate_dense<SF_THREADS, LP / 4>(a.g.val, N, C, P, SP, LP, WholeSample{0, 1}, none, put);
         } else if (DENSE && KS == 3) {                       // Zg and Zg2 = T_2(S) . [H | X] from one pass over the source rows (g2.val: T_2, dense)
-            aggregate_dense_own2<SF_THREADS, 4, false>(a.g.val, a.g2.val, N, C, Hb, Hb, SC_H, SC_H, n_lo, n_hi, row_lo, row_hi, none, put,
+            aggregate_dense<SF_THREADS, 4, 2, 1>(a.g.val, a.g2.val, N, C, Hb, Hb, SC_H, SC_H, own, none, put,
                                                        [&](int row, int q, f32x4 s) { st4(Zg2b + (unsigned)row * LP + 4 * q, s); });
-            aggregate_dense_own2<SF_THREADS, XQ, false>(a.g.val, a.g2.val, N, C, Xb, Xb, cin, cin, n_lo, n_hi, row_lo, row_hi, none,
+            aggregate_dense<SF_THREADS, XQ, 2, 1>(a.g.val, a.g2.val, N, C, Xb, Xb, cin, cin, own, none,
                                                         [&](int row, int q, f32x4 s) { st4(Zgb + (unsigned)row * LP + SC_H + 4 * q, s); },
                                                         [&](int row, int q, f32x4 s) { st4(Zg2b + (unsigned)row * LP + SC_H + 4 * q, s); });
         } else if (DENSE) {                                  // the H block and the X block of the slab from their own planes
-            aggregate_dense_own<SF_THREADS, 4>(a.g.val, N, C, Hb, SC_H, SC_H, n_lo, n_hi, row_lo, row_hi, none, put);
-            aggregate_dense_own<SF_THREADS, XQ>(a.g.val, N, C, Xb, cin, cin, n_lo, n_hi, row_lo, row_hi, none,
+            aggregate_dense<SF_THREADS, 4>(a.g.val, N, C, Hb, SC_H, SC_H, own, none, put);
+            aggregate_dense<SF_THREADS, XQ>(a.g.val, N, C, Xb, cin, cin, own, none,
                                                 [&](int row, int q, f32x4 s) { st4(Zgb + (unsigned)row * LP + SC_H + 4 * q, s); });
         } else {
             auto input_rows = [&](int src, int q) -> f32x4 {
@@ -664,9 +540,9 @@ __global__ __launch_bounds__(WgShape<KS>::FWD_THREADS) void small_fwd_kernel(Sma
                         if (4 * (q - 4) + i < cin) x[i] = Xb[(unsigned)src * cin + 4 * (q - 4) + i];
                     return x;
                 };
-            aggregate_rows<SF_THREADS, LP / 4>(gp, gc, gv, NC, C, invC, row_lo, row_hi, input_rows, none, put);
+            aggregate_rows<SF_THREADS, LP / 4>(gp, gc, gv, C, invC, row_lo, row_hi, input_rows, none, put);
             if constexpr (KS == 3)                           // Zg2 = T_2(S) . [H | X]: the same input rows through the second graph
-                aggregate_rows<SF_THREADS, LP / 4>(a.g2.rowptr, a.g2.colidx, a.g2.val, NC, C, invC, row_lo, row_hi, input_rows, none,
+                aggregate_rows<SF_THREADS, LP / 4>(a.g2.rowptr, a.g2.colidx, a.g2.val, C, invC, row_lo, row_hi, input_rows, none,
                                                    [&](int row, int q, f32x4 s) { st4(Zg2b + (unsigned)row * LP + 4 * q, s); });
         }
     }
@@ -703,17 +579,17 @@ __global__ __launch_bounds__(WgShape<KS>::FWD_THREADS) void small_fwd_kernel(Sma
         auto none = [](int, int) -> f32x4 { return zero4(); };
         auto put = [&](int row, int q, f32x4 s) { st4(Zcb + (unsigned)row * SC_H + 4 * q, s); };
         if (DENSE && STAGED)
-            aggregate_dense<SF_THREADS, 4>(a.g.val, N, C, Q, SQ, 0, 1, none, put);
+            aggregate_dense<SF_THREADS, 4>(a.g.val, N, C, Q, SQ, SC_H, WholeSample{0, 1}, none, put);
         else if (DENSE && KS == 3)                           // Zc and Zc2 = T_2(S) . (R*H), one pass
-            aggregate_dense_own2<SF_THREADS, 4, false>(a.g.val, a.g2.val, N, C, RHb, RHb, SC_H, SC_H, n_lo, n_hi, row_lo, row_hi, none, put,
+            aggregate_dense<SF_THREADS, 4, 2, 1>(a.g.val, a.g2.val, N, C, RHb, RHb, SC_H, SC_H, own, none, put,
                                                        [&](int row, int q, f32x4 s) { st4(Zc2b + (unsigned)row * SC_H + 4 * q, s); });
         else if (DENSE)
-            aggregate_dense_own<SF_THREADS, 4>(a.g.val, N, C, RHb, SC_H, SC_H, n_lo, n_hi, row_lo, row_hi, none, put);
+            aggregate_dense<SF_THREADS, 4>(a.g.val, N, C, RHb, SC_H, SC_H, own, none, put);
         else {
             auto rh_rows = [&](int src, int q) -> f32x4 { return STAGED ? ld4(Q + (unsigned)src * SQ + 4 * q) : ld4(RHb + (unsigned)src * SC_H + 4 * q); };
-            aggregate_rows<SF_THREADS, 4>(gp, gc, gv, NC, C, invC, row_lo, row_hi, rh_rows, none, put);
+            aggregate_rows<SF_THREADS, 4>(gp, gc, gv, C, invC, row_lo, row_hi, rh_rows, none, put);
             if constexpr (KS == 3)                           // Zc2 = T_2(S) . (R*H)
-                aggregate_rows<SF_THREADS, 4>(a.g2.rowptr, a.g2.colidx, a.g2.val, NC, C, invC, row_lo, row_hi, rh_rows, none,
+                aggregate_rows<SF_THREADS, 4>(a.g2.rowptr, a.g2.colidx, a.g2.val, C, invC, row_lo, row_hi, rh_rows, none,
                                               [&](int row, int q, f32x4 s) { st4(Zc2b + (unsigned)row * SC_H + 4 * q, s); });
         }
     }
@@ -1048,7 +924,7 @@ __global__ __launch_bounds__(WgShape<KS>::BWD_THREADS) void small_bwd_kernel(Sma
     auto sync = [&](int after) { if (phase == 0 || (phase == 7 && after == 2)) __syncthreads(); };
     const int t_lo = (int)((long long)a.tiles * split / splits), t_hi = (int)((long long)a.tiles * (split + 1) / splits);
     const int row_lo = min(t_lo * a.rpt, NC), row_hi = min(t_hi * a.rpt, NC);
-    const int n_lo = div_c(row_lo, invC), n_hi = div_c(row_hi + C - 1, invC);      // the nodes of the workgroup's own rows
+    const OwnRows own{div_c(row_lo, invC), div_c(row_hi + C - 1, invC), row_lo, row_hi};      // the nodes of the workgroup's own rows
     const int tile0 = t_lo + group, tstep = WgShape<KS>::BWD_GROUPS;
     float* dPw = a.dP + (((size_t)blockIdx.x * splits + split) * (SB_WAVES / 4) + group) * a.P;      // (rows per sample: stc_cell_small_param_rows, either order)
     float* dWg = dPw;
@@ -1118,17 +994,17 @@ __global__ __launch_bounds__(WgShape<KS>::BWD_THREADS) void small_bwd_kernel(Sma
             }
         };
         if (DENSE && KS == 3)                        // dZ_0 + S^T dZ_1 + T_2(S)^T dZ_2 as one pass of two matrix products (g2.val: T_2(S), dense)
-            aggregate_dense_own2<SB_THREADS, LP / 4, true>(a.g.val, a.g2.val, N, C, dZ1, dZ2, LP, LP, n_lo, n_hi, row_lo, row_hi, from_dz0, gate_bwd,
+            aggregate_dense<SB_THREADS, LP / 4, 2, 2>(a.g.val, a.g2.val, N, C, dZ1, dZ2, LP, LP, own, from_dz0, gate_bwd,
                                                            gate_bwd);
         else if (DENSE && !STAGED)
-            aggregate_dense_own<SB_THREADS, LP / 4>(a.g.val, N, C, dZ1, LP, LP, n_lo, n_hi, row_lo, row_hi, from_dz0, gate_bwd);
+            aggregate_dense<SB_THREADS, LP / 4>(a.g.val, N, C, dZ1, LP, LP, own, from_dz0, gate_bwd);
         else if (DENSE)
-            aggregate_dense<SB_THREADS, LP / 4>(a.g.val, N, C, dZ1, LP, split, splits, from_dz0, gate_bwd);
+            aggregate_dense<SB_THREADS, LP / 4>(a.g.val, N, C, dZ1, LP, LP, WholeSample{split, splits}, from_dz0, gate_bwd);
         else if constexpr (KS == 3)
-            aggregate_rows2<SB_THREADS, LP / 4>(gp, gc, gv, a.g2.rowptr, a.g2.colidx, a.g2.val, C, invC, row_lo, row_hi, from_dz1,
+            aggregate_rows2<SB_THREADS, LP / 4, true>(gp, gc, gv, a.g2.rowptr, a.g2.colidx, a.g2.val, C, invC, row_lo, row_hi, from_dz1,
                                                 [&](int src, int q) -> f32x4 { return ld4(dZ2 + (unsigned)src * LP + 4 * q); }, from_dz0, gate_bwd);
         else
-            aggregate_rows<SB_THREADS, LP / 4>(gp, gc, gv, NC, C, invC, row_lo, row_hi, from_dz1, from_dz0, gate_bwd);
+            aggregate_rows<SB_THREADS, LP / 4>(gp, gc, gv, C, invC, row_lo, row_hi, from_dz1, from_dz0, gate_bwd);
     }
     sync(2);
     SC_PHASE_END(2);
@@ -1166,16 +1042,16 @@ __global__ __launch_bounds__(WgShape<KS>::BWD_THREADS) void small_bwd_kernel(Sma
                 }
             };
         if (DENSE && KS == 3)
-            aggregate_dense_own2<SB_THREADS, LP / 4, true>(a.g.val, a.g2.val, N, C, dZ1s, dZ2s, LP, LP, n_lo, n_hi, row_lo, row_hi, from_dz0, add_in, add_in);
+            aggregate_dense<SB_THREADS, LP / 4, 2, 2>(a.g.val, a.g2.val, N, C, dZ1s, dZ2s, LP, LP, own, from_dz0, add_in, add_in);
         else if (DENSE && !STAGED)
-            aggregate_dense_own<SB_THREADS, LP / 4>(a.g.val, N, C, dZ1s, LP, LP, n_lo, n_hi, row_lo, row_hi, from_dz0, add_in);
+            aggregate_dense<SB_THREADS, LP / 4>(a.g.val, N, C, dZ1s, LP, LP, own, from_dz0, add_in);
         else if (DENSE)
-            aggregate_dense<SB_THREADS, LP / 4>(a.g.val, N, C, dZ1s, LP, split, splits, from_dz0, add_in);
+            aggregate_dense<SB_THREADS, LP / 4>(a.g.val, N, C, dZ1s, LP, LP, WholeSample{split, splits}, from_dz0, add_in);
         else if constexpr (KS == 3)
-            aggregate_rows2<SB_THREADS, LP / 4>(gp, gc, gv, a.g2.rowptr, a.g2.colidx, a.g2.val, C, invC, row_lo, row_hi, from_dz1,
+            aggregate_rows2<SB_THREADS, LP / 4, true>(gp, gc, gv, a.g2.rowptr, a.g2.colidx, a.g2.val, C, invC, row_lo, row_hi, from_dz1,
                                                 [&](int src, int q) -> f32x4 { return ld4(dZ2s + (unsigned)src * LP + 4 * q); }, from_dz0, add_in);
         else
-            aggregate_rows<SB_THREADS, LP / 4>(gp, gc, gv, NC, C, invC, row_lo, row_hi, from_dz1, from_dz0, add_in);
+            aggregate_rows<SB_THREADS, LP / 4>(gp, gc, gv, C, invC, row_lo, row_hi, from_dz1, from_dz0, add_in);
     }
 }
 

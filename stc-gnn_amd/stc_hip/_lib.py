@@ -969,6 +969,15 @@ class HipKernels:
         self._same_device(like_g, rp2, ci2, v2, *planes2)
         return (rp2.data_ptr(), ci2.data_ptr(), v2.data_ptr(), v2.numel()), (planes2[0].data_ptr(), planes2[1].data_ptr())
 
+    def _small_head(self, what, split_phases, splits, rowptr, colidx, val, X, H, Tc, Zg, Zc, graph2, Zg2, Zc2):
+        """Both directions' head, after their own checks: (B, N, C, cin, Kc), phase codes, leading launch arguments, Zg2 / Zc2 pointers."""
+        (B, N, Cc, _), cin, Kc = H.shape, X.shape[-1], Tc.shape[0]
+        dense = int(is_full_pattern(colidx, N, N))
+        g2, p2 = self._small_order3(what, Tc, graph2, (Zg2, Zc2), Zg, Zc, dense, N)
+        phases = (0,) if splits == 1 and not (dense and Kc == 3) else split_phases
+        head = (rowptr.data_ptr(), colidx.data_ptr(), val.data_ptr(), N, val.numel(), dense, *g2, X.data_ptr(), cin, H.data_ptr(), Tc.data_ptr(), Kc, Kc)
+        return (B, N, Cc, cin, Kc), phases, head, p2
+
     def cell_small_fwd(self, rowptr, colidx, val, X, H, Tc, Wg, bg, Wc, bc, U, R, Cand, Hnew, RH, Zg, Zc, checked=True, Z0=None, splits=1, Z0c=None,
                        Z1c=None, graph2=None, Zg2=None, Zc2=None, Z2c=None):
         """One STC_Cell step (reference STC_GNN.py:65-79) in one launch: ``stc_cell_small_fwd_f32``.  (rowptr, colidx, val): CSR of Gs^T.
@@ -981,7 +990,7 @@ class HipKernels:
         workgroups), each over G workgroups per sample that own a contiguous range of row tiles -- for batches too small to fill the chip
         with one workgroup per sample (``cell_small_splits``)."""
         if checked:
-            B, N, Cc, cin, Kc = self._small_shapes('cell_small_fwd', rowptr, colidx, val, X, H, Tc, Wg, Wc, dict(U=U, R=R, Cand=Cand, Hnew=Hnew, RH=RH), Zg, Zc)
+            self._small_shapes('cell_small_fwd', rowptr, colidx, val, X, H, Tc, Wg, Wc, dict(U=U, R=R, Cand=Cand, Hnew=Hnew, RH=RH), Zg, Zc)
             for name, t_ in (('Z0', Z0), ('Z0c', Z0c), ('Z1c', Z1c), ('Z2c', Z2c)):
                 if t_ is not None:
                     _tensor('cell_small_fwd.' + name, t_, tuple(Zg.shape))
@@ -989,14 +998,9 @@ class HipKernels:
             for name, b_, n in (('bg', bg, 32), ('bc', bc, 16)):
                 if b_ is not None:
                     _tensor('cell_small_fwd.' + name, b_, (n,))
-        else:
-            (B, N, Cc, _), cin, Kc = H.shape, X.shape[-1], Tc.shape[0]
-        dense = int(is_full_pattern(colidx, N, N))
-        g2, p2 = self._small_order3('cell_small_fwd', Tc, graph2, (Zg2, Zc2), Zg, Zc, dense, N)
-        phases = (0,) if splits == 1 and not (dense and Kc == 3) else self.SMALL_FWD_PHASES
+        (B, N, Cc, cin, Kc), phases, head, p2 = self._small_head('cell_small_fwd', self.SMALL_FWD_PHASES, splits, rowptr, colidx, val, X, H, Tc, Zg, Zc, graph2, Zg2, Zc2)
         for phase in phases:
-            self._launch('stc_cell_small_fwd_f32', H, rowptr.data_ptr(), colidx.data_ptr(), val.data_ptr(), N, val.numel(), dense, *g2, X.data_ptr(), cin,
-                         H.data_ptr(), Tc.data_ptr(), Kc, Kc, Wg.data_ptr(), _ptr(bg), Wc.data_ptr(), _ptr(bc), U.data_ptr(), R.data_ptr(), Cand.data_ptr(),
+            self._launch('stc_cell_small_fwd_f32', H, *head, Wg.data_ptr(), _ptr(bg), Wc.data_ptr(), _ptr(bc), U.data_ptr(), R.data_ptr(), Cand.data_ptr(),
                          Hnew.data_ptr(), RH.data_ptr(), Zg.data_ptr(), Zc.data_ptr(), *p2, _ptr(Z0), _ptr(Z0c), _ptr(Z1c), _ptr(Z2c), phase, splits, B, Cc,
                          nbytes=(4 * B * N * Cc * (cin + 16 * 8 + 2 * self.cell_small_zg_width(cin))) // len(phases))
 
@@ -1037,16 +1041,10 @@ class HipKernels:
                 if t_ is not None:
                     _tensor('cell_small_bwd.' + name, t_, shape)
             self._same_device(H, dHnew, dparams, dZ1c, dZ1g, dYg, dZ2c, dZ2g, *([dX] if dX is not None else []))
-        else:
-            (B, N, Cc, _), cin, Kc = H.shape, X.shape[-1], Tc.shape[0]
-        nbytes = self.lib.stc_cell_small_workspace_bytes(N, Cc, cin, B, Kc)
-        ws = self._get_workspace(H.device, nbytes)
-        dense = int(is_full_pattern(colidx, N, N))
-        g2, p2 = self._small_order3('cell_small_bwd', Tc, graph2, (Zg2, Zc2), Zg, Zc, dense, N)
-        phases = (0,) if splits == 1 and not (dense and Kc == 3) else self.SMALL_BWD_PHASES
+        (B, N, Cc, cin, Kc), phases, head, p2 = self._small_head('cell_small_bwd', self.SMALL_BWD_PHASES, splits, rowptr, colidx, val, X, H, Tc, Zg, Zc, graph2, Zg2, Zc2)
+        ws = self._get_workspace(H.device, self.lib.stc_cell_small_workspace_bytes(N, Cc, cin, B, Kc))
         for phase in phases:
-            self._launch('stc_cell_small_bwd_f32', H, rowptr.data_ptr(), colidx.data_ptr(), val.data_ptr(), N, val.numel(), dense, *g2, X.data_ptr(), cin,
-                         H.data_ptr(), Tc.data_ptr(), Kc, Kc, Wg.data_ptr(), Wc.data_ptr(), U.data_ptr(), R.data_ptr(), Cand.data_ptr(), RH.data_ptr(),
+            self._launch('stc_cell_small_bwd_f32', H, *head, Wg.data_ptr(), Wc.data_ptr(), U.data_ptr(), R.data_ptr(), Cand.data_ptr(), RH.data_ptr(),
                          Zg.data_ptr(), Zc.data_ptr(), *p2, dHnew.data_ptr(), _ptr(dX), int(bool(accumulate_x)), _ptr(dH), int(bool(accumulate_h)),
                          dparams.data_ptr(), dparams.shape[1], int(bool(has_bg)), int(bool(has_bc)), _ptr(dZ1c), _ptr(dZ1g), _ptr(dYg), _ptr(dYc), _ptr(dZ2c), _ptr(dZ2g),
                          ws.data_ptr(), ws.numel(), phase, splits, B, Cc,

@@ -111,6 +111,63 @@ def _layout(schedule, cin, n_cells, outputs):
     return out_slot, inner_slot, pos, counts
 
 
+class _Buffers:
+    """The stacked buffers of a pass, by name.  Of every cell, indexed [cell]: the planes U, R, Cand, RH, Zc (order 3: + Zc2 = T_2(S).(R*H)).  Per
+    width group w (``_layout``), indexed [w][position]: the slabs Zg and -- learned graphs: what the graph-gradient products read -- Z0, Z0c, Z1c;
+    at order 3 the third slabs Zg2 = T_2(S).[H | Xt | 0] and (learned) Z2c.  In the backward (``saved``: the forward's planes and slabs), for
+    learned graphs, what its launches leave (zeros where a cell is never reached): the gradients of the aggregated slabs dZ1c, dZ1g (order 3:
+    dZ2c, dZ2g) and the gate / candidate pre-activation gradients dYg, dYc.  A slot that the pass does not have is None."""
+    def __init__(self, k, Ks, learned, counts, dims, n_cells, like, saved=None):
+        B, N, C = self.dims = dims
+        self.Ks, self.counts, o3, cells = Ks, counts, Ks == 3, [max(1, c) for c in counts]
+        if saved is None:
+            self.planes = like.new_empty(6 if o3 else 5, n_cells, B, N, C, H16)
+            n_slabs = (4 if learned else 1) + o3 * (2 if learned else 1)
+            self.slabs = [like.new_empty(n_slabs, cells[w], B, N * C, k.cell_small_zg_width((1, H16)[w])) for w in (0, 1)]
+        else:
+            self.planes, *self.slabs = saved
+        per_slot = lambda stacked: iter(zip(*(st.unbind(0) for st in stacked)))      # slot by slot: (narrow group's, wide group's)
+        slots = per_slot(self.slabs)
+        self.Zg, self.Z0, self.Z0c, self.Z1c = (next(slots), next(slots), next(slots), next(slots)) if learned else (next(slots), None, None, None)
+        self.Zg2 = next(slots) if o3 else None
+        self.Z2c = next(slots) if o3 and learned else None
+        self.dZ1c = self.dZ1g = self.dZ2c = self.dZ2g = self.dYg = self.dYc = None
+        if saved is not None and learned:
+            slots = per_slot([like.new_zeros(4 if o3 else 2, cells[w], B, N * C, self.slabs[w].shape[-1]) for w in (0, 1)])
+            self.dZ1c, self.dZ1g, self.dZ2c, self.dZ2g = (*slots, None, None)[:4]
+            self.dYg, self.dYc = ([like.new_zeros(cells[w], B, N * C, width) for w in (0, 1)] for width in (2 * H16, H16))
+        self.U, self.R, self.Cand, self.RH, self.Zc, self.Zc2 = (*(p.unbind(0) for p in self.planes.unbind(0)), None)[:6]
+
+    def _cell(self, j, pos, graph2, **learned):                      # learned: the learned graphs' share of a launch, by argument name
+        (B, N, C), (w, i) = self.dims, pos
+        order3 = dict(graph2=graph2, Zg2=self.Zg2[w][i], Zc2=self.Zc2[j].view(B, N * C, H16)) if self.Ks == 3 else {}
+        return dict(U=self.U[j], R=self.R[j], Cand=self.Cand[j], RH=self.RH[j], Zg=self.Zg[w][i], Zc=self.Zc[j].view(B, N * C, H16),
+                    **{name: s[w][i] for name, s in learned.items() if s is not None}, **order3)
+
+    def fwd_args(self, j, pos, graph2):                              # cell j's buffers as keyword arguments of ``cell_small_fwd``
+        return self._cell(j, pos, graph2, Z0=self.Z0, Z0c=self.Z0c, Z1c=self.Z1c, Z2c=self.Z2c)
+
+    def bwd_args(self, j, pos, graph2):                              # ... of ``cell_small_bwd``
+        return self._cell(j, pos, graph2, dZ1c=self.dZ1c, dZ1g=self.dZ1g, dZ2c=self.dZ2c, dZ2g=self.dZ2g, dYg=self.dYg, dYc=self.dYc)
+
+
+def _graph2(op, Ks, t2, device, direction):
+    """Order 3's T_2(S) for ``direction`` ('fwd' / 'bwd'): the full pattern with the dense ``t2``, else the fixed graph's own; order 2: None."""
+    if Ks == 3 and t2 is not None:
+        return getattr(op, direction + '_rowptr'), getattr(op, direction + '_colidx'), t2
+    g2 = op.source.second_order(device) if Ks == 3 else None
+    return g2 and tuple(g2[f'{direction}2_{part}'] for part in ('rowptr', 'colidx', 'val'))
+
+
+def _slab_order(W, Ks, Kc, cw, LP):
+    """W (..., Ks * Kc * (cw + 16), Ho) as (..., Ks, Kc, LP, Ho) with its rows in the slabs' column order [H (16) | X (cin) | 0]."""
+    Wv = W.view(*W.shape[:-2], Ks, Kc, cw + H16, W.shape[-1])
+    Wp = Wv.new_zeros(*Wv.shape[:-2], LP, W.shape[-1])
+    Wp[..., :H16, :] = Wv[..., cw:, :]
+    Wp[..., H16:H16 + cw, :] = Wv[..., :cw, :]
+    return Wp
+
+
 class _StcSmallGraph(Function):
     """schedule[j] = (stack, ('ext', i) | ('cell', k), ('ext', i) | ('cell', k)): parameter set, source of Xt, source of H."""
 
@@ -136,48 +193,26 @@ class _StcSmallGraph(Function):
         out_slot, inner_slot, pos, counts = _layout(schedule, cin, n_cells, outputs)
         out_stack = ref.new_empty(len(outputs), B, N, C, H16)        # the requested states are produced in place, stacked
         inner = ref.new_empty(max(1, n_cells - len(outputs)), B, N, C, H16)
-        planes = ref.new_empty(6 if Ks == 3 else 5, n_cells, B, N, C, H16)   # U, R, Cand, R*H, S.(R*H) of every cell (order 3: + T_2(S).(R*H))
         learned = bool(ctx.needs_input_grad[6] or ctx.needs_input_grad[7])
-        dense3 = Ks == 3 and t2f is not None
-        # per width group: the aggregate Zg of every cell and, for learned graphs, the slabs Z0, Z0c, Z1c the graph-gradient products read
-        widths = (k.cell_small_zg_width(1), k.cell_small_zg_width(H16))
-        if Ks == 3 and learned and not dense3:
+        if Ks == 3 and learned and t2f is None:
             raise ValueError('stc_cell_graph: at Chebyshev order 3 the small-graph cell kernels take learned graphs as a dense Gs only')
-        # (fixed graphs at order 3: slot 1 holds the third slab T_2(S).[H | Xt | 0]; learned graphs keep Z0, Z0c, Z1c in slots 1..3 and, at
-        #  order 3, the third slabs of the gates / the candidate in slots 4, 5)
-        zg2 = 4 if learned else 1
-        slabs = [ref.new_empty((6 if Ks == 3 else 4) if learned else (2 if Ks == 3 else 1), max(1, counts[w]), B, N * C, widths[w]) for w in (0, 1)]
-        t2b = None
-        if dense3:                                                   # the backward's orientation, T_2^T = 2 Gs^2 - I: formed once per forward
-            t2f = _c(t2f.detach())
-            t2b = t2f.view(N, N).t().contiguous().view(-1)
-            graph2 = (op.fwd_rowptr, op.fwd_colidx, t2f)
-        elif Ks == 3:
-            g2 = op.source.second_order(ref.device)
-            graph2 = (g2['fwd2_rowptr'], g2['fwd2_colidx'], g2['fwd2_val'])
+        bufs = _Buffers(k, Ks, learned, counts, (B, N, C), n_cells, ref)
+        t2f = _c(t2f.detach()) if Ks == 3 and t2f is not None else None
+        ctx.t2b = None if t2f is None else t2f.view(N, N).t().contiguous().view(-1)      # T_2^T = 2 Gs^2 - I for the backward: once per forward, detached
+        graph2 = _graph2(op, Ks, t2f, ref.device, 'fwd')
         out_alias = _alias(out_stack)
         state = [out_alias[out_slot[j]] if j in out_slot else inner[inner_slot[j]] for j in range(n_cells)]
-        U, R, Cand, RH, Zc, *Zc2 = (p.unbind(0) for p in planes.unbind(0))
         source = lambda src: ext[src[1]] if src[0] == 'ext' else state[src[1]]
         # Few samples: a cell step runs as a few launches over several workgroups per sample (each owning a contiguous range of row tiles)
         # instead of one launch with one workgroup per sample -- at the SF shape (batch 32) backward 79 -> ~45 us per cell in three
         # launches, forward 35 -> 24 us in two.  Dense learned graphs split alike: their aggregations are matrix products, in the forward over
         # the node tiles that cover a workgroup's own rows (so that the phase pairs still share a launch), in the backward over all workgroups.
         splits = k.cell_small_splits(B, N * C)
-        fwd_splits = splits
         for j, (s_id, x, hs) in enumerate(schedule):
-            Wg, bg, Wc, bc = stacks[s_id]
-            w, i = pos[j]
-            extra = dict(Z0=slabs[w][1, i], Z0c=slabs[w][2, i], Z1c=slabs[w][3, i]) if learned else {}
-            if Ks == 3:
-                extra.update(graph2=graph2, Zg2=slabs[w][zg2, i], Zc2=Zc2[0][j].view(B, N * C, H16))
-                if learned:
-                    extra.update(Z2c=slabs[w][5, i])
-            k.cell_small_fwd(op.fwd_rowptr, op.fwd_colidx, fwd_val, source(x), source(hs), Tc, Wg, bg, Wc, bc, U[j], R[j], Cand[j], state[j], RH[j],
-                             slabs[w][0, i], Zc[j].view(B, N * C, H16), checked=False, splits=fwd_splits, **extra)
-        ctx.save_for_backward(Tc, out_alias, inner, planes, slabs[0], slabs[1], *ext, *[p for st in stacks for p in st])
+            k.cell_small_fwd(op.fwd_rowptr, op.fwd_colidx, fwd_val, source(x), source(hs), Tc, *stacks[s_id], Hnew=state[j], checked=False,
+                             splits=splits, **bufs.fwd_args(j, pos[j], graph2))
+        ctx.save_for_backward(Tc, out_alias, inner, bufs.planes, *bufs.slabs, *ext, *[p for st in stacks for p in st])
         ctx.meta = (k, op, Ks, list(schedule), tuple(outputs), cin, (B, N, C), len(ext), splits)
-        ctx.t2b = t2b                                                # (detached, never an input or output of the node: kept as it is)
         _guard(ctx, out_stack)
         return out_stack
 
@@ -187,30 +222,15 @@ class _StcSmallGraph(Function):
         k, op, Ks, schedule, outputs, cin, (B, N, C), n_ext, splits = ctx.meta
         _check_guard(ctx)
         Tc, out_alias, inner, planes, slabs_n, slabs_w, *rest = ctx.saved_tensors
-        slabs = (slabs_n, slabs_w)
-        need_Tc, need_val = ctx.needs_input_grad[6], ctx.needs_input_grad[7]
+        need_Tc, need_val, need_t2 = ctx.needs_input_grad[6:9]
         learned = bool(need_Tc or need_val)
-        dense3 = Ks == 3 and ctx.t2b is not None
-        need_t2 = dense3 and ctx.needs_input_grad[8]
-        zg2 = 4 if learned else 1
         ext, stacks = rest[:n_ext], _stacks(rest[n_ext:])
         n_cells = len(schedule)
         out_slot, inner_slot, pos, counts = _layout(schedule, cin, n_cells, outputs)
         state = [out_alias[out_slot[j]] if j in out_slot else inner[inner_slot[j]] for j in range(n_cells)]
-        # learned graphs: what the launches leave for the graph-gradient products, per width group (zeros where a cell is never reached):
-        # the gradients of the two aggregated slabs, the gate and candidate pre-activation gradients
-        # (order 3: + those of the two third slabs)
-        dslab = [Tc.new_zeros(4 if Ks == 3 else 2, max(1, counts[w]), B, N * C, slabs[w].shape[-1]) for w in (0, 1)] if learned else None
-        dyg = [Tc.new_zeros(max(1, counts[w]), B, N * C, 2 * H16) for w in (0, 1)] if learned else None
-        dyc = [Tc.new_zeros(max(1, counts[w]), B, N * C, H16) for w in (0, 1)] if learned else None
-        U, R, Cand, RH, Zc, *Zc2 = (p.unbind(0) for p in planes.unbind(0))
+        bufs = _Buffers(k, Ks, learned, counts, (B, N, C), n_cells, Tc, saved=(planes, slabs_n, slabs_w))
         source = lambda src: ext[src[1]] if src[0] == 'ext' else state[src[1]]
-        Kc = Tc.shape[0]
-        if dense3:
-            graph2 = (op.bwd_rowptr, op.bwd_colidx, ctx.t2b)
-        elif Ks == 3:
-            g2 = op.source.second_order(Tc.device)
-            graph2 = (g2['bwd2_rowptr'], g2['bwd2_colidx'], g2['bwd2_val'])
+        Kc, graph2 = Tc.shape[0], _graph2(op, Ks, ctx.t2b, Tc.device, 'bwd')
         P = max(k.cell_small_params(Ks, Kc, w) for w in cin)
         dP = Tc.new_zeros(len(stacks), B * splits * k.cell_small_param_rows, P)   # parameter-gradient partials, every cell adds to its set's rows
         G = Tc.new_empty(n_cells, B, N, C, H16)                      # gradient owed to every cell's state
@@ -225,9 +245,8 @@ class _StcSmallGraph(Function):
                 continue                                             # nothing downstream depends on this cell
             s_id, x, hs = schedule[j]
             Wg, bg, Wc, bc = stacks[s_id]
-            dX = dH = None
+            dX = dH = late = None
             acc_x = acc_h = False
-            late = None
             if hs[0] == 'cell':
                 dH, acc_h = Gv[hs[1]], owed[hs[1]]
                 owed[hs[1]] = True
@@ -237,15 +256,9 @@ class _StcSmallGraph(Function):
                 else:
                     dX, acc_x = Gv[x[1]], owed[x[1]]
                     owed[x[1]] = True
-            w, i = pos[j]
-            extra = dict(dZ1c=dslab[w][0, i], dZ1g=dslab[w][1, i], dYg=dyg[w][i], dYc=dyc[w][i]) if learned else {}
-            if Ks == 3:
-                extra.update(graph2=graph2, Zg2=slabs[w][zg2, i], Zc2=Zc2[0][j].view(B, N * C, H16))
-                if learned:
-                    extra.update(dZ2c=dslab[w][2, i], dZ2g=dslab[w][3, i])
-            k.cell_small_bwd(op.bwd_rowptr, op.bwd_colidx, op.bwd_val, source(x), source(hs), Tc, Wg, Wc, U[j], R[j], Cand[j], RH[j], slabs[w][0, i],
-                             Zc[j].view(B, N * C, H16), Gv[j], dX, acc_x, dH, acc_h, dPv[s_id], bg is not None, bc is not None, checked=False,
-                             splits=splits, **extra)
+            k.cell_small_bwd(op.bwd_rowptr, op.bwd_colidx, op.bwd_val, source(x), source(hs), Tc, Wg, Wc, dHnew=Gv[j], dX=dX, accumulate_x=acc_x, dH=dH,
+                             accumulate_h=acc_h, dparams=dPv[s_id], has_bg=bg is not None, has_bc=bc is not None, checked=False, splits=splits,
+                             **bufs.bwd_args(j, pos[j], graph2))
             if late is not None:
                 Gv[late].add_(dX)
         sums = dP.sum(1)                                             # (sets, P)
@@ -259,31 +272,25 @@ class _StcSmallGraph(Function):
             dWg, dbg = row[:nW * 32].view(nW, 32), row[nW * 32:nW * 32 + 32]
             dWc, dbc = row[nW * 32 + 32:nW * 48 + 32].view(nW, H16), row[nW * 48 + 32:nW * 48 + 48]
             flat += [dWg, dbg if st[1] is not None else None, dWc, dbc if st[3] is not None else None]
-        dT = dS = dT2 = None
-        if learned:
-            dT, dS, dT2 = _graph_gradients(k, Tc, Ks, stacks, schedule, cin, pos, counts, (B, N, C), slabs, dslab, dyg, dyc, need_Tc, need_val, need_t2)
-        return (None,) * 6 + (dT, dS, dT2) + (None,) * n_ext + tuple(flat)
+        graph_grads = _graph_gradients(bufs, k, Tc, stacks, schedule, cin, pos, need_Tc, need_val, need_t2 and ctx.t2b is not None) if learned else (None,) * 3
+        return (None,) * 6 + graph_grads + (None,) * n_ext + tuple(flat)
 
 
-def _graph_gradients(k, Tc, Ks, stacks, schedule, cin, pos, counts, dims, slabs, dslab, dyg, dyc, need_Tc, need_val, need_t2=False):
-    """(dT_c, d fwd_val, d T_2) of a learned-graph backward pass from what the cell launches left (module docstring), per width group (index 0:
-    narrow inputs, 1: 16-column inputs).  slabs[w] = (Zg, Z0, Z0c, Z1c[, Zg2, Z2c]), dslab[w] = (dZ1c, dZ1g[, dZ2c, dZ2g]) of every cell of the
-    group (the bracketed ones at order 3), in the kernels' column order [H (16) | X (cin) | 0]; W's rows are re-ordered to match.  d T_2 (order 3)
-    is the same product as d fwd_val on the third slabs' gradients, its partials in the same buffer.  The sums over cells and samples run in ``graph_grad`` /
-    ``mix_grad`` (stc_graph_grad_f32 / stc_mix_grad_f32: fp32 matrix products per plane, float64 accumulation):
+def _graph_gradients(bufs, k, Tc, stacks, schedule, cin, pos, need_Tc, need_val, need_t2=False):
+    """(dT_c, d fwd_val, d T_2) of a learned-graph backward pass from what the cell launches left in ``bufs`` (module docstring), per width group
+    (index 0: narrow inputs, 1: 16-column inputs), in the kernels' column order [H (16) | X (cin) | 0]; W's rows are re-ordered to match.  d T_2
+    (order 3) is the same product as d fwd_val on the third slabs' gradients, its partials in the same buffer.  The sums over cells and samples
+    run in ``graph_grad`` / ``mix_grad`` (stc_graph_grad_f32 / stc_mix_grad_f32: fp32 matrix products per plane, float64 accumulation):
       d fwd_val = sum_cells [dZ1g x Z0 + dZ1c x Z0c]                                      (every cell of a width at once)
       dT_c[c, d] = < W[(ks, c)], Q_ks[c, :, d, :] >,  Q_ks = Z_ks^T . dY                  (per parameter set and convolution)."""
-    B, N, C = dims
-    Kc = Tc.shape[0]
+    (B, N, C), Ks, counts, Kc = bufs.dims, bufs.Ks, bufs.counts, Tc.shape[0]
     # every product of the pass leaves its float64 partials in ONE (chunks, total) buffer, side by side, and one sum adds them all: per
     # product that was an allocation, a reduction and -- for dT_c -- a stack, three weight copies and an einsum of its own (~100 launches of a
     # few microseconds per step at the SF shape)
     graph_jobs = []                                               # (A, B, cells): dGs^T pieces, then (order 3) as many d T_2 pieces
-    for want, g, c in ((need_val, 1, 0), (need_t2, 3, 2)):
-        if want:
-            for w in (0, 1):
-                if counts[w]:
-                    graph_jobs += [(dslab[w][g], slabs[w][1], counts[w]), (dslab[w][c], slabs[w][2], counts[w])]
+    for want, dZg, dZc in ((need_val, bufs.dZ1g, bufs.dZ1c), (need_t2, bufs.dZ2g, bufs.dZ2c)):
+        for w in (w for w in (0, 1) if want and counts[w]):
+            graph_jobs += [(dZg[w], bufs.Z0[w], counts[w]), (dZc[w], bufs.Z0c[w], counts[w])]
     classes = {}                                                  # (width group, convolution) -> [(slab 0, slab 1, W, dY, first cell, step, cells)]
     dT_direct = []                                                # dT_c pieces formed directly on the matrix cores (stc_mix_dt_f32)
     if need_Tc:
@@ -295,26 +302,21 @@ def _graph_gradients(k, Tc, Ks, stacks, schedule, cin, pos, counts, dims, slabs,
             where = [pos[j][1] for j in cells]
             step = where[1] - where[0] if len(where) > 1 else 1
             # per convolution: (its Ks slabs, W, dY)
-            operands = (((slabs[w][1], slabs[w][0]) + ((slabs[w][4],) if Ks == 3 else ()), Wg, dyg[w]),
-                        ((slabs[w][2], slabs[w][3]) + ((slabs[w][5],) if Ks == 3 else ()), Wc, dyc[w]))
+            operands = (((bufs.Z0[w], bufs.Zg[w]) + ((bufs.Zg2[w],) if Ks == 3 else ()), Wg, bufs.dYg[w]),
+                        ((bufs.Z0c[w], bufs.Z1c[w]) + ((bufs.Z2c[w],) if Ks == 3 else ()), Wc, bufs.dYc[w]))
             if step < 1 or any(b_ - a_ != step for a_, b_ in zip(where, where[1:])):
                 # (a schedule STCGNN never builds: the set's cells are not evenly spaced inside their width group -- gather them)
                 pick = lambda t: torch.stack([t[i] for i in where])
                 operands = tuple((tuple(pick(s) for s in ss), W, pick(dY)) for ss, W, dY in operands)
                 first, step = 0, 1
             for conv, (ss, W, dY) in enumerate(operands):
-                s0 = ss[0]
-                LP, Ho, cw = s0.shape[-1], W.shape[1], cin[cells[0]]
+                LP, Ho, cw = ss[0].shape[-1], W.shape[1], cin[cells[0]]
                 if step == 1 and hasattr(k, 'mix_dT') and k.mix_dT_supported(Ks, Kc, C, LP, Ho):
                     # the set's cells are consecutive planes of their slabs: dT_c = sum over their rows of U_c . dY^T in ONE launch on tiles of
                     # floor(16 / C) nodes (U_c = [Z_0 | Z_1] . W_c re-formed inside) -- instead of Ks products Q = Z^T . dY with float64
                     # partials, their sum and a contraction with W per class (0.44 + ~0.2 ms of the 4.65 ms learned-graph SF step)
-                    n = len(cells)
-                    Wv = W.view(Ks, Kc, cw + H16, Ho)
-                    Wp = W.new_zeros(Ks, Kc, LP, Ho)                 # W's rows in the slabs' column order [H (16) | X (cin) | 0]
-                    Wp[:, :, :H16] = Wv[:, :, cw:]
-                    Wp[:, :, H16:H16 + cw] = Wv[:, :, :cw]
-                    rows = n * B * N
+                    n, rows = len(cells), len(cells) * B * N
+                    Wp = _slab_order(W, Ks, Kc, cw, LP)
                     piece = Tc.new_empty(Kc, C, C)
                     k.mix_dT([s[first:first + n].view(rows, C, LP) for s in ss], Wp.view(Ks * Kc * LP, Ho),
                              dY[first:first + n].view(rows, C, Ho), piece)
@@ -348,14 +350,11 @@ def _graph_gradients(k, Tc, Ks, stacks, schedule, cin, pos, counts, dims, slabs,
         dT += torch.stack(dT_direct).sum(0)
     off = 0
     for (w, cw, conv), es in classes.items():
-        LP, Ho, L = es[0][0][0].shape[-1], es[0][1].shape[1], cw + H16
+        LP, Ho = es[0][0][0].shape[-1], es[0][1].shape[1]
         size = len(es) * Ks * block(es[0][0][0], es[0][2])
         Q = sums[off:off + size].view(len(es), Ks, C, LP, C, Ho)
         off += size
-        Wv = torch.stack([e[1] for e in es]).view(len(es), Ks, Kc, L, Ho)
-        Wp = Wv.new_zeros(len(es), Ks, Kc, LP, Ho)              # W's rows in the slabs' column order [H (16) | X (cin) | 0]
-        Wp[..., :H16, :] = Wv[..., cw:, :]
-        Wp[..., H16:H16 + cw, :] = Wv[..., :cw, :]
+        Wp = _slab_order(torch.stack([e[1] for e in es]), Ks, Kc, cw, LP)
         # sum_{p,s,l,o} Q[p,s,c,l,d,o] W[p,s,k,l,o] as a product and a sum (as an einsum: a float64 GEMM with a 50-element result, 190 us)
         dT += (Q[:, :, None] * Wp.double()[:, :, :, None, :, None, :]).sum((0, 1, 4, 6))
     flat32 = lambda g: None if g is None else g.to(Tc.dtype).reshape(-1)

@@ -136,6 +136,28 @@ def test_one_cell_step_with_a_dense_graph_at_order_3(N, C, cin, B, splits, bias)
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('N,C,cin', [(37, 8, 3), (100, 5, 16)])
+def test_the_two_matrix_streams_of_the_dense_product_are_order_identical(N, C, cin):
+    """The dense aggregation runs both matrices through ONE tile product (same tile geometry, same masks, one accumulator chain per matrix in
+    the same order): with ``graph2`` carrying the first matrix's own values, the forward's split form leaves Zg2 bitwise equal to Zg and Zc2
+    to Zc (N neither a multiple of 16 nor of 4 with a narrow input; the SF shape with the wide one)."""
+    from stc_hip._lib import HipKernels
+    hip = HipKernels()
+    dev = torch.device('cuda')
+    B, splits = 2, 2
+    t = _inputs(B, N, C, cin, seed=N + C + cin, bias=True, K=3)
+    buf, _ = _buffers(B, N, C, cin, torch.float32, hip, K=3)
+    op = dense_operand(_dense_gs(N, seed=N).to(dev))
+    d = {n: v.to(dev) for n, v in t.items()}
+    b = {n: torch.full_like(v, float('nan')).to(dev) for n, v in buf.items()}
+    hip.cell_small_fwd(op.fwd_rowptr, op.fwd_colidx, op.fwd_val, d['X'], d['H'], d['Tc'], d['Wg'], d['bg'], d['Wc'], d['bc'], b['U'], b['R'], b['Cand'],
+                       b['Hnew'], b['RH'], b['Zg'], b['Zc'], splits=splits, graph2=(op.fwd_rowptr, op.fwd_colidx, op.fwd_val), Zg2=b['Zg2'], Zc2=b['Zc2'])
+    for name in ('Zg', 'Zc'):
+        assert bool(torch.isfinite(b[name]).all()), name
+        assert torch.equal(b[name + '2'], b[name]), f'{name}2 differs from {name} in {int((b[name + "2"] != b[name]).sum())} elements'
+
+
+@pytest.mark.gpu
 def test_refusals_of_the_dense_form_at_order_3():
     """Phase 0 (one workgroup per sample) with a dense graph at Ks = 3: STC_EUNSUPPORTED; a second graph of other than n * n values beside a dense
     first one: STC_EINVAL -- and nothing is launched (the NaN-filled outputs keep their bits)."""
