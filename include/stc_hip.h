@@ -529,6 +529,8 @@ int stc_cell_cand_bwd_planar_k_f32(const float* const* Zx, const float* const* Z
  * maximum in one slot by an atomic max), at no extra pass over Y.  (Until ABI v21 the cell backward kernels took it as their gradient
  * scale; since v22 they find their gradient maxima themselves, per node.) */
 #define STC_SPMM_SUM_MAX_ADD 8
+#define STC_SPMM_SUM_BF16_MAX_ADD 5      /* addends of stc_spmm_sum_bf16 */
+#define STC_RING2_MAX_ADD 5              /* addends of stc_ring2_sum_f32; interior addends of stc_ring2_chain_f32 */
 int stc_spmm_sum_f32(const int32_t* rowptr, const int32_t* colidx, const float* val,
                      const int32_t* blk_ptr, const int32_t* blk_cols, const float* blk_vals,
                      int32_t n_rows, int32_t n_cols, const float* X, const float* X2, float alpha,

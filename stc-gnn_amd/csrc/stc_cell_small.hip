@@ -27,7 +27,6 @@
 // Projections are project-then-mix:  V_kc = sum_ks Z_ks . W[(ks,kc,:)],  Y[(n,c')] = V_0 + sum_{kc>=1} sum_c T_kc[c,c'] V_kc[(n,c)] + b,
 // on v_mfma_f32_16x16x4_f32 (fp32 operands and accumulator: an fmaf chain per element, no split format).  A row tile = the C rows of
 // floor(16 / C) whole nodes, so the category mix stays inside a tile -- and is itself four matrix instructions on the accumulators (build_mix).
-#include <atomic>
 
 #include "stc_common.h"
 
@@ -1059,23 +1058,10 @@ int xq_of(int cin) { return cin == SC_H ? 4 : (cin >= 1 && cin <= 4 ? 1 : 0); }
 size_t graph_lds_bytes(int N, int nnz) { return (size_t)(((N + 4) & ~3) + 2 * ((nnz + 3) & ~3)) * 4; }
 constexpr size_t SC_LDS_BUDGET = 156 * 1024;     // of the 160 KB of a compute unit
 
-// Raise a kernel's dynamic-LDS cap only when a launch needs more than it was already granted ON THE CURRENT DEVICE (the attribute belongs to
-// the device's copy of the function; the attribute call costs microseconds, a launch here is tens of them).  Devices beyond the table are
-// granted on every launch.
-constexpr int SC_MAX_DEVICES = 16;
-struct Grants { std::atomic<size_t> per_device[SC_MAX_DEVICES]; };
-template <class K>
-hipError_t allow_lds_once(K kern, size_t bytes, Grants& grants) {
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-    std::atomic<size_t>* granted = dev >= 0 && dev < SC_MAX_DEVICES ? &grants.per_device[dev] : nullptr;
-    if (granted && bytes <= granted->load(std::memory_order_relaxed)) return hipSuccess;
-    const hipError_t e = stc::allow_lds(kern, bytes);
-    if (e == hipSuccess && granted) granted->store(bytes, std::memory_order_relaxed);
-    return e;
-}
-Grants g_granted[2][2][4];                       // [direction][wide input][mode]
-Grants g_granted3[2][2];                         // order 3, backward: [wide input][dense graph]
+// the dynamic-LDS cap of each kernel is raised when a launch needs more than it was granted (stc::allow_lds_once)
+using stc::allow_lds_once;
+stc::Grants g_granted[2][2][4];                  // [direction][wide input][mode]
+stc::Grants g_granted3[2][2];                    // order 3, backward: [wide input][dense graph]
 
 }  // namespace
 

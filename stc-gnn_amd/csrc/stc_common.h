@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -41,6 +42,22 @@ inline hipError_t allow_lds(K kernel, size_t bytes) {
     if (bytes <= 48 * 1024) return hipSuccess;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
+// Raise a kernel's dynamic-LDS cap only when a launch needs more than it was already granted ON THE CURRENT DEVICE (the attribute belongs to
+// the device's copy of the function; the attribute call costs microseconds, a launch tens of them at most).  One Grants per kernel
+// instantiation, static storage (zero: nothing granted).  Devices beyond the table are granted on every launch.
+constexpr int kMaxGrantDevices = 16;
+struct Grants { std::atomic<size_t> per_device[kMaxGrantDevices]; };
+template <class K>
+inline hipError_t allow_lds_once(K kern, size_t bytes, Grants& grants) {
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+    std::atomic<size_t>* granted = dev >= 0 && dev < kMaxGrantDevices ? &grants.per_device[dev] : nullptr;
+    if (granted && bytes <= granted->load(std::memory_order_relaxed)) return hipSuccess;
+    const hipError_t e = allow_lds(kern, bytes);
+    if (e == hipSuccess && granted) granted->store(bytes, std::memory_order_relaxed);
+    return e;
 }
 
 // Workgroups of `kernel` that are resident at once on the whole device (occupancy API x CU count).

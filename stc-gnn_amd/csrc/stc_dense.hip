@@ -14,7 +14,7 @@
 // Bound by the fp32 matrix pipe (32 cycles per MFMA) -- when the launch fills the chip: the passes over the rows of S are workgroups of
 // their own (blockIdx.y), and a pass is 128, 64 or 32 rows, the largest that still gives two workgroups per compute unit (BASELINE
 // configuration 2, batch 32 x 4 column groups x N = 200: 128 workgroups of two passes each took 34 us, half the chip idle).
-#include "stc_common.h"
+#include "stc_spmm_host.h"
 
 namespace {
 
@@ -122,12 +122,10 @@ __global__ __launch_bounds__(DA_THREADS) void dense_agg_kernel(
 
 extern "C" int stc_dense_agg_f32(const float* S, int32_t n_rows, int32_t n_cols, const float* X, const float* Y0, float* Y,
                                  int32_t batch, int32_t F, float alpha, float beta, void* stream) {
-    STC_REQUIRE(n_rows >= 0 && n_cols >= 0 && batch >= 0 && F >= 0, STC_EINVAL,
-                "stc_dense_agg_f32: negative size (n_rows=%d n_cols=%d batch=%d F=%d)", n_rows, n_cols, batch, F);
-    if (n_rows == 0 || batch == 0 || F == 0) return STC_OK;
-    STC_REQUIRE(S && Y && (n_cols == 0 || X), STC_EINVAL, "stc_dense_agg_f32: null S / X / Y");
-    STC_REQUIRE(beta == 0.f || Y0, STC_EINVAL, "stc_dense_agg_f32: beta != 0 needs Y0");
-    STC_REQUIRE(X != Y, STC_EINVAL, "stc_dense_agg_f32: X must not alias Y");
+    const stc::Plain p{n_rows, n_cols, batch, F, X, Y0, Y, beta};
+    // any F at any alignment (4-byte loads of X); batch is folded into grid.x: its limit is the workgroup count below
+    if (int rc = stc::check_plain("stc_dense_agg_f32", p, S && Y && (n_cols == 0 || X), 0, 0, 0)) return rc;
+    if (p.empty()) return STC_OK;
     STC_REQUIRE((long long)batch * n_rows * F < (1ll << 40) && (long long)n_rows * n_cols < (1ll << 31), STC_ELIMIT, "stc_dense_agg_f32: operand too large");
     const int col_groups = (F + 16 * DA_WAVES - 1) / (16 * DA_WAVES);
     const long long blocks = (long long)batch * col_groups;
@@ -144,6 +142,5 @@ extern "C" int stc_dense_agg_f32(const float* S, int32_t n_rows, int32_t n_cols,
                                 : (vec ? dense_agg_kernel<true, 2> : dense_agg_kernel<false, 2>);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks, passes), dim3(DA_THREADS), 0, static_cast<hipStream_t>(stream),
                        S, n_rows, n_cols, X, Y0, Y, F, col_groups, alpha, beta);
-    STC_LAUNCH_CHECK("stc_dense_agg_f32 launch");
-    return STC_OK;
+    return stc::launched("stc_dense_agg_f32 launch");
 }

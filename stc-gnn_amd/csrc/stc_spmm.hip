@@ -21,13 +21,11 @@
 // Epilogues: the GRU blend of the forward (EP_BLEND: Cand = tanh(A + S.Bm), Hnew = (1-U) H + U Cand, reference STC_GNN.py:76-78) and the
 // state-gradient sums of the backward (EP_SUM / EP_SUM2: Y = sum of addend planes + alpha S.(X [+ X2]), optionally with the blend backward
 // dY = Y U (1 - Cand^2) and the launch's max |Y| on the way) run on the accumulators, so neither intermediate is written to HBM.
-#include "stc_common.h"
-
-#ifndef STC_BCSR_DEFAULT_BLOCKS
-#define STC_BCSR_DEFAULT_BLOCKS 2
-#endif
+#include "stc_spmm_host.h"
 
 namespace {
+
+using stc::GraphArgs;
 
 constexpr int SPMM_THREADS = 256;
 constexpr int SPMM_WAVES = SPMM_THREADS / 64;
@@ -589,11 +587,6 @@ int next_pow2(int v) {
     return p;
 }
 
-struct GraphArgs {      // either form of the same matrix; BCSR is used when blk_ptr is given
-    const int32_t *rowptr, *colidx; const float* val;
-    const int32_t *blk_ptr, *blk_cols; const float* blk_vals;
-};
-
 template <int MODE>
 int launch_vector(const char* who, const GraphArgs& g, int n_rows, int n_cols, const float* X, int batch, int F,
                   const EpiArgs& ep, hipStream_t s) {
@@ -601,7 +594,7 @@ int launch_vector(const char* who, const GraphArgs& g, int n_rows, int n_cols, c
     const float4* X4 = reinterpret_cast<const float4*>(X);
     if (g.blk_ptr) {
         const int n_blocks = (n_rows + BR - 1) / BR;
-        constexpr int blocks = STC_BCSR_DEFAULT_BLOCKS;      // row blocks per workgroup (2: two waves share a block; 4 and 8 measured slower)
+        constexpr int blocks = 2;      // row blocks per workgroup: two waves share a block, each covers every other column block of 64*VPT float4 (4 and 8 measured slower)
         const int n_tiles = (n_blocks + blocks - 1) / blocks;
         const int per = (n_tiles + stc::kNumXcd - 1) / stc::kNumXcd;
         const dim3 grid(per * stc::kNumXcd, batch), block(SPMM_THREADS);
@@ -610,17 +603,11 @@ int launch_vector(const char* who, const GraphArgs& g, int n_rows, int n_cols, c
         // epilogue (sum / blend forms) the extra live registers cost what the pipelining gains (equal or slower): old loop.
         // (measured again for the state-gradient sum with ONE gathered operand, which is what the cell graph launches now: 27.1 vs 27.3 ms)
         const bool pipe = MODE == EP_PLAIN && (ep.Y0 == nullptr || ep.beta == 0.f);
-#define STC_BCSR_GO(VPT_, BLK_) do { if (pipe && BLK_ == 2 && F4 % (128 * VPT_) == 0) hipLaunchKernelGGL((spmm_bcsr_kernel<VPT_, MODE, 2, (MODE == EP_PLAIN), (MODE == EP_PLAIN)>), grid, block, 0, s, g.blk_ptr, g.blk_cols, g.blk_vals, \
-                                                   n_rows, n_cols, X4, F4, n_blocks, n_tiles, ep); \
-                                     else hipLaunchKernelGGL((spmm_bcsr_kernel<VPT_, MODE, BLK_, 0, 0>), grid, block, 0, s, g.blk_ptr, g.blk_cols, g.blk_vals, \
-                                                   n_rows, n_cols, X4, F4, n_blocks, n_tiles, ep); } while (0)
-        if (blocks == 2) {            // two waves per block: each covers every other column block of 64*VPT float4
-            if (F4 <= 128) STC_BCSR_GO(1, 2); else if (F4 <= 256) STC_BCSR_GO(2, 2); else STC_BCSR_GO(4, 2);
-        } else if (blocks == 4) {
-            if (F4 <= 64) STC_BCSR_GO(1, 4); else if (F4 <= 128) STC_BCSR_GO(2, 4); else STC_BCSR_GO(4, 4);
-        } else {
-            if (F4 <= 64) STC_BCSR_GO(1, 8); else if (F4 <= 128) STC_BCSR_GO(2, 8); else STC_BCSR_GO(4, 8);
-        }
+#define STC_BCSR_GO(VPT_) do { if (pipe && F4 % (128 * VPT_) == 0) hipLaunchKernelGGL((spmm_bcsr_kernel<VPT_, MODE, blocks, (MODE == EP_PLAIN), (MODE == EP_PLAIN)>), grid, block, 0, s, g.blk_ptr, g.blk_cols, g.blk_vals, \
+                                             n_rows, n_cols, X4, F4, n_blocks, n_tiles, ep); \
+                               else hipLaunchKernelGGL((spmm_bcsr_kernel<VPT_, MODE, blocks, 0, 0>), grid, block, 0, s, g.blk_ptr, g.blk_cols, g.blk_vals, \
+                                             n_rows, n_cols, X4, F4, n_blocks, n_tiles, ep); } while (0)
+        if (F4 <= 128) STC_BCSR_GO(1); else if (F4 <= 256) STC_BCSR_GO(2); else STC_BCSR_GO(4);
 #undef STC_BCSR_GO
     } else {
         const int n_tiles = (n_rows + SPMM_ROWS - 1) / SPMM_ROWS;
@@ -633,20 +620,22 @@ int launch_vector(const char* who, const GraphArgs& g, int n_rows, int n_cols, c
         else
             hipLaunchKernelGGL((spmm_wave_row_kernel<4, MODE>), grid, block, 0, s, g.rowptr, g.colidx, g.val, n_rows, n_cols, X4, F4, n_tiles, ep);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return stc::hip_status(e, who);
-    return STC_OK;
+    return stc::launched(who);
 }
 
-int check_fused(const char* who, const GraphArgs& g, int n_rows, int n_cols, const float* X, const float* Y0,
-                int batch, int C, int cin, int h, int pad) {
-    STC_REQUIRE(n_rows >= 0 && n_cols >= 0 && batch >= 0 && C >= 1 && cin >= 0 && h >= 1 && pad >= 0, STC_EINVAL, "%s: bad sizes", who);
-    STC_REQUIRE((cin + h + pad) % 4 == 0, STC_EINVAL, "%s: row width cin+h+pad = %d must be a multiple of 4", who, cin + h + pad);
-    STC_REQUIRE((long long)C * (cin + h + pad) >= 64, STC_ELIMIT, "%s: node row of %d floats is too narrow for the vector kernels", who, C * (cin + h + pad));
-    STC_REQUIRE(batch <= 65535, STC_ELIMIT, "%s: batch %d > 65535 (grid.y)", who, batch);
-    if (n_rows == 0 || batch == 0) return STC_OK;
+EpiArgs plain_epi(const float* Y0, float* Y, float alpha, float beta) {      // Y = alpha S.X + beta Y0
+    EpiArgs ep{};
+    ep.Y0 = reinterpret_cast<const float4*>(Y0); ep.Y = reinterpret_cast<float4*>(Y); ep.alpha = alpha; ep.beta = beta;
+    return ep;
+}
+
+// state rows on the fp32 vector kernels: X the gathered operand, Y0 the other plane of the same shape (A, or the result of a sum)
+int check_fused(const char* who, const GraphArgs& g, int n_rows, int n_cols, const float* X, const float* Y0, int batch, int C, int h) {
     // the column / value arrays may be null for a graph without edges (pointer arrays all zero: they are never read)
-    STC_REQUIRE(g.blk_ptr || g.rowptr, STC_EINVAL, "%s: neither graph form given", who);
+    if (int rc = stc::check_state_rows(who, n_rows, batch, C, h, g.blk_ptr || g.rowptr)) return rc;
+    STC_REQUIRE(n_cols >= 0, STC_EINVAL, "%s: bad sizes", who);
+    STC_REQUIRE((long long)C * h >= 64, STC_ELIMIT, "%s: node row of %d floats is too narrow for the vector kernels", who, C * h);
+    if (n_rows == 0 || batch == 0) return STC_OK;
     STC_REQUIRE(X && Y0 && n_cols > 0, STC_EINVAL, "%s: null X / Y0", who);
     STC_REQUIRE(stc::aligned16(X) && stc::aligned16(Y0), STC_EALIGN, "%s: X / Y0 must be 16-byte aligned", who);
     return STC_OK;
@@ -658,48 +647,33 @@ extern "C" int stc_csr_spmm_f32(const int32_t* rowptr, const int32_t* colidx, co
                                 int32_t n_rows, int32_t n_cols,
                                 const float* X, const float* Y0, float* Y,
                                 int32_t batch, int32_t F, float alpha, float beta, void* stream) {
-    STC_REQUIRE(n_rows >= 0 && n_cols >= 0 && batch >= 0 && F >= 0, STC_EINVAL,
-                "stc_csr_spmm_f32: negative size (n_rows=%d n_cols=%d batch=%d F=%d)", n_rows, n_cols, batch, F);
-    if (n_rows == 0 || batch == 0 || F == 0) return STC_OK;
-    STC_REQUIRE(rowptr && Y, STC_EINVAL, "stc_csr_spmm_f32: null rowptr/Y");
-    STC_REQUIRE(n_cols > 0 && X, STC_EINVAL, "stc_csr_spmm_f32: null X or n_cols == 0 with rows to produce");
-    // colidx/val may be null for a graph without edges (rowptr all zero): they are then never read
-    STC_REQUIRE(beta == 0.f || Y0, STC_EINVAL, "stc_csr_spmm_f32: beta != 0 needs Y0");
-    STC_REQUIRE(batch <= 65535, STC_ELIMIT, "stc_csr_spmm_f32: batch %d > 65535 (grid.y)", batch);
-    STC_REQUIRE(X != Y, STC_EINVAL, "stc_csr_spmm_f32: X must not alias Y");
+    const stc::Plain p{n_rows, n_cols, batch, F, X, Y0, Y, beta};
+    // colidx/val may be null for a graph without edges (rowptr all zero): they are then never read.  Any F at any alignment: the generic kernel below
+    if (int rc = stc::check_plain("stc_csr_spmm_f32", p, rowptr && X && Y && n_cols > 0, 0, 0, 0)) return rc;
+    if (p.empty()) return STC_OK;
+    if (int rc = stc::check_batch("stc_csr_spmm_f32", batch)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
 
     const bool vec = (F % 4 == 0) && stc::aligned16(X) && stc::aligned16(Y) && (Y0 == nullptr || stc::aligned16(Y0)) && F >= 64;
     if (vec) {
-        EpiArgs ep{};
-        ep.Y0 = reinterpret_cast<const float4*>(Y0);
-        ep.Y = reinterpret_cast<float4*>(Y);
-        ep.alpha = alpha;
-        ep.beta = beta;
         const GraphArgs g{rowptr, colidx, val, nullptr, nullptr, nullptr};
-        return launch_vector<EP_PLAIN>("stc_csr_spmm_f32 launch", g, n_rows, n_cols, X, batch, F, ep, s);
+        return launch_vector<EP_PLAIN>("stc_csr_spmm_f32 launch", g, n_rows, n_cols, X, batch, F, plain_epi(Y0, Y, alpha, beta), s);
     }
     const int lanes = next_pow2(F) < SPMM_THREADS ? next_pow2(F) : SPMM_THREADS;
     const int rows_per_block = SPMM_THREADS / lanes;
     dim3 grid((n_rows + rows_per_block - 1) / rows_per_block, batch), block(SPMM_THREADS);
     hipLaunchKernelGGL(spmm_generic_kernel, grid, block, 0, s, rowptr, colidx, val, n_rows, n_cols, X, Y0, Y, F, alpha, beta, lanes);
-    STC_LAUNCH_CHECK("stc_csr_spmm_f32 launch");
-    return STC_OK;
+    return stc::launched("stc_csr_spmm_f32 launch");
 }
 
 extern "C" int stc_bcsr_spmm_f32(const int32_t* blk_ptr, const int32_t* blk_cols, const float* blk_vals,
                                  int32_t n_rows, int32_t n_cols,
                                  const float* X, const float* Y0, float* Y,
                                  int32_t batch, int32_t F, float alpha, float beta, void* stream) {
-    STC_REQUIRE(n_rows >= 0 && n_cols >= 0 && batch >= 0 && F >= 0, STC_EINVAL, "stc_bcsr_spmm_f32: negative size");
-    if (n_rows == 0 || batch == 0 || F == 0) return STC_OK;
-    STC_REQUIRE(blk_ptr && X && Y, STC_EINVAL, "stc_bcsr_spmm_f32: null pointer");
-    STC_REQUIRE(beta == 0.f || Y0, STC_EINVAL, "stc_bcsr_spmm_f32: beta != 0 needs Y0");
-    STC_REQUIRE(X != Y, STC_EINVAL, "stc_bcsr_spmm_f32: X must not alias Y");
-    STC_REQUIRE(F % 4 == 0 && F >= 4, STC_EINVAL, "stc_bcsr_spmm_f32: F=%d must be a positive multiple of 4", F);
-    STC_REQUIRE(stc::aligned16(X) && stc::aligned16(Y) && (!Y0 || stc::aligned16(Y0)), STC_EALIGN,
-                "stc_bcsr_spmm_f32: X / Y / Y0 must be 16-byte aligned");
-    STC_REQUIRE(batch <= 65535, STC_ELIMIT, "stc_bcsr_spmm_f32: batch %d > 65535 (grid.y)", batch);
+    const stc::Plain p{n_rows, n_cols, batch, F, X, Y0, Y, beta};
+    if (int rc = stc::check_plain("stc_bcsr_spmm_f32", p, blk_ptr && X && Y, 4, 4, STC_EINVAL)) return rc;
+    if (p.empty()) return STC_OK;
+    if (int rc = stc::check_batch("stc_bcsr_spmm_f32", batch)) return rc;
     const int F4 = F / 4;
     if (F4 <= 16 && (F4 & (F4 - 1)) == 0) {            // narrow rows (<= 256 bytes): several row blocks per wave
         const int n_blocks = (n_rows + BR - 1) / BR;
@@ -710,16 +684,10 @@ extern "C" int stc_bcsr_spmm_f32(const int32_t* blk_ptr, const int32_t* blk_cols
         switch (F4) { case 1: STC_NARROW_GO(1); break; case 2: STC_NARROW_GO(2); break; case 4: STC_NARROW_GO(4); break;
                       case 8: STC_NARROW_GO(8); break; default: STC_NARROW_GO(16); break; }
 #undef STC_NARROW_GO
-        STC_LAUNCH_CHECK("stc_bcsr_spmm_f32 (narrow rows) launch");
-        return STC_OK;
+        return stc::launched("stc_bcsr_spmm_f32 (narrow rows) launch");
     }
-    EpiArgs ep{};
-    ep.Y0 = reinterpret_cast<const float4*>(Y0);
-    ep.Y = reinterpret_cast<float4*>(Y);
-    ep.alpha = alpha;
-    ep.beta = beta;
     const GraphArgs g{nullptr, nullptr, nullptr, blk_ptr, blk_cols, blk_vals};
-    return launch_vector<EP_PLAIN>("stc_bcsr_spmm_f32 launch", g, n_rows, n_cols, X, batch, F, ep, static_cast<hipStream_t>(stream));
+    return launch_vector<EP_PLAIN>("stc_bcsr_spmm_f32 launch", g, n_rows, n_cols, X, batch, F, plain_epi(Y0, Y, alpha, beta), static_cast<hipStream_t>(stream));
 }
 
 extern "C" int stc_spmm_blend_fwd_f32(const int32_t* rowptr, const int32_t* colidx, const float* val,
@@ -730,8 +698,7 @@ extern "C" int stc_spmm_blend_fwd_f32(const int32_t* rowptr, const int32_t* coli
                                       float* copy1, int32_t copy1_ld, int32_t copy1_off,
                                       int32_t batch, int32_t C, int32_t h, void* stream) {
     const GraphArgs g{rowptr, colidx, val, blk_ptr, blk_cols, blk_vals};
-    STC_REQUIRE(h == 16, STC_EUNSUPPORTED, "stc_spmm_blend_fwd_f32: hidden width %d (the blend epilogue is built for 16)", h);
-    if (int rc = check_fused("stc_spmm_blend_fwd_f32", g, n_rows, n_cols, Bm, A, batch, C, 0, h, 0)) return rc;
+    if (int rc = check_fused("stc_spmm_blend_fwd_f32", g, n_rows, n_cols, Bm, A, batch, C, h)) return rc;
     if (n_rows == 0 || batch == 0) return STC_OK;
     STC_REQUIRE(U && H && Hnew, STC_EINVAL, "stc_spmm_blend_fwd_f32: null pointer");      // (Cand may be null: not stored)
     STC_REQUIRE(stc::aligned16(U) && stc::aligned16(H) && (!Cand || stc::aligned16(Cand)) && stc::aligned16(Hnew), STC_EALIGN,
@@ -765,9 +732,9 @@ extern "C" int stc_spmm_sum_f32(const int32_t* rowptr, const int32_t* colidx, co
     const GraphArgs g{rowptr, colidx, val, blk_ptr, blk_cols, blk_vals};
     STC_REQUIRE(h == 16, STC_EUNSUPPORTED, "stc_spmm_sum_f32: hidden width %d (built for 16)", h);
     STC_REQUIRE(!amax || n_amax >= 1, STC_EINVAL, "stc_spmm_sum_f32: amax with %d slots", n_amax);
-    STC_REQUIRE(n_add >= 0 && n_add <= STC_SPMM_SUM_MAX_ADD && (n_add == 0 || (add && add_ld && add_off)), STC_EINVAL,
-                "stc_spmm_sum_f32: 0..%d addends, got %d", STC_SPMM_SUM_MAX_ADD, n_add);
-    if (int rc = check_fused("stc_spmm_sum_f32", g, n_rows, n_cols, X, Y, batch, C, 0, h, 0)) return rc;      // (Y checked as the aligned "Y0" operand)
+    if (int rc = stc::check_addend_count("stc_spmm_sum_f32", "addend", n_add, 0, STC_SPMM_SUM_MAX_ADD, STC_EINVAL)) return rc;
+    STC_REQUIRE(n_add == 0 || (add && add_ld && add_off), STC_EINVAL, "stc_spmm_sum_f32: null list of addends, ld or off");
+    if (int rc = check_fused("stc_spmm_sum_f32", g, n_rows, n_cols, X, Y, batch, C, h)) return rc;      // (Y checked as the aligned "Y0" operand)
     if (n_rows == 0 || batch == 0) return STC_OK;
     STC_REQUIRE(X != Y && X2 != Y, STC_EINVAL, "stc_spmm_sum_f32: Y must not alias a gathered operand");
     STC_REQUIRE(!X2 || stc::aligned16(X2), STC_EALIGN, "stc_spmm_sum_f32: X2 not 16-byte aligned");
@@ -775,16 +742,15 @@ extern "C" int stc_spmm_sum_f32(const int32_t* rowptr, const int32_t* colidx, co
     ep.Y = reinterpret_cast<float4*>(Y);
     ep.C = C; ep.L = h; ep.cin = 0; ep.h = h;
     ep.X2 = reinterpret_cast<const float4*>(X2);
-    STC_REQUIRE(!dY || (U && Cand && stc::aligned16(U) && stc::aligned16(Cand) && stc::aligned16(dY) && dY != Y), STC_EINVAL,
-                "stc_spmm_sum_f32: dY needs U and Cand (16-byte aligned, not aliasing Y)");
+    if (int rc = stc::check_dy("stc_spmm_sum_f32", dY, U, Cand, Y)) return rc;
     ep.gU = U; ep.gCand = Cand; ep.dYout = dY;
     ep.amax = reinterpret_cast<unsigned*>(amax); ep.n_amax = n_amax;
     ep.alpha = alpha;
     ep.n_add = n_add;
+    if (int rc = stc::check_addends("stc_spmm_sum_f32", "addend", add, n_add, Y, nullptr)) return rc;
     for (int i = 0; i < n_add; ++i) {
-        STC_REQUIRE(add[i] && add_off[i] >= 0 && add_off[i] + h <= add_ld[i] && ((add_ld[i] | add_off[i]) & 3) == 0 && stc::aligned16(add[i]), STC_EINVAL,
-                    "stc_spmm_sum_f32: addend %d (ld %d, off %d) must be non-null, 16-byte aligned, with ld and off multiples of 4", i, add_ld[i], add_off[i]);
-        STC_REQUIRE(add[i] != Y, STC_EINVAL, "stc_spmm_sum_f32: Y must not alias an addend");
+        STC_REQUIRE(add_off[i] >= 0 && add_off[i] + h <= add_ld[i] && ((add_ld[i] | add_off[i]) & 3) == 0, STC_EINVAL,
+                    "stc_spmm_sum_f32: addend %d (ld %d, off %d): columns [off, off+%d) of rows of ld floats, ld and off multiples of 4", i, add_ld[i], add_off[i], h);
         ep.add[i] = add[i]; ep.add_ld[i] = add_ld[i]; ep.add_off[i] = add_off[i]; ep.add_scale[i] = add_scale ? add_scale[i] : 1.f;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -802,6 +768,5 @@ extern "C" int stc_csr_sddmm_f32(const int32_t* rowptr, const int32_t* colidx,
     STC_REQUIRE((batch == 0 || F == 0) || (A && Bm), STC_EINVAL, "stc_csr_sddmm_f32: null A/Bm");
     hipLaunchKernelGGL(sddmm_kernel, dim3(n_rows), dim3(SPMM_THREADS), 0, static_cast<hipStream_t>(stream),
                        rowptr, colidx, n_rows, n_cols, A, Bm, out, batch, F, alpha, accumulate);
-    STC_LAUNCH_CHECK("stc_csr_sddmm_f32 launch");
-    return STC_OK;
+    return stc::launched("stc_csr_sddmm_f32 launch");
 }

@@ -14,9 +14,11 @@
 // scalar, each lane streams 16-byte pieces (8 bf16, 1 KiB per wave instruction) with 4 neighbour rows in flight, blocks
 // are remapped so each XCD walks a contiguous band of rows, output / Y0 are non-temporal.  HBM-bound: a node row of
 // C*L = 2048 bf16 is the same 4 KiB as the fp32 row of the C = 32 configuration.
-#include "stc_common.h"
+#include "stc_spmm_host.h"
 
 namespace {
+
+using stc::GraphArgs;
 
 constexpr int SPMM_THREADS = 256;
 constexpr int SPMM_WAVES = SPMM_THREADS / 64;
@@ -69,6 +71,7 @@ struct Epi {
     const u32x4* add[5]; int n_add;
     const u32x4* gCand; u32x4* dY;
 };
+static_assert(sizeof(Epi::add) / sizeof(const u32x4*) == STC_SPMM_SUM_BF16_MAX_ADD, "the addend slots of the kernel argument are the ABI's limit");
 
 __device__ __forceinline__ void unpack8(const u32x4 v, float (&r)[8]) {
 #pragma unroll
@@ -366,25 +369,6 @@ __global__ __launch_bounds__(SPMM_THREADS) void spmm_bcsr_bf16_kernel(
     }
 }
 
-int check_common(const char* who, int n_rows, int n_cols, const void* X, const void* Y0, const void* Y,
-                 int batch, int F, float beta) {
-    STC_REQUIRE(n_rows >= 0 && n_cols >= 0 && batch >= 0 && F >= 0, STC_EINVAL, "%s: negative size (n_rows=%d n_cols=%d batch=%d F=%d)",
-                who, n_rows, n_cols, batch, F);
-    if (n_rows == 0 || batch == 0 || F == 0) return STC_OK;
-    STC_REQUIRE(X && Y && n_cols > 0, STC_EINVAL, "%s: null X / Y or n_cols == 0 with rows to produce", who);
-    STC_REQUIRE(beta == 0.f || Y0, STC_EINVAL, "%s: beta != 0 needs Y0", who);
-    STC_REQUIRE(X != Y, STC_EINVAL, "%s: X must not alias Y", who);
-    STC_REQUIRE(F % 8 == 0, STC_EINVAL, "%s: F=%d must be a multiple of 8 (16-byte pieces of bf16)", who, F);
-    STC_REQUIRE(stc::aligned16(X) && stc::aligned16(Y) && (!Y0 || stc::aligned16(Y0)), STC_EALIGN, "%s: X / Y / Y0 must be 16-byte aligned", who);
-    STC_REQUIRE(batch <= 65535, STC_ELIMIT, "%s: batch %d > 65535 (grid.y)", who, batch);
-    return STC_OK;
-}
-
-struct GraphArgs {      // either form of the same matrix; BCSR is used when blk_ptr is given
-    const int32_t *rowptr, *colidx; const float* val;
-    const int32_t *blk_ptr, *blk_cols; const float* blk_vals;
-};
-
 template <int MODE>
 int launch(const char* who, const GraphArgs& g, int n_rows, int n_cols, const void* X, int batch, int F, const Epi& ep, hipStream_t s) {
     const u32x4* X8 = reinterpret_cast<const u32x4*>(X);
@@ -410,17 +394,18 @@ int launch(const char* who, const GraphArgs& g, int n_rows, int n_cols, const vo
         else
             hipLaunchKernelGGL((spmm_wave_row_bf16_kernel<2, MODE>), grid, block, 0, s, g.rowptr, g.colidx, g.val, n_rows, n_cols, X8, F8, n_tiles, ep);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return stc::hip_status(e, who);
-    return STC_OK;
+    return stc::launched(who);
 }
 
-int check_state_rows(const char* who, const GraphArgs& g, int n_rows, int batch, int C, int h) {
-    STC_REQUIRE(h == 16, STC_EUNSUPPORTED, "%s: hidden width %d (built for 16)", who, h);
-    STC_REQUIRE(n_rows >= 0 && batch >= 0 && C >= 1, STC_EINVAL, "%s: bad sizes", who);
-    STC_REQUIRE(batch <= 65535, STC_ELIMIT, "%s: batch %d > 65535 (grid.y)", who, batch);
-    STC_REQUIRE(n_rows == 0 || batch == 0 || g.blk_ptr || g.rowptr, STC_EINVAL, "%s: neither graph form given", who);
-    return STC_OK;
+// the plain product on bf16 rows (16-byte pieces of 8 elements) on either graph form; its pointer array is checked last
+int plain_bf16(const char* who, const char* launch_who, const GraphArgs& g, const stc::Plain& p, float alpha, void* Y, void* stream) {
+    if (int rc = stc::check_plain(who, p, p.X && p.Y && p.n_cols > 0, 8, 8, STC_EINVAL)) return rc;
+    if (p.empty()) return STC_OK;
+    if (int rc = stc::check_batch(who, p.batch)) return rc;
+    STC_REQUIRE(g.rowptr || g.blk_ptr, STC_EINVAL, "%s: null rowptr / blk_ptr", who);      // colidx / val may be null for a graph without edges
+    Epi ep{};
+    ep.Y0 = reinterpret_cast<const u32x4*>(p.Y0); ep.Y = reinterpret_cast<u32x4*>(Y); ep.alpha = alpha; ep.beta = p.beta;
+    return launch<EP_PLAIN>(launch_who, g, p.n_rows, p.n_cols, p.X, p.batch, p.F, ep, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace
@@ -429,26 +414,16 @@ extern "C" int stc_csr_spmm_bf16(const int32_t* rowptr, const int32_t* colidx, c
                                  int32_t n_rows, int32_t n_cols,
                                  const void* X, const void* Y0, void* Y,
                                  int32_t batch, int32_t F, float alpha, float beta, void* stream) {
-    if (int rc = check_common("stc_csr_spmm_bf16", n_rows, n_cols, X, Y0, Y, batch, F, beta)) return rc;
-    if (n_rows == 0 || batch == 0 || F == 0) return STC_OK;
-    STC_REQUIRE(rowptr, STC_EINVAL, "stc_csr_spmm_bf16: null rowptr");      // colidx / val may be null for a graph without edges
-    Epi ep{};
-    ep.Y0 = reinterpret_cast<const u32x4*>(Y0); ep.Y = reinterpret_cast<u32x4*>(Y); ep.alpha = alpha; ep.beta = beta;
-    const GraphArgs g{rowptr, colidx, val, nullptr, nullptr, nullptr};
-    return launch<EP_PLAIN>("stc_csr_spmm_bf16 launch", g, n_rows, n_cols, X, batch, F, ep, static_cast<hipStream_t>(stream));
+    return plain_bf16("stc_csr_spmm_bf16", "stc_csr_spmm_bf16 launch", GraphArgs{rowptr, colidx, val, nullptr, nullptr, nullptr},
+                      stc::Plain{n_rows, n_cols, batch, F, X, Y0, Y, beta}, alpha, Y, stream);
 }
 
 extern "C" int stc_bcsr_spmm_bf16(const int32_t* blk_ptr, const int32_t* blk_cols, const float* blk_vals,
                                   int32_t n_rows, int32_t n_cols,
                                   const void* X, const void* Y0, void* Y,
                                   int32_t batch, int32_t F, float alpha, float beta, void* stream) {
-    if (int rc = check_common("stc_bcsr_spmm_bf16", n_rows, n_cols, X, Y0, Y, batch, F, beta)) return rc;
-    if (n_rows == 0 || batch == 0 || F == 0) return STC_OK;
-    STC_REQUIRE(blk_ptr, STC_EINVAL, "stc_bcsr_spmm_bf16: null blk_ptr");
-    Epi ep{};
-    ep.Y0 = reinterpret_cast<const u32x4*>(Y0); ep.Y = reinterpret_cast<u32x4*>(Y); ep.alpha = alpha; ep.beta = beta;
-    const GraphArgs g{nullptr, nullptr, nullptr, blk_ptr, blk_cols, blk_vals};
-    return launch<EP_PLAIN>("stc_bcsr_spmm_bf16 launch", g, n_rows, n_cols, X, batch, F, ep, static_cast<hipStream_t>(stream));
+    return plain_bf16("stc_bcsr_spmm_bf16", "stc_bcsr_spmm_bf16 launch", GraphArgs{nullptr, nullptr, nullptr, blk_ptr, blk_cols, blk_vals},
+                      stc::Plain{n_rows, n_cols, batch, F, X, Y0, Y, beta}, alpha, Y, stream);
 }
 
 extern "C" int stc_spmm_blend_fwd_bf16(const int32_t* rowptr, const int32_t* colidx, const float* val,
@@ -457,7 +432,7 @@ extern "C" int stc_spmm_blend_fwd_bf16(const int32_t* rowptr, const int32_t* col
                                        const void* U, const void* H, void* Cand, void* Hnew,
                                        int32_t batch, int32_t C, int32_t h, void* stream) {
     const GraphArgs g{rowptr, colidx, val, blk_ptr, blk_cols, blk_vals};
-    if (int rc = check_state_rows("stc_spmm_blend_fwd_bf16", g, n_rows, batch, C, h)) return rc;
+    if (int rc = stc::check_state_rows("stc_spmm_blend_fwd_bf16", n_rows, batch, C, h, g.blk_ptr || g.rowptr)) return rc;
     if (n_rows == 0 || batch == 0) return STC_OK;
     STC_REQUIRE(Bm && A && U && H && Cand && Hnew && n_cols > 0, STC_EINVAL, "stc_spmm_blend_fwd_bf16: null pointer");
     STC_REQUIRE(stc::aligned16(Bm) && stc::aligned16(A) && stc::aligned16(U) && stc::aligned16(H) && stc::aligned16(Cand) && stc::aligned16(Hnew),
@@ -477,23 +452,21 @@ extern "C" int stc_spmm_sum_bf16(const int32_t* rowptr, const int32_t* colidx, c
                                  void* Y, const void* U, const void* Cand, void* dY,
                                  int32_t batch, int32_t C, int32_t h, void* stream) {
     const GraphArgs g{rowptr, colidx, val, blk_ptr, blk_cols, blk_vals};
-    if (int rc = check_state_rows("stc_spmm_sum_bf16", g, n_rows, batch, C, h)) return rc;
-    STC_REQUIRE(n_add >= 0 && n_add <= 5 && (n_add == 0 || add), STC_EINVAL, "stc_spmm_sum_bf16: 0..5 addends, got %d", n_add);
+    if (int rc = stc::check_state_rows("stc_spmm_sum_bf16", n_rows, batch, C, h, g.blk_ptr || g.rowptr)) return rc;
+    if (int rc = stc::check_addend_count("stc_spmm_sum_bf16", "addend", n_add, 0, STC_SPMM_SUM_BF16_MAX_ADD, STC_EINVAL)) return rc;
+    STC_REQUIRE(n_add == 0 || add, STC_EINVAL, "stc_spmm_sum_bf16: null list of addends");
     if (n_rows == 0 || batch == 0) return STC_OK;
     STC_REQUIRE(X && Y && n_cols > 0, STC_EINVAL, "stc_spmm_sum_bf16: null pointer");
     STC_REQUIRE(stc::aligned16(X) && stc::aligned16(Y) && (!X2 || stc::aligned16(X2)), STC_EALIGN, "stc_spmm_sum_bf16: operands must be 16-byte aligned");
     STC_REQUIRE(X != Y && X2 != Y, STC_EINVAL, "stc_spmm_sum_bf16: Y must not alias a gathered operand");
-    STC_REQUIRE(!dY || (U && Cand && stc::aligned16(U) && stc::aligned16(Cand) && stc::aligned16(dY) && dY != Y), STC_EINVAL,
-                "stc_spmm_sum_bf16: dY needs U and Cand (16-byte aligned, not aliasing Y)");
+    if (int rc = stc::check_dy("stc_spmm_sum_bf16", dY, U, Cand, Y)) return rc;
+    if (int rc = stc::check_addends("stc_spmm_sum_bf16", "addend", add, n_add, Y, nullptr)) return rc;
     Epi ep{};
     ep.Y = reinterpret_cast<u32x4*>(Y);
     ep.X2 = reinterpret_cast<const u32x4*>(X2);
     ep.U = reinterpret_cast<const u32x4*>(U); ep.gCand = reinterpret_cast<const u32x4*>(Cand); ep.dY = reinterpret_cast<u32x4*>(dY);
     ep.n_add = n_add;
-    for (int i = 0; i < n_add; ++i) {
-        STC_REQUIRE(add[i] && stc::aligned16(add[i]) && add[i] != Y, STC_EINVAL, "stc_spmm_sum_bf16: addend %d null, misaligned or aliasing Y", i);
-        ep.add[i] = reinterpret_cast<const u32x4*>(add[i]);
-    }
+    for (int i = 0; i < n_add; ++i) ep.add[i] = reinterpret_cast<const u32x4*>(add[i]);
     hipStream_t s = static_cast<hipStream_t>(stream);
     return X2 ? launch<EP_SUM2>("stc_spmm_sum_bf16 launch", g, n_rows, n_cols, X, batch, C * h, ep, s)
               : launch<EP_SUM>("stc_spmm_sum_bf16 launch", g, n_rows, n_cols, X, batch, C * h, ep, s);

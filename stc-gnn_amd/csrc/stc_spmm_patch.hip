@@ -14,9 +14,8 @@
 // so that a workgroup has its next two chunks in flight while it multiplies (tools/probes/spmm_patch_sweep.hip: 180 us for the
 // bench's unit against 211 us row-blocked and 181 us for a plain copy of the same two planes).  The sum of a row runs over its
 // entries in CSR order with one fmaf each, from zero: bit for bit the row-blocked and the CSR kernels' result.
-#include "stc_common.h"
+#include "stc_spmm_host.h"
 
-#include <atomic>
 #include <type_traits>
 
 namespace {
@@ -244,49 +243,41 @@ __global__ __launch_bounds__(PT_THREADS, 2) void spmm_patch_kernel(PatchPlan pl,
     }
 }
 
-}  // namespace
+using Kernel = void (*)(PatchPlan, int, int, const v4f*, const v4f*, v4f*, int, float, float);
+struct PatchKernel { Kernel kern; stc::Grants* grants; };
+template <int W, bool HAS_Y0, bool BF16>
+stc::Grants g_granted;                                   // 64 KiB of dynamic LDS is above the default limit: raised once per kernel and device
 
-namespace {
-
-// X / Y0 / Y as 16-byte pieces: F4 of them per row (F / 4 floats or F / 8 bf16)
-int launch_patch(const char* who, const PatchPlan& pl, int n_rows, int n_cols, const void* X, const void* Y0, void* Y, int batch, int F4, bool bf16,
-                 float alpha, float beta, hipStream_t s) {
-    const size_t lds = (size_t)PT_SRC * PT_Q * 16;
-    const bool has_y0 = Y0 != nullptr && beta != 0.f;
-    using Kernel = void (*)(PatchPlan, int, int, const v4f*, const v4f*, v4f*, int, float, float);
-    Kernel kern = nullptr;
-    int slot = 0;
-#define STC_PATCH_W(W_, SLOT_) case W_: kern = bf16 ? (has_y0 ? spmm_patch_kernel<W_, true, true> : spmm_patch_kernel<W_, false, true>)  \
-                                                    : (has_y0 ? spmm_patch_kernel<W_, true, false> : spmm_patch_kernel<W_, false, false>); slot = SLOT_; break
-    switch (pl.width) { STC_PATCH_W(4, 0); STC_PATCH_W(8, 1); STC_PATCH_W(12, 2); STC_PATCH_W(16, 3); STC_PATCH_W(24, 4); STC_PATCH_W(32, 5);
-                        default: STC_REQUIRE(false, STC_EUNSUPPORTED, "%s: width %d (built for 4, 8, 12, 16, 24, 32)", who, pl.width); }
-#undef STC_PATCH_W
-    static std::atomic<int> granted[6][2][2][16];        // 64 KiB of dynamic LDS is above the default limit: once per kernel and device
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;      // a device the table does not cover: granted on every launch
-    if (dev < 0 || !granted[slot][has_y0][bf16][dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return stc::hip_status(e, who);
-        if (dev >= 0) granted[slot][has_y0][bf16][dev].store(1, std::memory_order_release);
-    }
-    const int per = (pl.n_patches + stc::kNumXcd - 1) / stc::kNumXcd;
-    hipLaunchKernelGGL(kern, dim3(per * stc::kNumXcd, batch), dim3(PT_THREADS), lds, s, pl, n_rows, n_cols, static_cast<const v4f*>(X),
-                       static_cast<const v4f*>(Y0), static_cast<v4f*>(Y), F4, alpha, beta);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return stc::hip_status(e, who);
-    return STC_OK;
+template <int W>
+PatchKernel patch_kernel(bool has_y0, bool bf16) {
+    if (bf16) return has_y0 ? PatchKernel{spmm_patch_kernel<W, true, true>, &g_granted<W, true, true>} : PatchKernel{spmm_patch_kernel<W, false, true>, &g_granted<W, false, true>};
+    return has_y0 ? PatchKernel{spmm_patch_kernel<W, true, false>, &g_granted<W, true, false>} : PatchKernel{spmm_patch_kernel<W, false, false>, &g_granted<W, false, false>};
 }
 
-int check_patch(const char* who, const void* patch_src, const void* patch_rows, const void* patch_cnt, const void* patch_idx, const void* patch_val,
-                int n_patches, int n_rows, int n_cols, const void* X, const void* Y0, const void* Y, int batch, int F, int chunk_elems, float beta) {
-    STC_REQUIRE(patch_src && patch_rows && patch_cnt && patch_idx && patch_val && X && Y, STC_EINVAL, "%s: null pointer", who);
-    STC_REQUIRE(n_patches >= 1 && (long long)n_patches * PT_ROWS >= n_rows, STC_EINVAL, "%s: %d patches of %d rows cannot cover %d rows", who, n_patches, PT_ROWS, n_rows);
-    STC_REQUIRE(F % chunk_elems == 0, STC_EUNSUPPORTED, "%s: F=%d must be a multiple of %d (rows in whole 1 KiB chunks)", who, F, chunk_elems);
-    STC_REQUIRE(beta == 0.f || Y0, STC_EINVAL, "%s: beta != 0 needs Y0", who);
-    STC_REQUIRE(X != Y, STC_EINVAL, "%s: X must not alias Y", who);
-    STC_REQUIRE(stc::aligned16(X) && stc::aligned16(Y) && (!Y0 || stc::aligned16(Y0)), STC_EALIGN, "%s: X / Y / Y0 must be 16-byte aligned", who);
-    STC_REQUIRE(batch <= 65535, STC_ELIMIT, "%s: batch %d > 65535 (grid.y)", who, batch);
-    return STC_OK;
+// piece: elements of a 16-byte piece (4 floats or 8 bf16); rows come in whole 1 KiB chunks of PT_Q pieces
+int patch_spmm(const char* who, const char* launch_who, const PatchPlan& pl, const stc::Plain& p, int piece, float alpha, void* Y, void* stream) {
+    STC_REQUIRE(pl.n_patches >= 0, STC_EINVAL, "%s: negative size (n_patches=%d)", who, pl.n_patches);
+    if (int rc = stc::check_plain(who, p, pl.src && pl.rows && pl.cnt && pl.idx && pl.val && p.X && p.Y, piece, piece * PT_Q, STC_EUNSUPPORTED)) return rc;
+    if (p.empty()) return STC_OK;
+    STC_REQUIRE(pl.n_patches >= 1 && (long long)pl.n_patches * PT_ROWS >= p.n_rows, STC_EINVAL, "%s: %d patches of %d rows cannot cover %d rows", who, pl.n_patches, PT_ROWS, p.n_rows);
+    if (int rc = stc::check_batch(who, p.batch)) return rc;
+    const size_t lds = (size_t)PT_SRC * PT_Q * 16;
+    const bool has_y0 = p.Y0 != nullptr && p.beta != 0.f, bf16 = piece == 8;
+    PatchKernel k{};
+    switch (pl.width) {
+        case 4: k = patch_kernel<4>(has_y0, bf16); break;
+        case 8: k = patch_kernel<8>(has_y0, bf16); break;
+        case 12: k = patch_kernel<12>(has_y0, bf16); break;
+        case 16: k = patch_kernel<16>(has_y0, bf16); break;
+        case 24: k = patch_kernel<24>(has_y0, bf16); break;
+        case 32: k = patch_kernel<32>(has_y0, bf16); break;
+        default: STC_REQUIRE(false, STC_EUNSUPPORTED, "%s: width %d (built for 4, 8, 12, 16, 24, 32)", launch_who, pl.width);
+    }
+    if (int rc = stc::hip_status(stc::allow_lds_once(k.kern, lds, *k.grants), launch_who)) return rc;
+    const int per = (pl.n_patches + stc::kNumXcd - 1) / stc::kNumXcd;
+    hipLaunchKernelGGL(k.kern, dim3(per * stc::kNumXcd, p.batch), dim3(PT_THREADS), lds, static_cast<hipStream_t>(stream), pl, p.n_rows, p.n_cols,
+                       static_cast<const v4f*>(p.X), static_cast<const v4f*>(p.Y0), static_cast<v4f*>(Y), p.F / piece, alpha, p.beta);
+    return stc::launched(launch_who);
 }
 
 }  // namespace
@@ -295,20 +286,14 @@ extern "C" int stc_patch_spmm_f32(const int32_t* patch_src, const int32_t* patch
                                   const uint8_t* patch_idx, const float* patch_val, int32_t n_patches, int32_t width,
                                   int32_t n_rows, int32_t n_cols, const float* X, const float* Y0, float* Y,
                                   int32_t batch, int32_t F, float alpha, float beta, void* stream) {
-    STC_REQUIRE(n_rows >= 0 && n_cols >= 0 && batch >= 0 && F >= 0 && n_patches >= 0, STC_EINVAL, "stc_patch_spmm_f32: negative size");
-    if (n_rows == 0 || batch == 0 || F == 0) return STC_OK;
-    if (int rc = check_patch("stc_patch_spmm_f32", patch_src, patch_rows, patch_cnt, patch_idx, patch_val, n_patches, n_rows, n_cols, X, Y0, Y, batch, F, 4 * PT_Q, beta)) return rc;
-    const PatchPlan pl{patch_src, patch_rows, patch_cnt, patch_idx, patch_val, n_patches, width};
-    return launch_patch("stc_patch_spmm_f32 launch", pl, n_rows, n_cols, X, Y0, Y, batch, F / 4, false, alpha, beta, static_cast<hipStream_t>(stream));
+    return patch_spmm("stc_patch_spmm_f32", "stc_patch_spmm_f32 launch", PatchPlan{patch_src, patch_rows, patch_cnt, patch_idx, patch_val, n_patches, width},
+                      stc::Plain{n_rows, n_cols, batch, F, X, Y0, Y, beta}, 4, alpha, Y, stream);
 }
 
 extern "C" int stc_patch_spmm_bf16(const int32_t* patch_src, const int32_t* patch_rows, const int32_t* patch_cnt,
                                    const uint8_t* patch_idx, const float* patch_val, int32_t n_patches, int32_t width,
                                    int32_t n_rows, int32_t n_cols, const void* X, const void* Y0, void* Y,
                                    int32_t batch, int32_t F, float alpha, float beta, void* stream) {
-    STC_REQUIRE(n_rows >= 0 && n_cols >= 0 && batch >= 0 && F >= 0 && n_patches >= 0, STC_EINVAL, "stc_patch_spmm_bf16: negative size");
-    if (n_rows == 0 || batch == 0 || F == 0) return STC_OK;
-    if (int rc = check_patch("stc_patch_spmm_bf16", patch_src, patch_rows, patch_cnt, patch_idx, patch_val, n_patches, n_rows, n_cols, X, Y0, Y, batch, F, 8 * PT_Q, beta)) return rc;
-    const PatchPlan pl{patch_src, patch_rows, patch_cnt, patch_idx, patch_val, n_patches, width};
-    return launch_patch("stc_patch_spmm_bf16 launch", pl, n_rows, n_cols, X, Y0, Y, batch, F / 8, true, alpha, beta, static_cast<hipStream_t>(stream));
+    return patch_spmm("stc_patch_spmm_bf16", "stc_patch_spmm_bf16 launch", PatchPlan{patch_src, patch_rows, patch_cnt, patch_idx, patch_val, n_patches, width},
+                      stc::Plain{n_rows, n_cols, batch, F, X, Y0, Y, beta}, 8, alpha, Y, stream);
 }

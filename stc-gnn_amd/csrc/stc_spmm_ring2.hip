@@ -15,9 +15,7 @@
 // Column chunks of 32 float4 (512 bytes of a row): half a wave per row, 96 x 512 B = 48 KiB of LDS + 6 KiB of tables, two workgroups per
 // compute unit.  Per chunk: staged registers -> LDS | next chunk requested | first ring: gather, addends, dY -> registers | dY -> LDS
 // (over the staged rows) | interior: gather, store.  Tables ((LDS offset, value) pairs) sit in LDS and are read as broadcasts.
-#include "stc_common.h"
-
-#include <atomic>
+#include "stc_spmm_host.h"
 
 namespace {
 
@@ -30,7 +28,7 @@ constexpr int R2_Q = 32;                         // float4 pieces per chunk and 
 constexpr int R2_STAGE = R2_L2 / (2 * R2_WAVES); // rows a half-wave stages per chunk (12)
 constexpr int R2_S1 = R2_L1 / (2 * R2_WAVES);    // first-ring slots per half-wave (8)
 constexpr int R2_S2 = R2_INT / (2 * R2_WAVES);   // interior rows per half-wave (4)
-constexpr int R2_MAX_ADD = 5;
+constexpr int R2_MAX_ADD = STC_RING2_MAX_ADD;
 
 using v4f = __attribute__((ext_vector_type(4))) float;
 
@@ -242,14 +240,14 @@ int launch_ring2(const Ring2Args& a, int batch, hipStream_t s, int n_add0 = 0) {
     }
     const int per = (a.pl.n_patches + stc::kNumXcd - 1) / stc::kNumXcd;
     hipLaunchKernelGGL(kern, dim3(per * stc::kNumXcd, batch), dim3(R2_THREADS), lds, s, a);
-    STC_LAUNCH_CHECK("stc_ring2 launch");
-    return STC_OK;
+    return stc::launched("stc_ring2 launch");
 }
 
 int check_ring2(const char* who, const void* l2_rows, const void* l1_rows, const void* int_rows, const void* t1, const void* t2, int n_patches, int n_rows,
                 int batch, int C, int h) {
     STC_REQUIRE(h == 16 && C >= 1 && (C * h) % (4 * R2_Q) == 0, STC_EUNSUPPORTED, "%s: rows of C * h = %d floats (hidden 16, whole 512-byte chunks)", who, C * h);
-    STC_REQUIRE(batch >= 0 && batch <= 65535 && n_rows >= 0 && n_patches >= 0, STC_EINVAL, "%s: bad sizes", who);
+    STC_REQUIRE(batch <= 65535 && n_patches >= 0, STC_EINVAL, "%s: bad sizes", who);      // (this front answers a batch beyond grid.y with STC_EINVAL)
+    if (int rc = stc::check_state_rows(who, n_rows, batch, C, h, true)) return rc;          // (the plan stands for the graph)
     STC_REQUIRE((long long)batch * n_rows * (C * h / 4) < (1ll << 28), STC_ELIMIT, "%s: planes of %lld 16-byte pieces (32-bit offsets: < 2^28)", who,
                 (long long)batch * n_rows * (C * h / 4));
     if (batch == 0 || n_rows == 0) return STC_OK;
@@ -266,7 +264,7 @@ extern "C" int stc_ring2_sum_f32(const int32_t* l2_rows, const int32_t* l1_rows,
                                  const float* A, const float* A2, int32_t n_add, const float* const* add,
                                  const float* U, const float* Cand, float* Y, float* Z,
                                  int32_t batch, int32_t C, int32_t h, void* stream) {
-    STC_REQUIRE(n_add >= 0 && n_add <= R2_MAX_ADD, STC_ELIMIT, "stc_ring2_sum_f32: 0..%d addends, got %d", R2_MAX_ADD, n_add);
+    if (int rc = stc::check_addend_count("stc_ring2_sum_f32", "addend", n_add, 0, R2_MAX_ADD, STC_ELIMIT)) return rc;
     if (int rc = check_ring2("stc_ring2_sum_f32", l2_rows, l1_rows, int_rows, t1, t2, n_patches, n_rows, batch, C, h)) return rc;
     if (batch == 0 || n_rows == 0) return STC_OK;
     STC_REQUIRE(A && U && Cand && Y && Z && (n_add == 0 || add), STC_EINVAL, "stc_ring2_sum_f32: null pointer");
@@ -279,10 +277,8 @@ extern "C" int stc_ring2_sum_f32(const int32_t* l2_rows, const int32_t* l1_rows,
     a.A = reinterpret_cast<const v4f*>(A);
     a.A2 = reinterpret_cast<const v4f*>(A2);
     a.n_add = n_add;
-    for (int i = 0; i < n_add; ++i) {
-        STC_REQUIRE(add[i] && stc::aligned16(add[i]) && add[i] != Y && add[i] != Z, STC_EINVAL, "stc_ring2_sum_f32: addend %d null, misaligned or aliasing a result", i);
-        a.add[i] = reinterpret_cast<const v4f*>(add[i]);
-    }
+    if (int rc = stc::check_addends("stc_ring2_sum_f32", "addend", add, n_add, Y, Z)) return rc;
+    for (int i = 0; i < n_add; ++i) a.add[i] = reinterpret_cast<const v4f*>(add[i]);
     a.U = reinterpret_cast<const v4f*>(U);
     a.Cand = reinterpret_cast<const v4f*>(Cand);
     a.Y = reinterpret_cast<v4f*>(Y);
@@ -326,8 +322,8 @@ extern "C" int stc_ring2_chain_f32(const int32_t* l2_rows, const int32_t* l1_row
                                    const float* A, const float* A2, float alpha1, int32_t n_add1, const float* const* add1, float* V,
                                    float alpha2, int32_t n_add0, const float* const* add0, const float* scale0, float* Z,
                                    int32_t batch, int32_t C, int32_t h, void* stream) {
-    STC_REQUIRE(n_add1 >= 0 && n_add1 <= 2, STC_ELIMIT, "stc_ring2_chain_f32: 0..2 first-ring addends, got %d", n_add1);
-    STC_REQUIRE(n_add0 >= 1 && n_add0 <= R2_MAX_ADD, STC_ELIMIT, "stc_ring2_chain_f32: 1..%d interior addends, got %d", R2_MAX_ADD, n_add0);
+    if (int rc = stc::check_addend_count("stc_ring2_chain_f32", "first-ring addend", n_add1, 0, 2, STC_ELIMIT)) return rc;
+    if (int rc = stc::check_addend_count("stc_ring2_chain_f32", "interior addend", n_add0, 1, R2_MAX_ADD, STC_ELIMIT)) return rc;
     if (int rc = check_ring2("stc_ring2_chain_f32", l2_rows, l1_rows, int_rows, t1, t2, n_patches, n_rows, batch, C, h)) return rc;
     if (batch == 0 || n_rows == 0) return STC_OK;
     STC_REQUIRE(A && Z && add0 && (n_add1 == 0 || add1), STC_EINVAL, "stc_ring2_chain_f32: null pointer");
@@ -339,12 +335,10 @@ extern "C" int stc_ring2_chain_f32(const int32_t* l2_rows, const int32_t* l1_row
     a.A = reinterpret_cast<const v4f*>(A);
     a.A2 = reinterpret_cast<const v4f*>(A2);
     a.n_add = n_add1;
-    for (int i = 0; i < n_add1; ++i) {
-        STC_REQUIRE(add1[i] && stc::aligned16(add1[i]) && add1[i] != Z && add1[i] != V, STC_EINVAL, "stc_ring2_chain_f32: first-ring addend %d null, misaligned or aliasing a result", i);
-        a.add[i] = reinterpret_cast<const v4f*>(add1[i]);
-    }
+    if (int rc = stc::check_addends("stc_ring2_chain_f32", "first-ring addend", add1, n_add1, Z, V)) return rc;
+    if (int rc = stc::check_addends("stc_ring2_chain_f32", "interior addend", add0, n_add0, Z, V)) return rc;
+    for (int i = 0; i < n_add1; ++i) a.add[i] = reinterpret_cast<const v4f*>(add1[i]);
     for (int i = 0; i < n_add0; ++i) {
-        STC_REQUIRE(add0[i] && stc::aligned16(add0[i]) && add0[i] != Z && add0[i] != V, STC_EINVAL, "stc_ring2_chain_f32: interior addend %d null, misaligned or aliasing a result", i);
         a.add0[i] = reinterpret_cast<const v4f*>(add0[i]);
         a.scale0[i] = scale0 ? scale0[i] : 1.f;
     }

@@ -25,7 +25,7 @@ LIB_PATH = os.path.join(_PKG_ROOT, 'libstc_hip.so')
 ABI_VERSION = 35
 FMT_BF16X3, FMT_F16X2 = 0, 1          # operand formats of the split-operand matrix-core kernels
 MAX_K = 4
-SPMM_SUM_MAX_ADD = 8
+SPMM_SUM_MAX_ADD, SPMM_SUM_BF16_MAX_ADD, RING2_MAX_ADD = 8, 5, 5      # addends of stc_spmm_sum_f32 / _bf16 and of the two-ring launches
 PATCH_ROWS, PATCH_MAX_SRC = 32, 64
 RING2_INTERIOR, RING2_FIRST, RING2_SECOND, RING2_WIDTH = 32, 64, 96, 8     # rows of a two-ring patch and of its rings, entries per row
 
@@ -455,7 +455,7 @@ class HipKernels:
         self._launch('stc_spmm_sum_f32', Y, *g, n, n, _ptr(X), _ptr(X2), float(alpha), len(addends), ptrs, lds, offs, scales, _ptr(Y), _ptr(U), _ptr(Cand), _ptr(dY),
                      _ptr(amax), 0 if amax is None else amax.numel(), B, Cc, h, nbytes=nbytes)
 
-    RING2_MAX_ADD = 5
+    RING2_MAX_ADD = RING2_MAX_ADD         # (the cell-graph executor reads it from the kernel set)
 
     @staticmethod
     def ring2_fits(B, n, Cc, h) -> bool:
@@ -1488,7 +1488,6 @@ class _Bf16Planar:
     entry points refuse, and their argument lists (those of the fp32 entry points without format, maxima, accumulate flags, offsets)."""
 
     name = 'hip-gfx950-bf16'
-    SPMM_SUM_MAX_ADD = 5         # addends stc_spmm_sum_bf16 takes (the fp32 entry point: STC_SPMM_SUM_MAX_ADD)
 
     def __init__(self, base: HipKernels):
         self.b = base
@@ -1521,11 +1520,11 @@ class _Bf16Planar:
 
     def spmm_sum(self, rowptr, colidx, val, plan, X, X2, addends, Y, blend=None):
         b = self.b
-        B, n, Cc, h, (U, Cand, dY), nbytes = b._spmm_sum_checked(torch.bfloat16, self.SPMM_SUM_MAX_ADD, rowptr, colidx, val, X, X2, addends, Y, blend)
+        B, n, Cc, h, (U, Cand, dY), nbytes = b._spmm_sum_checked(torch.bfloat16, SPMM_SUM_BF16_MAX_ADD, rowptr, colidx, val, X, X2, addends, Y, blend)
         for t, off in addends:
             if off != 0 or tuple(t.shape) != tuple(Y.shape):
                 raise StcError('spmm_sum (bf16): addends are whole planes')
-        ptrs = (_p * self.SPMM_SUM_MAX_ADD)(*[t.data_ptr() for t, _ in addends])
+        ptrs = (_p * SPMM_SUM_BF16_MAX_ADD)(*[t.data_ptr() for t, _ in addends])
         g = b._graph_ptrs(rowptr, colidx, val, plan, n)
         b._launch('stc_spmm_sum_bf16', Y, *g, n, n, _ptr(X), _ptr(X2), len(addends), ptrs, _ptr(Y), _ptr(U), _ptr(Cand), _ptr(dY), B, Cc, h, nbytes=nbytes)
 

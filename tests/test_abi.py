@@ -23,6 +23,7 @@ def test_header_and_python_export_lists_agree():
     header = open(os.path.join(REPO, 'include', 'stc_hip.h')).read()
     mirrored = {'STC_ABI_VERSION': _lib.ABI_VERSION, 'STC_MAX_K': _lib.MAX_K, 'STC_FMT_BF16X3': _lib.FMT_BF16X3, 'STC_FMT_F16X2': _lib.FMT_F16X2,
                 'STC_ACT_AMAX_SLOTS': _lib.HipKernels.ACT_AMAX_SLOTS, 'STC_SPMM_SUM_MAX_ADD': _lib.SPMM_SUM_MAX_ADD,
+                'STC_SPMM_SUM_BF16_MAX_ADD': _lib.SPMM_SUM_BF16_MAX_ADD, 'STC_RING2_MAX_ADD': _lib.RING2_MAX_ADD,
                 'STC_PATCH_ROWS': _lib.PATCH_ROWS, 'STC_PATCH_MAX_SRC': _lib.PATCH_MAX_SRC,
                 'STC_RING2_INTERIOR': _lib.RING2_INTERIOR, 'STC_RING2_FIRST': _lib.RING2_FIRST, 'STC_RING2_SECOND': _lib.RING2_SECOND,
                 'STC_RING2_WIDTH': _lib.RING2_WIDTH}

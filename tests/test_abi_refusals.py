@@ -9,31 +9,14 @@ The 21 entry points: 15 on fp32 rows / planes (csrc/stc_node.hip) and 6 on bf16 
 the two fronts answer the same fault with different codes (workspace alignment: STC_EALIGN vs STC_EINVAL; input width:
 STC_EINVAL vs STC_EUNSUPPORTED; a null plane of the bf16 node kernel: STC_EALIGN) the table records each as it is.
 """
-import ctypes
 import itertools
 
 import pytest
 
 from stc_hip import _lib
+from tests.abi_refusal_table import EALIGN, EINVAL, ELIMIT, EUNSUPPORTED, MIS, OK, P, PP, case_into, check_refusal, with_null
 
-OK, EINVAL, EALIGN, ELIMIT, EUNSUPPORTED = 0, -1, -2, -3, -4
 MAX_GRID = 512          # partial rows a backward workspace holds (NODE_BWD_MAX_GRID / MF_BWD_MAX_GRID)
-
-_BUF = ctypes.create_string_buffer(1 << 14)
-_BASE = (ctypes.addressof(_BUF) + 15) & ~15
-_next = itertools.count()
-
-
-def P():
-    """A distinct 16-byte aligned, non-null address (never dereferenced)."""
-    return _BASE + 16 * (next(_next) % 1000)
-
-
-def PP(n):
-    return [P() for _ in range(n)]
-
-
-MIS = _BASE + 4         # misaligned: refused before it is read
 BIG = 1 << 40           # a workspace size that is always enough (the workspace itself is never touched)
 
 
@@ -100,21 +83,12 @@ GOOD = {
 }
 
 
-def with_null(ptrs, i, value=None):
-    out = list(ptrs)
-    out[i] = value
-    return out
-
-
 def _z(fn, name):
     return GOOD[fn][name]
 
 
 CASES = []
-
-
-def case(fn, fault, code, *needles):
-    CASES.append(pytest.param(fn, fault, code, needles, id=f'{fn}-{len(CASES)}'))
+case = case_into(CASES)
 
 
 def dims_cases(fn, order='Ks', limit_code=ELIMIT, inval_code=EINVAL):
@@ -382,19 +356,6 @@ def lib():
     return lib
 
 
-def _call(lib, fn, fault):
-    args = dict(GOOD[fn])
-    assert set(fault) <= set(args), f'{fn}: unknown argument in {sorted(fault)}'
-    args.update(fault)
-    keep, argv = [], []
-    for value in args.values():
-        if isinstance(value, list):
-            value = (ctypes.c_void_p * len(value))(*value)
-            keep.append(value)
-        argv.append(value)
-    return getattr(lib, fn)(*argv)
-
-
 def test_table_covers_every_node_and_cell_entry_point():
     assert len(GOOD) == 21 and set(GOOD) <= set(_lib.EXPORTS)
     assert {p.values[0] for p in CASES} == set(GOOD)
@@ -404,12 +365,7 @@ def test_table_covers_every_node_and_cell_entry_point():
 
 @pytest.mark.parametrize('fn, fault, code, needles', CASES)
 def test_refusal(lib, fn, fault, code, needles):
-    rc = _call(lib, fn, fault)
-    message = lib.stc_last_error().decode()
-    assert rc == code, f'{fn}({fault}) returned {rc}: {message}'
-    assert message.startswith(fn + ':'), message
-    for needle in needles:
-        assert needle in message, f'{fn}({fault}): {needle!r} not in {message!r}'
+    check_refusal(lib, GOOD, fn, fault, code, needles)
 
 
 def test_dispatch_level_is_checked(lib):

@@ -375,6 +375,11 @@ for dt, tag, tol in ((torch.float32, 'f32', TOL), (torch.bfloat16, 'bf16', BTOL)
     for n, F, B, beta, inplace in ((37, 64, 2, 0.0, False), (203, 1024, 1, -1.0, True), (77, 16, 2, -1.0, False), (30, 2048, 1, 0.0, False)):
         case(f'bcsr_spmm_{tag}-n{n}-F{F}-beta{beta}{"-inplace" if inplace else ""}', {f'stc_bcsr_spmm_{tag}'},
              *_spmm_plan(lambda n=n, F=F: _banded_matrix(n, 4, n + F), F, B, beta, dt, inplace), tol=tol, cpu=(n == 37 and tag == 'f32'))
+    # every arm of the row-blocked ladders (csrc/stc_spmm.hip launch_vector: float4 per lane 1 / 2 / 4, pipelined gather for beta = 0 and whole
+    # column blocks, old loop otherwise; csrc/stc_spmm_bf16.hip launch: rows of <= 512, <= 1024, more columns), at the smallest shape with a ragged block
+    for F, beta in ((512, 0.0), (320, 0.0), (1024, 0.0), (1280, -1.0)) if tag == 'f32' else ((512, 0.0), (1024, 0.0), (2048, 0.0)):
+        case(f'bcsr_spmm_{tag}-n37-F{F}-beta{beta}-ladder', {f'stc_bcsr_spmm_{tag}'},
+             *_spmm_plan(lambda F=F: _banded_matrix(37, 4, 37 + F), F, 2, beta, dt, False), tol=tol)
     Fp = 256 if tag == 'f32' else 512
     for (H, W, permute), B, beta, inplace, side in (((17, 41, None), 2, 0.0, False, 'fwd'), ((17, 41, None), 1, -1.0, True, 'bwd'),
                                                     ((40, 40, 7), 1, -1.0, False, 'fwd'), ((40, 40, 7), 1, 0.0, False, 'bwd')):
@@ -450,6 +455,8 @@ for dt, tag, tol in ((torch.float32, 'f32', TOL), (torch.bfloat16, 'bf16', BTOL)
     for H, W, B, C, n_add, dual, blend in ((5, 5, 2, 32, 3, True, True), (4, 7, 1, 64, 5, False, False), (1, 1, 1, 32, 2, False, True), (9, 33, 1, 32, 0, True, True)):
         case(f'spmm_sum_{tag}-{H}x{W}-C{C}-add{n_add}{"-dual" if dual else ""}{"-blend" if blend else ""}', {f'stc_spmm_sum_{tag}'},
              *_spmm_sum(H, W, B, C, n_add, dual, blend, dt), tol=tol, cpu=(H == 5 and tag == 'f32'))
+    # C = 128: rows of 2048 columns, the widest arm of both dispatch ladders
+    case(f'spmm_sum_{tag}-4x7-C128-add2-blend', {f'stc_spmm_sum_{tag}'}, *_spmm_sum(4, 7, 1, 128, 2, False, True, dt), tol=tol)
 case('spmm_sum_f32-4x7-strided-addend-alpha2', {'stc_spmm_sum_f32'}, *_spmm_sum(4, 7, 2, 32, 1, False, False, torch.float32, strided=True, alpha=2.0))
 
 
@@ -498,6 +505,8 @@ for H, W, B, C, copies in ((5, 5, 2, 32, 'pair'), (4, 7, 3, 32, 'side'), (3, 3, 
     case(f'spmm_blend_f32-{H}x{W}-C{C}-{copies}', {'stc_spmm_blend_fwd_f32'}, **_spmm_blend(H, W, B, C, torch.float32, copies), cpu=(H == 4))
 for H, W, B, C in ((5, 5, 2, 32), (4, 7, 1, 64), (1, 1, 1, 32)):
     case(f'spmm_blend_bf16-{H}x{W}-C{C}', {'stc_spmm_blend_fwd_bf16'}, **_spmm_blend(H, W, B, C, torch.bfloat16, None), tol=BTOL)
+case('spmm_blend_f32-4x7-C128-None', {'stc_spmm_blend_fwd_f32'}, **_spmm_blend(4, 7, 1, 128, torch.float32, None))          # C = 128: the widest arm
+case('spmm_blend_bf16-4x7-C128', {'stc_spmm_blend_fwd_bf16'}, **_spmm_blend(4, 7, 1, 128, torch.bfloat16, None), tol=BTOL)
 
 
 def _ring2(kind, H, W, B, dual=False, n_add=1):
