@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define STC_ABI_VERSION 35
+#define STC_ABI_VERSION 36
 #define STC_MAX_K 4          /* highest Chebyshev order (Ks, Kc) the node kernels accept */
 
 /* Operand formats of the split-operand matrix-core kernels (C = 32 / 64, hidden 16).  Every fp32 operand is split into low-precision
@@ -600,7 +600,13 @@ int stc_head_bwd_f32(const float* H, const float* w, const float* y, const float
  * (phases 5, 6 as they are); backward: dZ_0 + S^T dZ_1 + T_2^T dZ_2 likewise in phases 7 and 4 (sequence 1, 7, 4).  Learned-graph operands
  * as at order 2, plus (new trailing pointers, NULL = not wanted, order 3 with a dense graph only) Z2c (forward, like Zg): the candidate's
  * third slab [T_2 x (R*H) | T_2 x Xt | 0] -- the gates' third slab is Zg2 itself -- and dZ2c / dZ2g (backward, like Zg): the gradients of
- * the candidate's / gates' third slab, so that dT_2 = sum dZ2 x Z0 is one more stc_graph_grad_f32 product and dT_c runs over three slabs. */
+ * the candidate's / gates' third slab, so that dT_2 = sum dZ2 x Z0 is one more stc_graph_grad_f32 product and dT_c runs over three slabs.
+ * Forward without a backward (ABI v36; no signature change): R and Cand of stc_cell_small_fwd_f32 may be NULL, each on its own, NULL = not
+ * wanted -- only stc_cell_small_bwd_f32 reads them.  The gates epilogue still forms R*H (in RH and in its staged copy) and the candidate
+ * epilogue still blends into Hnew: the launch skips the store of the absent plane and nothing else, in every form (orders 2 and 3, narrow and
+ * wide inputs, CSR and dense graphs, phase 0 and the split phases), so every other output keeps its bits.  U, Hnew, RH, Zg, Zc (order 3: Zg2,
+ * Zc2) stay required: later phases of the same cell read them across barriers and launch boundaries; a NULL there is STC_EINVAL as before.
+ * R and Cand, when given, are 16-byte aligned like the other planes. */
 int stc_cell_small_supported(int32_t Ks, int32_t Kc, int32_t C, int32_t cin, int32_t h);
 size_t stc_cell_small_workspace_bytes(int32_t n_nodes, int32_t C, int32_t cin, int32_t batch, int32_t Ks);
 int stc_cell_small_param_rows(void);

@@ -447,7 +447,7 @@ __global__ __launch_bounds__(WgShape<KS>::FWD_THREADS) void small_fwd_kernel(Sma
     const float* Xb = a.X + r0 * cin;
     const float* Hb = a.H + r0 * SC_H;
     float* Ub = a.U + r0 * SC_H;
-    float* Rb = a.R + r0 * SC_H;
+    float* Rb = a.R ? a.R + r0 * SC_H : nullptr;             // (R and Cand: read by a backward only -- not stored when absent)
     float* RHb = a.RH + r0 * SC_H;           // (written in phase 2, read later in the launch: never through a __restrict__ / const path)
     float* Zgb = a.Zg + r0 * LP;
     float* Zcb = a.Zc + r0 * SC_H;
@@ -562,7 +562,7 @@ __global__ __launch_bounds__(WgShape<KS>::FWD_THREADS) void small_fwd_kernel(Sma
                     Ub[e] = g;
                 } else {
                     const float rh = g * (STAGED ? P[(unsigned)grow * SP + j] : Hb[e]);
-                    Rb[e] = g;
+                    if (Rb) Rb[e] = g;
                     RHb[e] = rh;
                     if (STAGED) Q[(unsigned)grow * SQ + j] = rh;
                 }
@@ -618,7 +618,7 @@ __global__ __launch_bounds__(WgShape<KS>::FWD_THREADS) void small_fwd_kernel(Sma
     // 4: candidate + blend
     if (runs(4)) {
         const float bias = a.bc ? a.bc[j] : 0.f;
-        float* Cb = a.Cand + r0 * SC_H;
+        float* Cb = a.Cand ? a.Cand + r0 * SC_H : nullptr;
         float* Hn = a.Hnew + r0 * SC_H;
         fwd_conv<KS, KC, XQ>(Wc_r, M, t_lo + wave, SF_WAVES, t_hi, a.rpt, NC, j, kq,
             [&](int row) { return STAGED ? load_op<XQ>(Q, SQ, P + 16, SP, true, cin, row, kq) : load_op<XQ>(RHb, SC_H, Xb, cin, false, cin, row, kq); },
@@ -627,7 +627,7 @@ __global__ __launch_bounds__(WgShape<KS>::FWD_THREADS) void small_fwd_kernel(Sma
             [&](int grow, float y) {
                 const size_t e = (unsigned)grow * SC_H + j;
                 const float cd = tanh_hw(y + bias), u = Ub[e], hh = STAGED ? P[(unsigned)grow * SP + j] : Hb[e];
-                Cb[e] = cd;
+                if (Cb) Cb[e] = cd;
                 Hn[e] = (1.f - u) * hh + u * cd;
             });
     }
@@ -1099,12 +1099,14 @@ extern "C" int stc_cell_small_fwd_f32(const int32_t* rowptr, const int32_t* coli
                                       float* Zg, float* Zc, float* Zg2, float* Zc2, float* Z0, float* Z0c, float* Z1c, float* Z2c, int32_t phase,
                                       int32_t splits, int32_t batch, int32_t C, void* stream) {
     SC_COMMON_CHECKS("stc_cell_small_fwd_f32")
-    STC_REQUIRE(rowptr && (nnz == 0 || (colidx && val)) && X && H && Tc && Wg && Wc && U && R && Cand && Hnew && RH && Zg && Zc, STC_EINVAL,
+    // R and Cand are read by a backward only: NULL = not wanted, the epilogues then skip that store (U, RH, Zg, Zc are read by later phases of the cell)
+    STC_REQUIRE(rowptr && (nnz == 0 || (colidx && val)) && X && H && Tc && Wg && Wc && U && Hnew && RH && Zg && Zc, STC_EINVAL,
                 "stc_cell_small_fwd_f32: null operand");
     STC_REQUIRE(Hnew != H, STC_EINVAL, "stc_cell_small_fwd_f32: Hnew must not alias H (neighbour rows are read after the first rows are written)");
     const int xq = xq_of(cin);
-    STC_REQUIRE(stc::aligned16(H) && stc::aligned16(U) && stc::aligned16(R) && stc::aligned16(RH) && stc::aligned16(Zg) && stc::aligned16(Zc) &&
-                    (xq != 4 || stc::aligned16(X)) && stc::aligned16(Z0), STC_EINVAL, "stc_cell_small_fwd_f32: planes must be 16-byte aligned");
+    STC_REQUIRE(stc::aligned16(H) && stc::aligned16(U) && stc::aligned16(R) && stc::aligned16(Cand) && stc::aligned16(RH) && stc::aligned16(Zg) &&
+                    stc::aligned16(Zc) && (xq != 4 || stc::aligned16(X)) && stc::aligned16(Z0), STC_EINVAL,
+                "stc_cell_small_fwd_f32: planes must be 16-byte aligned");
     const int npt = 16 / C, rpt = npt * C;
     STC_REQUIRE(phase >= 0 && phase <= 6 && splits >= 1 && splits <= 64 && (phase != 0 || splits == 1), STC_EINVAL,
                 "stc_cell_small_fwd_f32: phase %d / splits %d (phase 0 = the whole cell, one workgroup per sample; 1..4 = one phase, 5 = 1 + 2, "

@@ -22,7 +22,7 @@ from .graph import is_full_pattern
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, 'libstc_hip.so')
 # Mirrors of include/stc_hip.h (#define STC_<name>; tests/test_abi.py compares each, and HipKernels.ACT_AMAX_SLOTS, with the header)
-ABI_VERSION = 35
+ABI_VERSION = 36
 FMT_BF16X3, FMT_F16X2 = 0, 1          # operand formats of the split-operand matrix-core kernels
 MAX_K = 4
 SPMM_SUM_MAX_ADD, SPMM_SUM_BF16_MAX_ADD, RING2_MAX_ADD = 8, 5, 5      # addends of stc_spmm_sum_f32 / _bf16 and of the two-ring launches
@@ -907,6 +907,9 @@ class HipKernels:
     #: Chebyshev order 3 with a learned dense graph on these kernels (``graph2`` = T_2(S) as a dense matrix; split form only).  A kernel set
     #: without the attribute keeps that combination on the general path (``small.small_graph_supported``).
     small_dense_order3 = True
+    #: ``cell_small_fwd`` takes ``R=None`` / ``Cand=None`` (ABI v36): planes that only ``cell_small_bwd`` reads, not stored when absent.  A kernel set
+    #: without the attribute gets scratch planes from the forward-only executor (``small._forward_only``).
+    small_optional_stores = True
 
     def cell_small_supported(self, Ks, Kc, Cc, cin, h, n_nodes=0) -> bool:
         return n_nodes * Cc <= self.SMALL_MAX_ROWS and bool(self.lib.stc_cell_small_supported(Ks, Kc, Cc, cin, h))
@@ -985,12 +988,15 @@ class HipKernels:
         Beside a dense graph (the cached full pattern) ``graph2`` is that pattern with T_2 as a dense matrix; the step then always runs as the
         split launches (with ``splits`` = 1 too), and ``Z2c`` (optional, like Zg) receives the candidate's third slab.
         ``checked=False``: the caller built every buffer itself from shapes it already validated (the cell-graph executor).
+        ``R`` / ``Cand`` = None (each on its own): a forward that no backward follows -- the launch does not store that plane, everything else
+        keeps its bits (``small_optional_stores``).
         ``Z0`` (optional, like Zg): receives the slab [H | Xt | 0] (learned graphs: operand of the graph-gradient product).
         ``splits`` = G > 1: the cell as TWO launches (phases 1 + 2, then 3 + 4: R*H of the neighbours is the one dependency that crosses
         workgroups), each over G workgroups per sample that own a contiguous range of row tiles -- for batches too small to fill the chip
         with one workgroup per sample (``cell_small_splits``)."""
         if checked:
-            self._small_shapes('cell_small_fwd', rowptr, colidx, val, X, H, Tc, Wg, Wc, dict(U=U, R=R, Cand=Cand, Hnew=Hnew, RH=RH), Zg, Zc)
+            given = {name: t_ for name, t_ in (('R', R), ('Cand', Cand)) if t_ is not None}      # only the planes given are validated
+            self._small_shapes('cell_small_fwd', rowptr, colidx, val, X, H, Tc, Wg, Wc, dict(U=U, Hnew=Hnew, RH=RH, **given), Zg, Zc)
             for name, t_ in (('Z0', Z0), ('Z0c', Z0c), ('Z1c', Z1c), ('Z2c', Z2c)):
                 if t_ is not None:
                     _tensor('cell_small_fwd.' + name, t_, tuple(Zg.shape))
@@ -1000,9 +1006,9 @@ class HipKernels:
                     _tensor('cell_small_fwd.' + name, b_, (n,))
         (B, N, Cc, cin, Kc), phases, head, p2 = self._small_head('cell_small_fwd', self.SMALL_FWD_PHASES, splits, rowptr, colidx, val, X, H, Tc, Zg, Zc, graph2, Zg2, Zc2)
         for phase in phases:
-            self._launch('stc_cell_small_fwd_f32', H, *head, Wg.data_ptr(), _ptr(bg), Wc.data_ptr(), _ptr(bc), U.data_ptr(), R.data_ptr(), Cand.data_ptr(),
+            self._launch('stc_cell_small_fwd_f32', H, *head, Wg.data_ptr(), _ptr(bg), Wc.data_ptr(), _ptr(bc), U.data_ptr(), _ptr(R), _ptr(Cand),
                          Hnew.data_ptr(), RH.data_ptr(), Zg.data_ptr(), Zc.data_ptr(), *p2, _ptr(Z0), _ptr(Z0c), _ptr(Z1c), _ptr(Z2c), phase, splits, B, Cc,
-                         nbytes=(4 * B * N * Cc * (cin + 16 * 8 + 2 * self.cell_small_zg_width(cin))) // len(phases))
+                         nbytes=(4 * B * N * Cc * (cin + 16 * (8 - (R is None) - (Cand is None)) + 2 * self.cell_small_zg_width(cin))) // len(phases))
 
     # Launches of a split cell step (phase codes of stc_cell_small_*_f32; 5 = 1 + 2, 6 = 3 + 4, 7 = 2 + 3), CSR and dense graphs alike
     SMALL_FWD_PHASES = (5, 6)

@@ -32,7 +32,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .graph import SpatialOperand
-from .small import _alias, _check_guard, _guard, _out_slots, _stacks, _unpack, small_graph_supported, stc_small_graph
+from .small import _alias, _check_guard, _guard, _out_slots, _stacks, _unpack, last_uses, small_graph_supported, stc_small_graph, wavefront
 
 _kernels = None
 
@@ -767,21 +767,12 @@ class _ForwardPass(_Pass):
 
     # ---- forward only: the order the cells run in and what is dropped after each
     def wavefront(self):
-        """The cells by level (longest path from the external tensors), schedule order inside a level: a topological order of the same graph in
-        which a state's consumers follow it closely -- the encoder's schedule is layer-major, so in ITS order every state of a layer lives until
-        the next layer has run (one state and one aggregation per observed step); by level, a constant number of them.  A cell's launches read
-        the same operands in either order: same bits."""
-        level = []
-        for _, x, hs in self.schedule:
-            level.append(1 + max([level[src[1]] for src in (x, hs) if src[0] == 'cell'], default=0))
-        return sorted(range(len(self.schedule)), key=lambda j: (level[j], j))
+        """The cells by level, schedule order inside a level (``small.wavefront``: shared with the few-category executor)."""
+        return wavefront(self.schedule)
 
     def last_uses(self, order):
         """source -> the cell after whose launches nothing in ``order`` reads it any more."""
-        last = {}
-        for j in order:
-            last[self.schedule[j][1]] = last[self.schedule[j][2]] = j
-        return last
+        return last_uses(self.schedule, order)
 
     def release(self, j, last, keep):
         """After cell j: its input rows, and every source it was the last consumer of -- the state (unless it is in ``keep``: the outputs live in

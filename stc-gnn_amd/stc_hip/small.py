@@ -16,6 +16,8 @@ pre-activation gradients) and the backward forms  dGs^T = sum_cells dZ_1 x Z_0  
 products per parameter set at the end -- not per cell.  At Chebyshev order 3 the second matrix T_2 = 2 V V - I (V = Gs^T) is formed OUTSIDE the
 node with differentiable torch ops and handed in as a second values tensor: the node returns  dT_2 = sum_cells dZ_2 x Z_0  beside d fwd_val,
 and torch's autograd carries it through the N x N product to Gs.
+A pass that no backward follows (``torch.no_grad()``, or nothing requires grad) skips the node: ``_forward_only`` runs the same launches on one
+shared set of scratch planes, keeps no state beyond its last reader and leaves R / Cand unstored (``stc_small_graph`` picks the route).
 """
 from __future__ import annotations
 
@@ -40,7 +42,9 @@ def small_graph_supported(k, op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_
     if dtype != torch.float32 or not hasattr(k, 'cell_small_supported') or (op.fwd_val.requires_grad and op.nnz != op.n * op.n):
         return False
     if Ks == 3:                                                     # order 3: T_2(S) as a second graph --
-        if op.fwd_val.requires_grad:                                # a learned full-pattern graph (T_2 dense, split launches) where the kernel set takes one
+        # a learned full-pattern graph (T_2 dense, split launches) where the kernel set takes one; with grad mode off (evaluation: the generator's
+        # Gs does not require grad there) the same graph as it arrives then -- in grad mode a dense graph that needs no gradient keeps the general path
+        if op.fwd_val.requires_grad or (not torch.is_grad_enabled() and op.source is None and op.nnz == op.n * op.n):
             if not getattr(k, 'small_dense_order3', False) or op.n * C > k.SMALL_STAGED_ROWS:
                 return False
         elif op.source is None or op.nnz == op.n * op.n:            # else fixed sparse graphs (CsrGraph.second_order)
@@ -90,6 +94,43 @@ def _check_guard(ctx):
     if stack is not None and stack._version != ctx.out_stack_version:
         raise RuntimeError('stc_cell_graph: the returned state stack was modified in place after the forward pass; the states saved for '
                            'backward share its storage (treat the stack as read-only, or clone it before editing)')
+
+
+def wavefront(schedule):
+    """The cells by level (longest path from the external tensors), schedule order inside a level: a topological order of the same graph in
+    which a state's consumers follow it closely -- the encoder's schedule is layer-major, so in ITS order every state of a layer lives until
+    the next layer has run (one state and one aggregation per observed step); by level, a constant number of them.  A cell's launches read
+    the same operands in either order: same bits."""
+    level = []
+    for _, x, hs in schedule:
+        level.append(1 + max([level[src[1]] for src in (x, hs) if src[0] == 'cell'], default=0))
+    return sorted(range(len(schedule)), key=lambda j: (level[j], j))
+
+
+def last_uses(schedule, order):
+    """source -> the cell after whose launches nothing in ``order`` reads it any more."""
+    last = {}
+    for j in order:
+        last[schedule[j][1]] = last[schedule[j][2]] = j
+    return last
+
+
+def _checked_shapes(op, Ks, schedule, ext, stacks, Tc):
+    """((B, N, C), input width of every cell) of a few-category schedule, its operands checked (the per-cell launches skip the wrapper's checks)."""
+    ref = ext[0]
+    B, N, C = ref.shape[:3]
+    cin = [ext[x[1]].shape[-1] if x[0] == 'ext' else H16 for _, x, _ in schedule]
+    for t in ext:
+        if t.shape[:3] != (B, N, C) or t.dtype != torch.float32 or t.device != ref.device:
+            raise ValueError(f'stc_cell_graph: external tensors must be float32 (B, N, C, *) on one device, got {tuple(t.shape)} {t.dtype}')
+    if N != op.n or Tc.shape[1:] != (C, C):
+        raise ValueError(f'stc_cell_graph: graphs are for N={op.n}, C={Tc.shape[1]}; got N={N}, C={C}')
+    for (s_id, _, hs), w in zip(schedule, cin):
+        Wg, bg, Wc, bc = stacks[s_id]
+        rows = Ks * Tc.shape[0] * (w + H16)
+        if Wg.shape != (rows, 2 * H16) or Wc.shape != (rows, H16) or (hs[0] == 'ext' and ext[hs[1]].shape[-1] != H16):
+            raise ValueError(f'stc_cell_graph: parameter set {s_id} does not fit an input of {w} + {H16} columns')
+    return (B, N, C), cin
 
 
 def _layout(schedule, cin, n_cells, outputs):
@@ -178,18 +219,7 @@ class _StcSmallGraph(Function):
         ext, stacks, Tc, fwd_val = _unpack(n_ext, Tc, fwd_val, tensors)
         n_cells = len(schedule)
         ref = ext[0]
-        B, N, C = ref.shape[:3]
-        cin = [ext[x[1]].shape[-1] if x[0] == 'ext' else H16 for _, x, _ in schedule]
-        for t in ext:                                                # (the per-cell launches below skip the wrapper's checks)
-            if t.shape[:3] != (B, N, C) or t.dtype != torch.float32 or t.device != ref.device:
-                raise ValueError(f'stc_cell_graph: external tensors must be float32 (B, N, C, *) on one device, got {tuple(t.shape)} {t.dtype}')
-        if N != op.n or Tc.shape[1:] != (C, C):
-            raise ValueError(f'stc_cell_graph: graphs are for N={op.n}, C={Tc.shape[1]}; got N={N}, C={C}')
-        for (s_id, _, hs), w in zip(schedule, cin):
-            Wg, bg, Wc, bc = stacks[s_id]
-            rows = Ks * Tc.shape[0] * (w + H16)
-            if Wg.shape != (rows, 2 * H16) or Wc.shape != (rows, H16) or (hs[0] == 'ext' and ext[hs[1]].shape[-1] != H16):
-                raise ValueError(f'stc_cell_graph: parameter set {s_id} does not fit an input of {w} + {H16} columns')
+        (B, N, C), cin = _checked_shapes(op, Ks, schedule, ext, stacks, Tc)
         out_slot, inner_slot, pos, counts = _layout(schedule, cin, n_cells, outputs)
         out_stack = ref.new_empty(len(outputs), B, N, C, H16)        # the requested states are produced in place, stacked
         inner = ref.new_empty(max(1, n_cells - len(outputs)), B, N, C, H16)
@@ -369,7 +399,50 @@ def dense_second_order(op: SpatialOperand) -> torch.Tensor:
     return (2.0 * (V @ V) - torch.eye(op.n, dtype=V.dtype, device=V.device)).reshape(-1)
 
 
+def _forward_only(k, op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, t2f, tensors):
+    """``_StcSmallGraph.forward`` for a pass that no backward follows (evaluation, forecasting): the same launches per cell, in the same argument
+    order, with the same ``splits`` -- but nothing is saved.  ONE set of the planes and slabs that carry a cell from phase to phase (U, RH, Zc and,
+    per input-width group, Zg; order 3: Zc2, Zg2) serves every cell: the launches are stream-ordered and a cell's scratch is dead once its last
+    launch has been issued.  No learned-graph slabs; R and Cand -- read by a backward only -- are not stored where the kernel set takes None for
+    them (``small_optional_stores``; else one shared plane each).  The cells run by level (``wavefront``) and an inner state goes back to the
+    allocator after the last cell that reads it has launched, so memory does not grow with the number of cells.  The requested states are
+    written in place into the returned stack: bit for bit that of the autograd node."""
+    ext, stacks, Tc, fwd_val = _unpack(n_ext, Tc, fwd_val, tensors)
+    ref = ext[0]
+    (B, N, C), cin = _checked_shapes(op, Ks, schedule, ext, stacks, Tc)
+    out_slot = _out_slots(outputs)
+    out_stack = ref.new_empty(len(outputs), B, N, C, H16)
+    plane, rows = (lambda: ref.new_empty(B, N, C, H16)), (lambda width: ref.new_empty(B, N * C, width))
+    o3 = Ks == 3
+    shared = dict(U=plane(), RH=plane(), Zc=rows(H16), **(dict(Zc2=rows(H16)) if o3 else {}))
+    shared.update(dict(R=None, Cand=None) if getattr(k, 'small_optional_stores', False) else dict(R=plane(), Cand=plane()))
+    slabs = {w: dict(Zg=rows(k.cell_small_zg_width(w)), **(dict(Zg2=rows(k.cell_small_zg_width(w))) if o3 else {})) for w in set(cin)}
+    if o3:
+        shared['graph2'] = _graph2(op, Ks, None if t2f is None else _c(t2f), ref.device, 'fwd')
+    splits = k.cell_small_splits(B, N * C)
+    state = [None] * len(schedule)
+    source = lambda src: ext[src[1]] if src[0] == 'ext' else state[src[1]]
+    order = wavefront(schedule)
+    last = last_uses(schedule, order)
+    for j in order:
+        s_id, x, hs = schedule[j]
+        state[j] = out_stack[out_slot[j]] if j in out_slot else plane()
+        k.cell_small_fwd(op.fwd_rowptr, op.fwd_colidx, fwd_val, source(x), source(hs), Tc, *stacks[s_id], Hnew=state[j], checked=False, splits=splits,
+                         **shared, **slabs[cin[j]])
+        for src in {x, hs, ('cell', j)}:                             # (an output lives in the stack; dropping its view frees nothing)
+            if src[0] == 'cell' and last.get(src, j) == j:
+                state[src[1]] = None
+    return out_stack
+
+
 def stc_small_graph(k, op: SpatialOperand, Tc, Ks: int, schedule, outputs, ext, stacks):
+    """The schedule on the few-category cell kernels: the autograd node, or -- grad mode off, or nothing that requires grad (the predicate of
+    ``ops.stc_cell_graph``) -- the forward-only route."""
     flat = [p for st in stacks for p in st]
-    t2f = dense_second_order(op) if Ks == 3 and op.nnz == op.n * op.n and op.source is None else None
+    dense3 = Ks == 3 and op.nnz == op.n * op.n and op.source is None
+    if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (Tc, op.fwd_val, *ext, *flat)):
+        with torch.no_grad():
+            return _forward_only(k, op, Ks, list(schedule), list(outputs), len(ext), Tc, op.fwd_val, dense_second_order(op) if dense3 else None,
+                                 (*ext, *flat))
+    t2f = dense_second_order(op) if dense3 else None
     return _StcSmallGraph.apply(k, op, Ks, list(schedule), list(outputs), len(ext), Tc, op.fwd_val, t2f, *ext, *flat)

@@ -7,6 +7,8 @@
 #   infer            forward-only (no_grad) step of the metric configuration (tools/bench_infer.py): its one JSON line on stdout
 #   sf-learned-k3    SF shape, learned dense graphs at Chebyshev order 3, HIP-graph replay (tools/bench_sf.py --order 3), three repeats: its
 #                    text line and its one JSON line on stdout
+#   sf-infer         SF shape, the no_grad forward alone (tools/bench_sf.py --infer), eager and as a HIP-graph replay, csr-fixed and dense-learned at
+#                    orders 2 and 3, three repeats each: per run its text line and its one JSON line on stdout (eight of each)
 #   presets          --preset cfg2 (K = 2, 3) / cfg4 / cfg5 / sf / sf-learned lines -> gpurun_out/preset_*.json
 #   stats            rocprofv3 --kernel-trace --stats of the bench command -> gpurun_out/kernel_stats.csv
 #   traffic          FETCH_SIZE / WRITE_SIZE PMC passes (tools/gpu_pmc_bench.sh) -> gpurun_out/spmm_traffic_bench.json
@@ -33,6 +35,13 @@ PY
            ;;
     infer) timeout -k 10 600 python tools/bench_infer.py --steps ${INFER_STEPS:-10} --warmup 3; rc=$? ;;
     sf-learned-k3) timeout -k 10 600 python tools/bench_sf.py --mode dense-learned --order 3 --graph --steps 20 --repeats 3 --json; rc=$? ;;
+    sf-infer) rc=0
+           for cfg in "csr-fixed 2" "csr-fixed 3" "dense-learned 2" "dense-learned 3"; do
+             for g in "" "--graph"; do
+               [ $rc -eq 0 ] || break                                   # (nothing more on the GPU after a step that failed)
+               timeout -k 10 300 python tools/bench_sf.py --infer --mode ${cfg% *} --order ${cfg#* } $g --steps 20 --repeats 3 --json; rc=$?
+             done
+           done ;;
     presets) rc=0
            for p in "cfg2 --order 2" "cfg2 --order 3" "cfg4" "cfg5" "sf" "sf-learned"; do
              n=$(echo $p | tr -d ' -'); timeout -k 10 900 python bench.py --preset $p --steps 5 --warmup 2 > gpurun_out/preset_$n.json 2> gpurun_out/preset_$n.err || rc=1
