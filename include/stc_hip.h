@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define STC_ABI_VERSION 36
+#define STC_ABI_VERSION 37
 #define STC_MAX_K 4          /* highest Chebyshev order (Ks, Kc) the node kernels accept */
 
 /* Operand formats of the split-operand matrix-core kernels (C = 32 / 64, hidden 16).  Every fp32 operand is split into low-precision
@@ -171,6 +171,13 @@ int stc_ring2_blend_f32(const int32_t* l2_rows, const int32_t* l1_rows, const in
                         const float* Bm, const float* A, const float* U, const float* H,
                         float* Cand, float* Hnew, float* SHnew,
                         int32_t batch, int32_t C, int32_t h, void* stream);
+/* stc_ring2_blend_f32 on the zero initial state (ABI v37; a cell's first time step): Hnew = U Cand, no H operand.  Cand, Hnew and SHnew are
+ * what stc_ring2_blend_f32 gives for a plane of zeros as H. */
+int stc_ring2_blend_first_f32(const int32_t* l2_rows, const int32_t* l1_rows, const int32_t* int_rows, const int32_t* t1, const int32_t* t2,
+                              int32_t n_patches, int32_t n_rows,
+                              const float* Bm, const float* A, const float* U,
+                              float* Cand, float* Hnew, float* SHnew,
+                              int32_t batch, int32_t C, int32_t h, void* stream);
 /* Two CHAINED aggregations on the same plan format (ABI v28): the feature-side Chebyshev recurrence of order 3 (reference STC_GNN.py:24-29
  * applied to the features, :37; BASELINE configuration 4) and its transpose, each one launch instead of two:
  *     V = alpha1 S.(A [+ A2]) + sum_k add1[k]          Z = alpha2 S.V + sum_k scale0[k] add0[k]
@@ -479,6 +486,28 @@ int stc_cell_bwd_planar_f32(const float* X, const float* H, const float* SX, con
                             int32_t operand_format, const float* act_amax,
                             void* workspace, size_t workspace_bytes,
                             int64_t nodes, int32_t C, int32_t Lw, int32_t h, void* stream);
+
+/* ---- first-step forms of the planar cell launches (ABI v37; C = 32, h = 16: stc_cell_first_supported) --------------------
+ * The first time step of every layer runs on the zero initial state (reference STC_GNN.py: init_hidden).  These forms take no H, S.H or Rg
+ * plane and produce no Rg, R*H, dH or dS.H: R only ever multiplies H = 0 and dR carries the factor H.  What they do produce is what the
+ * general entry points produce for explicit planes of zeros, from the same products in the same order.
+ *   stc_cell_gates_fwd_first_f32: U, A, Bm of stc_cell_gates_fwd_planar_f32 (the candidate's input is [X | 0]); act_amax receives the maxima
+ *     of |X|, |SX| in the rows that entry point uses, the H rows stay at the buffer's zero.
+ *   stc_cell_bwd_first_f32: dX, dSX (wide input only; accumulate_x as above) and dWg, dbg, dWc, dbc of stc_cell_bwd_planar_f32 at full
+ *     shape -- the H rows of both weight gradients and the reset-gate half of dWg / dbg are exact zeros.
+ *     workspace >= stc_cell_bwd_first_workspace_bytes(C, Lw, h) bytes, 16-byte aligned. */
+int stc_cell_first_supported(int32_t C, int32_t h);
+int stc_cell_gates_fwd_first_f32(const float* X, const float* SX, const float* Tc, const float* W, const float* bias, float* U,
+                                 const float* Wc, const float* bc, float* A, float* Bm,
+                                 int32_t operand_format, float* act_amax,
+                                 int64_t nodes, int32_t C, int32_t Lw, int32_t h, void* stream);
+size_t stc_cell_bwd_first_workspace_bytes(int32_t C, int32_t Lw, int32_t h);
+int stc_cell_bwd_first_f32(const float* X, const float* SX, const float* Tc, const float* Wg, const float* Wc,
+                           const float* U, const float* Cand, const float* dHnew, const float* dBm,
+                           float* dX, float* dSX, float* dWg, float* dbg, float* dWc, float* dbc,
+                           int32_t accumulate_x, int32_t operand_format, const float* act_amax,
+                           void* workspace, size_t workspace_bytes,
+                           int64_t nodes, int32_t C, int32_t Lw, int32_t h, void* stream);
 
 /* ---- planar cell convolutions of Chebyshev order K = 3 (C = 32, h = 16) ----------------------------------------------
  * The planar form above for BDG_Dif.cheby_poly order 3 (STC_GNN.py:24-29, 35-39; BASELINE configuration 4).  Zx[n] / Zh[n],

@@ -396,7 +396,11 @@ class STCGNN(nn.Module):
         if X.requires_grad or not ops.cell_graph_supported(pair.spatial, pair.Tc, self.Ks, C, h, [cin0, h], dtype=X.dtype):
             return None
         n_layers, horizon = len(enc), self.decoder.out_horizon
-        ext = [X[:, t] for t in range(T)] + [c.init_hidden(B).to(X.dtype) for c in enc]   # inputs, then the zero initial states
+        # inputs, then the zero initial states -- as shapes only where the executor runs their cells in the first-step forms (no plane is read)
+        if ops.first_step_route(pair.spatial, pair.Tc, self.Ks, C, h, [cin0, h], dtype=X.dtype):
+            ext = [X[:, t] for t in range(T)] + [ops.zero_state(c.gates.W, (B, c.num_nodes, c.num_categories, c.hidden_dim), X.dtype) for c in enc]
+        else:
+            ext = [X[:, t] for t in range(T)] + [c.init_hidden(B).to(X.dtype) for c in enc]
         eid = lambda l, t: l * T + t                                                    # encoder: layer-major, then time
         did = lambda l, s_: n_layers * T + s_ * n_layers + l                            # decoder: step-major, then layer
         schedule = []

@@ -53,7 +53,12 @@ constexpr size_t cb_lds_bytes() { return (size_t)CB_TABLE_FRAGS * F::NP * 64 * 1
 // the dW / db sums over nodes at the wave's reference scale), activation operands of the dW products per plane (a.zmax), and the tables
 // normalised per workgroup: block c = 0 of W carries sW sT, blocks c >= 1 carry sW and T_1 carries sT, so both halves of a contraction over
 // (c, o) arrive with the same factor a_n sT sW, which the tile's store takes out again.
-template <class F, int L, int PL, int ACCX = 0, int ACCH = 0>        // PL = 1: L = 32, rows [X | H];  PL = 2: L = 20, rows [H | x (cin = Lw - 16 <= 4) | pad], W rows permuted to match
+//
+// FIRST: the cell's state is the zero initial state (the first time step of every layer).  H, S.H and R are not read (the pointers may be
+// null), dH and dS.H are not written, and every product with an operand that is zero by construction is left out: the R*H tile and its
+// gradient, the H row block of both dW sums and of the gates' dX tiles, and the reset-gate half of the gates' dY (dR carries the factor H).
+// The products that remain are the general kernel's, in its order: the same bits as a launch on explicit zero planes.
+template <class F, int L, int PL, int ACCX = 0, int ACCH = 0, int FIRST = 0>        // PL = 1: L = 32, rows [X | H];  PL = 2: L = 20, rows [H | x (cin = Lw - 16 <= 4) | pad], W rows permuted to match
 __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs args_in_kernarg_segment) {
     using Op = typename F::Op;
     constexpr int NP = F::NP;
@@ -62,6 +67,8 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
     constexpr int LBD = PL == 1 ? 2 : 1;          // blocks of the row whose gradient is wanted (a narrow input plane gets none)
     static_assert((PL == 1 && L == 32) || (PL == 2 && L == 20), "planar rows are 16 + 16 or 16 + cin columns");
     static_assert(PL == 1 || !ACCX, "a narrow input plane gets no gradient");
+    static_assert(!FIRST || !ACCH, "a zero initial state gets no gradient");
+    constexpr int LBC = FIRST ? (PL == 1 ? 1 : 0) : LBD;      // blocks of the row whose gradient tiles are formed (FIRST: the X block of a wide row, none of a narrow one)
     constexpr bool AHEAD = !(ACCX && ACCH);       // W fragments fetched one product group ahead (12 registers; the both-sides variant has none to spare)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u32x4* TB = reinterpret_cast<u32x4*>(smem_raw);     // [NRB rb]          T_1[16rb + x][pair_row]
@@ -155,6 +162,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
 
     const float* P0[K] = {PL == 1 ? a.X : a.H, PL == 1 ? a.SX : a.SH};          // block 0 of slab n
     const float* P1[K] = {PL == 1 ? a.H : a.X, PL == 1 ? a.SH : a.SX};          // block 1 of slab n (PL = 2: the narrow plane)
+    constexpr bool LOAD0 = !(FIRST && RHB == 0), LOAD1 = !(FIRST && RHB == 1);  // FIRST: the state's block is zero, not read
 
     // One node's operands: the slab columns in accumulator layout (row 16kb + 4g + t, column x: the A operands of the dW products) and the
     // gate planes in row-on-lane layout (row 16kb + x, columns 4g .. 4g+3).  Everything element-wise is formed ONCE, in row layout, and
@@ -187,8 +195,9 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
                 const size_t row = r0 + 16 * kb + 4 * g + t, e = row * HID + x;
 #pragma unroll
                 for (int n = 0; n < K; ++n) {
-                    o.zg[n][0][kb][t] = P0[n][e];
-                    if constexpr (PL == 1) o.zg[n][1][kb][t] = P1[n][e];
+                    o.zg[n][0][kb][t] = LOAD0 ? P0[n][e] : 0.f;
+                    if constexpr (!LOAD1) o.zg[n][1][kb][t] = 0.f;
+                    else if constexpr (PL == 1) o.zg[n][1][kb][t] = P1[n][e];
                     else o.zg[n][1][kb][t] = x < cin ? P1[n][row * cin + x] : 0.f;
                 }
             }
@@ -196,10 +205,10 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
         for (int kb = 0; kb < NRB; ++kb) {
             const size_t e = (r0 + 16 * kb + x) * HID + 4 * g;
             o.uv[kb] = stc_ld_once(reinterpret_cast<const f32x4*>(a.U + e));
-            o.rv[kb] = stc_ld_once(reinterpret_cast<const f32x4*>(a.R + e));
+            if constexpr (FIRST) o.rv[kb] = kZero4; else o.rv[kb] = stc_ld_once(reinterpret_cast<const f32x4*>(a.R + e));
             o.cv[kb] = stc_ld_once(reinterpret_cast<const f32x4*>(a.Cand + e));
             o.gv[kb] = stc_ld_once(reinterpret_cast<const f32x4*>(a.dHnew + e));
-            o.hv[kb] = stc_ld_once(reinterpret_cast<const f32x4*>(a.H + e));
+            if constexpr (FIRST) o.hv[kb] = kZero4; else o.hv[kb] = stc_ld_once(reinterpret_cast<const f32x4*>(a.H + e));
             o.bv[kb] = stc_ld_once(reinterpret_cast<const f32x4*>(a.dBm + e));
         }
     };
@@ -237,6 +246,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
 
         // =========================================================== candidate convolution (post-aggregation form): dA = dY, dBm given
         f32x4 drh[NRB];                                            // gradient of the R*H plane, row-on-lane layout
+        if constexpr (FIRST) { drh[0] = kZero4; drh[1] = kZero4; }      // (not formed: it only ever multiplies H = 0)
         float a_c = 1.f, sh_c = 1.f;                               // FmtH2: this node's gradient scale in the candidate phase, and a / a_n for the sums over nodes
         {
             DyFrag<NRB, 1> gr[K];
@@ -248,7 +258,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         v0[kb][i] = gv[kb][i] * uv[kb][i] * (1.f - cv[kb][i] * cv[kb][i]);      // dY = dHnew * U * (1 - Cand^2)
-                        rh_v[kb][i] = rv[kb][i] * hv[kb][i];
+                        if constexpr (!FIRST) rh_v[kb][i] = rv[kb][i] * hv[kb][i];
                     }
                     v1[kb] = bv[kb];
                 }
@@ -264,7 +274,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
                 }
                 to_acc(0, v0, d0);
                 to_acc(1, v1, d1);
-                to_acc(2, rh_v, rh_d);
+                if constexpr (!FIRST) to_acc(2, rh_v, rh_d);
 #pragma unroll
                 for (int kb = 0; kb < NRB; ++kb) {
                     gr[0].v[kb][0] = v0[kb]; gr[1].v[kb][0] = v1[kb];
@@ -287,15 +297,15 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
                     qb[n][rb] = F::split(gr[n].v[rb][0], qv);
                 }
             Op wc;                                                  // fragments fetched one step ahead of the products that use them
-            if (AHEAD) wc = F::get(WC, 0, lo);
+            if (AHEAD && LBC > 0) wc = F::get(WC, 0, lo);
 #pragma unroll
-            for (int lb = 0; lb < LBD; ++lb) {
+            for (int lb = 0; lb < LBC; ++lb) {
                 f32x4 z[NRB] = {kZero4, kZero4};
 #pragma unroll
                 for (int n = 0; n < K; ++n) {
                     const Op w = AHEAD ? wc : F::get(WC, n * LB + lb, lo);
                     const int nn = n + 1 < K ? n + 1 : 0, nlb = n + 1 < K ? lb : lb + 1;
-                    if (AHEAD && nlb < LBD) wc = F::get(WC, nn * LB + nlb, lo);
+                    if (AHEAD && nlb < LBC) wc = F::get(WC, nn * LB + nlb, lo);
 #pragma unroll
                     for (int rb = 0; rb < NRB; ++rb) z[rb] = F::mm(w, qb[n][rb], z[rb]);
                 }
@@ -318,6 +328,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
             }
 #pragma unroll
             for (int lb = 0; lb < LB; ++lb) {
+                if (FIRST && lb == RHB) continue;                  // rows of R*H = 0: the tiles stay exact zeros
                 f32x4 c0, c1;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
@@ -345,11 +356,12 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
                 for (int i = 0; i < 4; ++i) {
                     const float u = uv[kb][i], r = rv[kb][i], h = hv[kb][i], d = drh[kb][i];
                     v0[kb][i] = gv[kb][i] * (cv[kb][i] - h) * u * (1.f - u);
+                    if constexpr (FIRST) { v1[kb][i] = 0.f; continue; }      // dR carries the factor H = 0; nobody is owed dH
                     v1[kb][i] = d * h * r * (1.f - r);
                     own[i] = d * r + gv[kb][i] * (1.f - u);        // what H is owed directly: reset-gate path + its share of the blend
                     if constexpr (F::SCALED) own[i] *= kg;          // the H plane's gates tile starts from it (times the gates' scale, below)
                 }
-                stash_h[kb * 64 + lane] = make_float4(own[0], own[1], own[2], own[3]);
+                if constexpr (!FIRST) stash_h[kb * 64 + lane] = make_float4(own[0], own[1], own[2], own[3]);
             }
             if constexpr (F::SCALED) {                             // the gates' dY into the node's own scale
                 float m = 0.f;
@@ -363,7 +375,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
                 for (int kb = 0; kb < NRB; ++kb) { v0[kb] *= a_g; v1[kb] *= a_g; }
             }
             to_acc(3, v0, d0);
-            to_acc(4, v1, d1);
+            if constexpr (FIRST) { d1[0] = kZero4; d1[1] = kZero4; } else to_acc(4, v1, d1);
 #pragma unroll
             for (int kb = 0; kb < NRB; ++kb) {
                 gr.v[kb][0] = v0[kb]; gr.v[kb][1] = v1[kb];
@@ -386,7 +398,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
         for (int rb = 0; rb < NRB; ++rb) {
             const Op& t = rb == 0 ? tb0 : tb1;
 #pragma unroll
-            for (int hb = 0; hb < 2; ++hb) Qv[rb][hb] = F::mm(gd[hb], t, kZero4);
+            for (int hb = 0; hb < 2; ++hb) Qv[rb][hb] = (FIRST && hb == 1) ? kZero4 : F::mm(gd[hb], t, kZero4);      // (FIRST: gd[1] is the zero reset-gate half)
         }
         Op qb[2][NRB];                                             // step s: blocks (c = s, hb = 0), (c = s, hb = 1)
 #pragma unroll
@@ -395,11 +407,11 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
             qb[1][rb] = F::split(Qv[rb][0], Qv[rb][1]);
         }
         Op wg;
-        if (AHEAD) wg = F::get(WG, 0, lo);
+        if (AHEAD && LBC > 0) wg = F::get(WG, 0, lo);
 #pragma unroll
         for (int n = 0; n < K; ++n)
 #pragma unroll
-            for (int lb = 0; lb < LBD; ++lb) {
+            for (int lb = 0; lb < LBC; ++lb) {
                 f32x4 z[NRB];
 #pragma unroll
                 for (int rb = 0; rb < NRB; ++rb) {
@@ -420,7 +432,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
                 for (int s = 0; s < 2; ++s) {
                     const Op w = AHEAD ? wg : F::get(WG, (n * LB + lb) * 2 + s, lo);
                     if (AHEAD) {                                               // the next fragment in this loop nest's order: (n, lb, s) -> s, lb, n
-                        const int ns = s + 1 < 2 ? s + 1 : 0, nlb = s + 1 < 2 ? lb : (lb + 1 < LBD ? lb + 1 : 0), nn = (s + 1 < 2 || lb + 1 < LBD) ? n : n + 1;
+                        const int ns = s + 1 < 2 ? s + 1 : 0, nlb = s + 1 < 2 ? lb : (lb + 1 < LBC ? lb + 1 : 0), nn = (s + 1 < 2 || lb + 1 < LBC) ? n : n + 1;
                         if (nn < K) wg = F::get(WG, (nn * LB + nlb) * 2 + ns, lo);
                     }
 #pragma unroll
@@ -444,7 +456,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
             for (int rb = 0; rb < NRB; ++rb) {
                 const Op& t = rb == 0 ? tb0 : tb1;
 #pragma unroll
-                for (int hb = 0; hb < 2; ++hb) Qd[rb][hb] = F::mm(t, gd[hb], kZero4);
+                for (int hb = 0; hb < 2; ++hb) Qd[rb][hb] = (FIRST && hb == 1) ? kZero4 : F::mm(t, gd[hb], kZero4);
             }
 #pragma unroll
             for (int hb = 0; hb < 2; ++hb) qd[hb] = F::split(Qd[0][hb], Qd[1][hb]);
@@ -453,6 +465,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
         for (int n = 0; n < K; ++n)
 #pragma unroll
             for (int lb = 0; lb < LB; ++lb) {
+                if (FIRST && lb == RHB) continue;                  // rows of H = 0 ...
                 const float (&zc)[NRB][4] = zg[n][lb];
                 Op za;
                 if constexpr (F::SCALED) {
@@ -463,7 +476,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
 #pragma unroll
                 for (int c = 0; c < K; ++c)
 #pragma unroll
-                    for (int hb = 0; hb < 2; ++hb) dWg[n][lb][c][hb] = F::mm(za, c == 0 ? gd[hb] : qd[hb], dWg[n][lb][c][hb]);
+                    for (int hb = 0; hb < (FIRST ? 1 : 2); ++hb) dWg[n][lb][c][hb] = F::mm(za, c == 0 ? gd[hb] : qd[hb], dWg[n][lb][c][hb]);      // (... and the reset-gate columns: exact zeros)
             }
         cur = nxt;
         nxt = nx2;
@@ -492,13 +505,13 @@ __global__ __launch_bounds__(CB_THREADS, 1) void cell_bwd_x3_kernel(CellBwdArgs 
     }
 }
 
-template <class F, int L, int PL, int ACCX = 0, int ACCH = 0>
+template <class F, int L, int PL, int ACCX = 0, int ACCH = 0, int FIRST = 0>
 int launch_cell_bwd(const CellBwdArgs& a, int* n_partials, hipStream_t stream) {
     const size_t slabs = (size_t)CB_WAVES * (4 * L * 32 + 32) * sizeof(float);
     const size_t lds = cb_lds_bytes<F>() > slabs ? cb_lds_bytes<F>() : slabs;
     static_assert(cb_lds_bytes<F>() <= stc::kMaxLdsBytes, "tables + per-wave tiles must fit the CU's LDS");
     if (lds > stc::kMaxLdsBytes) return STC_NOT_HANDLED;
-    constexpr auto kern = cell_bwd_x3_kernel<F, L, PL, ACCX, ACCH>;
+    constexpr auto kern = cell_bwd_x3_kernel<F, L, PL, ACCX, ACCH, FIRST>;
     if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(cell bwd x3)", CB_THREADS, lds, 1, a.nodes, CB_WAVES, MF_BWD_MAX_GRID, n_partials)) return rc;
     hipLaunchKernelGGL(kern, dim3(*n_partials), dim3(CB_THREADS), lds, stream, a);
     STC_LAUNCH_CHECK("cell_bwd_x3 launch");
@@ -554,6 +567,28 @@ int stc_cell_bwd_planar_x3(const float* X, const float* H, const float* SX, cons
     }
     return fmt == STC_FMT_F16X2 ? dispatch_cell_bwd<FmtH2>(a, cin, accumulate_x, accumulate_h, n_partials, stream)
                                 : dispatch_cell_bwd<FmtB3>(a, cin, accumulate_x, accumulate_h, n_partials, stream);
+}
+
+// The first-step form (FIRST): the cell's state is the zero initial state.  No H, S.H, R operands and no dH, dS.H results exist.
+int stc_cell_bwd_first_x3(const float* X, const float* SX, const float* Tc, const float* Wg, const float* Wc,
+                          const float* U, const float* Cand, const float* dHnew, const float* dBm,
+                          float* dX, float* dSX, float* partial_g, float* partial_c, int* n_partials,
+                          int want_dbg, int want_dbc, int accumulate_x, int fmt, const float* zmax,
+                          long long nodes, int C, int Lw, hipStream_t stream) {
+    const int cin = Lw - 16;
+    if (!stc_cell_bwd_planar_shape_ok(C, 16) || nodes <= 0 || nodes >= (1ll << 31) / C || !(cin == 16 || (cin >= 1 && cin <= 4))) return STC_NOT_HANDLED;
+    const float* wide[] = {U, Cand, dHnew, dBm};
+    if (!all_aligned16(wide, 4)) return STC_NOT_HANDLED;
+    CellBwdArgs a{X, nullptr, SX, nullptr, U, nullptr, Cand, dHnew, dBm, Tc, Wg, Wc, dX, dSX, nullptr, nullptr, partial_g, partial_c, (int)nodes, want_dbg, want_dbc, Lw, zmax};
+    const bool h2 = fmt == STC_FMT_F16X2;
+    if (cin != 16) {
+        if (accumulate_x) return STC_NOT_HANDLED;       // a narrow input plane gets no gradient
+        return h2 ? launch_cell_bwd<FmtH2, 20, 2, 0, 0, 1>(a, n_partials, stream) : launch_cell_bwd<FmtB3, 20, 2, 0, 0, 1>(a, n_partials, stream);
+    }
+    const float* more[] = {X, SX, dX, dSX};
+    if (!dX || !dSX || !all_aligned16(more, 4)) return STC_NOT_HANDLED;
+    if (accumulate_x) return h2 ? launch_cell_bwd<FmtH2, 32, 1, 1, 0, 1>(a, n_partials, stream) : launch_cell_bwd<FmtB3, 32, 1, 1, 0, 1>(a, n_partials, stream);
+    return h2 ? launch_cell_bwd<FmtH2, 32, 1, 0, 0, 1>(a, n_partials, stream) : launch_cell_bwd<FmtB3, 32, 1, 0, 0, 1>(a, n_partials, stream);
 }
 
 #endif      // STC_CB_ACC2_UNIT

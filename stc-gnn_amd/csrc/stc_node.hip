@@ -556,6 +556,56 @@ extern "C" int stc_cell_bwd_planar_f32(const float* X, const float* H, const flo
     return stc::grad_tail_reduce(g, 2, n_parts, s);
 }
 
+// ---- first-step forms of the planar cell launches: the state is the zero initial state, so no H, S.H, R or R*H plane exists on either side
+extern "C" int stc_cell_first_supported(int32_t C, int32_t h) {
+    return stc_cell_bwd_planar_supported(C, h);      // (one shape for the forward and the backward form: C = 32, h = 16)
+}
+
+extern "C" int stc_cell_gates_fwd_first_f32(const float* X, const float* SX, const float* Tc, const float* W, const float* bias, float* U,
+                                            const float* Wc, const float* bc, float* A, float* Bm,
+                                            int32_t operand_format, float* act_amax,
+                                            int64_t nodes, int32_t C, int32_t Lw, int32_t h, void* stream) {
+    const stc::PlanarRow row(Lw, h);
+    if (int rc = check_dims(__func__, 2, 2, C, row.L, Lw, 2 * h, nodes)) return rc;
+    if (int rc = stc::check_operand_format(__func__, operand_format)) return rc;
+    if (int rc = row.check_width(__func__, STC_EINVAL)) return rc;
+    if (!stc_cell_first_supported(C, h)) return stc::fail(STC_EUNSUPPORTED, "stc_cell_gates_fwd_first_f32: C=%d h=%d is not built (C = 32, h = 16)", C, h);
+    if (nodes == 0) return STC_OK;
+    STC_REQUIRE(X && SX && Tc && W && U && Wc && A && Bm, STC_EINVAL, "stc_cell_gates_fwd_first_f32: null pointer");
+    const int rc = stc_cell_gates_fwd_first_x3(X, SX, Tc, W, bias, U, Wc, bc, A, Bm, operand_format, act_amax, nodes, C, Lw, static_cast<hipStream_t>(stream));
+    return stc::dispatched(__func__, rc);
+}
+
+extern "C" size_t stc_cell_bwd_first_workspace_bytes(int32_t C, int32_t Lw, int32_t h) {
+    return stc_cell_bwd_planar_workspace_bytes(C, Lw, h);      // (the same partial rows: dW and db at full shape)
+}
+
+extern "C" int stc_cell_bwd_first_f32(const float* X, const float* SX, const float* Tc, const float* Wg, const float* Wc,
+                                      const float* U, const float* Cand, const float* dHnew, const float* dBm,
+                                      float* dX, float* dSX, float* dWg, float* dbg, float* dWc, float* dbc,
+                                      int32_t accumulate_x, int32_t operand_format, const float* act_amax,
+                                      void* workspace, size_t workspace_bytes,
+                                      int64_t nodes, int32_t C, int32_t Lw, int32_t h, void* stream) {
+    const stc::PlanarRow row(Lw, h);
+    if (int rc = check_dims(__func__, 2, 2, C, row.L, Lw, 2 * h, nodes)) return rc;
+    if (int rc = stc::check_operand_format(__func__, operand_format)) return rc;
+    if (int rc = row.check_width(__func__, STC_EINVAL)) return rc;
+    if (!stc_cell_first_supported(C, h)) return stc::fail(STC_EUNSUPPORTED, "stc_cell_bwd_first_f32: C=%d h=%d is not built (C = 32, h = 16)", C, h);
+    STC_REQUIRE(Wg && Wc && dWg && dWc && Tc, STC_EINVAL, "stc_cell_bwd_first_f32: null W/dW/Tc");
+    STC_REQUIRE(!accumulate_x || !row.narrow, STC_EINVAL, "stc_cell_bwd_first_f32: accumulate_x with a narrow input plane (it gets no gradient)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    stc::ParamGrad g[2] = {{dWg, dbg, 4 * Lw * 2 * h, 2 * h, stc_bdg_node_bwd_workspace_bytes(2, 2, C, row.L, 2 * h, 0)},       // gates, then candidate:
+                           {dWc, dbc, 4 * Lw * h, h, stc_bdg_node_bwd_workspace_bytes(2, 2, C, row.L, h, 0)}};                 // stc_cell_bwd_first_workspace_bytes
+    bool done;
+    if (int rc = stc::grad_tail_begin(__func__, g, 2, nodes, workspace, workspace_bytes, STC_EALIGN, s, &done); rc || done) return rc;
+    STC_REQUIRE(X && SX && U && Cand && dHnew && dBm && (row.narrow || (dX && dSX)), STC_EINVAL, "stc_cell_bwd_first_f32: null pointer");
+    int n_parts = 0;
+    if (int rc = stc::dispatched(__func__, stc_cell_bwd_first_x3(X, SX, Tc, Wg, Wc, U, Cand, dHnew, dBm, dX, dSX, g[0].partial, g[1].partial, &n_parts,
+                                                                 dbg != nullptr, dbc != nullptr, accumulate_x != 0, operand_format, act_amax, nodes, C, Lw, s)))
+        return rc;
+    return stc::grad_tail_reduce(g, 2, n_parts, s);
+}
+
 // ---- planar cell convolutions of Chebyshev order K (= 3; K = 2 has the entry points above): see stc_cell_conv_*_planar_k_x3
 extern "C" int stc_cell_planar_k_supported(int32_t K, int32_t C, int32_t h) {
     return (x3_enabled() && stc_cell_planar_k_shape_ok(K, C, h)) ? 1 : 0;

@@ -96,6 +96,17 @@ int stc_cell_bwd_planar_x3(const float* X, const float* H, const float* SX, cons
                            int want_dbg, int want_dbc, int accumulate_x, int accumulate_h, int fmt, const float* zmax,
                            long long nodes, int C, int Lw, hipStream_t stream);
 
+// First-step forms of the two launches (stc_node_x3.hip, stc_cell_bwd_x3.hip; C = 32): the cell's state is the zero initial state, so no H, S.H,
+// R or R*H plane exists on either side.
+int stc_cell_gates_fwd_first_x3(const float* X, const float* SX, const float* Tc, const float* W, const float* bias, float* U,
+                                const float* Wc, const float* bc, float* A, float* Bm, int fmt, float* zmax,
+                                long long nodes, int C, int Lw, hipStream_t stream);
+int stc_cell_bwd_first_x3(const float* X, const float* SX, const float* Tc, const float* Wg, const float* Wc,
+                          const float* U, const float* Cand, const float* dHnew, const float* dBm,
+                          float* dX, float* dSX, float* partial_g, float* partial_c, int* n_partials,
+                          int want_dbg, int want_dbc, int accumulate_x, int fmt, const float* zmax,
+                          long long nodes, int C, int Lw, hipStream_t stream);
+
 // Planar cell convolutions of order K = 3 (stc_node_x3.hip): Zx[n] / Zh[n] = T_n(S) of the X-side / H-side plane; mode 1 gates, 2 candidate.
 int stc_cell_planar_k_shape_ok(int K, int C, int h);
 int stc_cell_conv_fwd_planar_k_x3(const float* const* Zx, const float* const* Zh, int K, const float* Tc, const float* W, const float* bias, int mode,

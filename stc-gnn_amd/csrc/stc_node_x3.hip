@@ -65,6 +65,14 @@ struct Row8 {
             a = f32x4{x0, x1, x2, x3};
         }
     }
+    // ... and with no state plane at all (the first-step form: the state is zero): [0 | the narrow input columns | 0], lane group 2 alone loads
+    __device__ __forceinline__ void load_narrow_only(const float* __restrict__ xrow, int cin, int g) {
+        a = kZero4; b = kZero4;
+        if (g == 2) {
+            const float x0 = xrow[0], x1 = cin > 1 ? xrow[1] : 0.f, x2 = cin > 2 ? xrow[2] : 0.f, x3 = cin > 3 ? xrow[3] : 0.f;
+            a = f32x4{x0, x1, x2, x3};
+        }
+    }
     __device__ __forceinline__ float at(int e) const { return e < 4 ? a[e & 3] : b[e & 3]; }
     __device__ __forceinline__ void fma(float v, const Row8& o) {
 #pragma unroll
@@ -94,13 +102,19 @@ __host__ __device__ constexpr int piece_slot_row(bool pieces, int gg, int e) { r
 // (W's blocks c = 0 carry sW sT, blocks c >= 1 carry sW, T_c carries sT: projection and category mix then meet in one accumulator with the
 // common factor sW sT, taken out in the epilogue); activations carry one power of two per NODE, from the node's own maximum (the
 // reference's einsum is scale-free, two fp16 pieces are not: stc_x3_frag.h), taken out in the same epilogue.
-template <int NB2, int HB, int K, int L, int EPI, int PL = 0, int POST = 0, class F = FmtB3>
+//
+// FIRST (planar gates kernel with POST): the cell's state is the zero initial state (the first time step of every layer).  The state planes
+// are not read (their pointers may be null) and their row slots carry zeros; the reset gate, which only ever multiplies H = 0, is neither
+// projected nor stored, and the candidate's input is [X | 0].  U, A and Bm come from the products the general kernel issues, in its order:
+// the same bits as a launch on explicit zero planes.  The state planes' activation-maximum slots stay at the buffer's zero.
+template <int NB2, int HB, int K, int L, int EPI, int PL = 0, int POST = 0, class F = FmtB3, int FIRST = 0>
 __global__ __launch_bounds__(MF_THREADS, (NB2 == 1 ? 2 : 1)) void node_fwd_x3_kernel(
     ZPtrs Z, const float* __restrict__ Tc, const float* __restrict__ W, const float* __restrict__ bias,
     float* __restrict__ Y, int nodes, int Lw, FwdEpi epi, PostArgs post) {
     using Op = typename F::Op;
     constexpr int NP = F::NP;
     static_assert(!POST || (PL != 0 && EPI == EPI_GATES && K == 2), "the fused candidate projection belongs to the planar gates kernel");
+    static_assert(!FIRST || POST, "the first-step form belongs to the planar gates kernel with its candidate projection");
     constexpr int KL = K;                               // slabs read from HBM
     constexpr int NRB = 2 * NB2, C = 32 * NB2, Ho = 16 * HB, NCB = K * HB;
     constexpr int HID = 16;
@@ -184,7 +198,13 @@ __global__ __launch_bounds__(MF_THREADS, (NB2 == 1 ? 2 : 1)) void node_fwd_x3_ke
         for (int n = 0; n < KL; ++n)
 #pragma unroll
             for (int rb = 0; rb < NRB; ++rb) {
-                if constexpr (PL == 1) z[n][rb].load_pieces(Z.p[n] + ((size_t)nd * C + 16 * rb + x) * 16, Z.q[n] + ((size_t)nd * C + 16 * rb + x) * 16, g);
+                if constexpr (FIRST && PL == 1) {                  // [X piece | 0]
+                    z[n][rb].a = stc_ld_once(reinterpret_cast<const f32x4*>(Z.p[n] + ((size_t)nd * C + 16 * rb + x) * 16 + 4 * g));
+                    z[n][rb].b = kZero4;
+                } else if constexpr (FIRST) {                      // [0 | the narrow input columns | pad]
+                    z[n][rb].load_narrow_only(Z.q[n] + ((size_t)nd * C + 16 * rb + x) * (Lw - 16), Lw - 16, g);
+                }
+                else if constexpr (PL == 1) z[n][rb].load_pieces(Z.p[n] + ((size_t)nd * C + 16 * rb + x) * 16, Z.q[n] + ((size_t)nd * C + 16 * rb + x) * 16, g);
                 else if constexpr (PL == 2) z[n][rb].load_planes_narrow(Z.p[n] + ((size_t)nd * C + 16 * rb + x) * 16,
                                                                         Z.q[n] + ((size_t)nd * C + 16 * rb + x) * (Lw - 16), Lw - 16, g);
                 else z[n][rb].load(Z.p[n] + ((size_t)nd * C + 16 * rb + x) * L, g);
@@ -202,7 +222,7 @@ __global__ __launch_bounds__(MF_THREADS, (NB2 == 1 ? 2 : 1)) void node_fwd_x3_ke
         // EPI_GATES: lane x < L - 16 also writes one column of CandIn outside the R*H block, in the same row layout:
         // column x of Xt (re-read from slab 0, an L2 hit) while x < cin, else the zero of pad column x + 16
         const bool has_side = EPI == EPI_GATES && !PL && x < L - HID;
-        if constexpr (HT) {
+        if constexpr (HT && !FIRST) {
             if constexpr (PIECES) {                                // every lane holds the piece g of its H row
 #pragma unroll
                 for (int rb = 0; rb < NRB; ++rb) *reinterpret_cast<f32x4*>(th + ((wave * NRB + rb) * 16 + x) * TRS + 4 * g) = cur[0][rb].b;
@@ -271,6 +291,7 @@ __global__ __launch_bounds__(MF_THREADS, (NB2 == 1 ? 2 : 1)) void node_fwd_x3_ke
             }
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) {
+                if (FIRST && cb % HB == HB - 1) continue;          // the reset gate's columns
                 const Op w = F::get(Wx, n * NCB + cb, lo);
 #pragma unroll
                 for (int rb = 0; rb < NRB; ++rb) acc[rb][cb] = F::mm(za[rb], w, acc[rb][cb]);
@@ -281,7 +302,7 @@ __global__ __launch_bounds__(MF_THREADS, (NB2 == 1 ? 2 : 1)) void node_fwd_x3_ke
 #pragma unroll
         for (int c1 = 0; c1 < K - 1; ++c1)
 #pragma unroll
-            for (int hb = 0; hb < HB; ++hb)
+            for (int hb = 0; hb < (FIRST ? HB - 1 : HB); ++hb)
 #pragma unroll
                 for (int p = 0; p < NB2; ++p) {
                     const Op u = F::split(acc[2 * p][(c1 + 1) * HB + hb], acc[2 * p + 1][(c1 + 1) * HB + hb]);
@@ -323,6 +344,7 @@ __global__ __launch_bounds__(MF_THREADS, (NB2 == 1 ? 2 : 1)) void node_fwd_x3_ke
 #pragma unroll
                     for (int r = 0; r < 4; ++r) uu[rb][r] = fast_sigmoid(F::SCALED ? fmaf(acc[rb][0][r], invn, bv[0]) : acc[rb][0][r] + bv[0]);
                 put_plane(epi.U_out, uu);
+                if constexpr (!FIRST) {
 #pragma unroll
                 for (int rb = 0; rb < NRB; ++rb)
 #pragma unroll
@@ -346,6 +368,7 @@ __global__ __launch_bounds__(MF_THREADS, (NB2 == 1 ? 2 : 1)) void node_fwd_x3_ke
                     }
                 } else {
                     put_plane(epi.CandIn, gt);
+                }
                 }
             } else {
 #pragma unroll
@@ -371,7 +394,10 @@ __global__ __launch_bounds__(MF_THREADS, (NB2 == 1 ? 2 : 1)) void node_fwd_x3_ke
                     // ADDRESSES instead: cur[0] was stored to scratch on every node -- 64 B x 64 lanes x 250 880 nodes = 1.03 GB of
                     // dead stores per launch, the 1.39x HBM traffic rocprofv3 showed for this kernel, profiles/r02/.)
                     f32x4 a4, b4;
-                    if constexpr (PIECES) {                                               // piece order: [Xt columns 4g.. | R*H columns 4g..]
+                    if constexpr (FIRST) {                                                // [Xt | 0] / [0 | x | 0]: R*H = 0, the rows as they were loaded
+                        a4 = cur[0][rb].a;
+                        b4 = kZero4;
+                    } else if constexpr (PIECES) {                                               // piece order: [Xt columns 4g.. | R*H columns 4g..]
                         a4 = cur[0][rb].a;
                         b4 = *reinterpret_cast<const f32x4*>(tr + ((wave * NRB + rb) * 16 + x) * TRS + 4 * g);
                     } else {
@@ -453,7 +479,10 @@ __global__ __launch_bounds__(MF_THREADS, (NB2 == 1 ? 2 : 1)) void node_fwd_x3_ke
         if (epi.zmax) {                                          // rows [p planes of slab 0..K-1 | q planes of slab 0..K-1], launch order of Z
             const int slot = blockIdx.x * MF_WAVES + wave;
 #pragma unroll
-            for (int n = 0; n < KL; ++n) { leave_max(epi.zmax + n * STC_ACT_SLOTS, slot, pmax[n]); leave_max(epi.zmax + (KL + n) * STC_ACT_SLOTS, slot, qmax[n]); }
+            for (int n = 0; n < KL; ++n) {
+                if (!(FIRST && PL == 2)) leave_max(epi.zmax + n * STC_ACT_SLOTS, slot, pmax[n]);
+                if (!(FIRST && PL == 1)) leave_max(epi.zmax + (KL + n) * STC_ACT_SLOTS, slot, qmax[n]);
+            }
         }
     }
 }
@@ -1275,14 +1304,14 @@ __global__ __launch_bounds__(MF_THREADS, (NB2 == 1 ? 2 : 1)) void node_bwd2_x3_k
 }
 
 // --------------------------------------------------------------------------------------- host side
-template <int NB2, int HB, int K, int L, int EPI = EPI_NONE, int PL = 0, int POST = 0, class F = FmtB3>
+template <int NB2, int HB, int K, int L, int EPI = EPI_NONE, int PL = 0, int POST = 0, class F = FmtB3, int FIRST = 0>
 int launch_fwd(const float* const* Z, const float* Tc, const float* W, const float* bias, float* Y,
                long long nodes, int Lw, hipStream_t stream, FwdEpi epi = FwdEpi{}, PostArgs post = PostArgs{}) {
     constexpr int NRB = 2 * NB2, NCB = K * HB;
     const size_t lds = (size_t)(K * NCB + (K - 1) * NRB * NB2 + (POST ? K * K : 0)) * F::NP * 64 * 16
                        + ((POST ? 1 : 0) + (EPI == EPI_GATES && PL != 0 ? 1 : 0)) * (size_t)MF_WAVES * NRB * 16 * 20 * 4;      // R*H tile (POST), H tile (planar gates)
     if (lds > stc::kMaxLdsBytes) return STC_NOT_HANDLED;
-    constexpr auto kern = node_fwd_x3_kernel<NB2, HB, K, L, EPI, PL, POST, F>;
+    constexpr auto kern = node_fwd_x3_kernel<NB2, HB, K, L, EPI, PL, POST, F, FIRST>;
     int grid;
     if (int rc = stc::persistent_grid<kern>("hipFuncSetAttribute(node fwd x3)", MF_THREADS, lds, 2, nodes, MF_WAVES, INT_MAX, &grid)) return rc;
     ZPtrs zp{};
@@ -1562,6 +1591,28 @@ int stc_cell_gates_fwd_planar_x3(const float* X, const float* H, const float* SX
     epi.H = H; epi.U_out = U; epi.R_out = R; epi.CandIn = RH; epi.cin = cin; epi.zmax = zmax;
     return fmt == STC_FMT_F16X2 ? gates_fwd_planar_go<FmtH2>(X, H, SX, SH, Tc, W, bias, epi, post, fused, cin, nodes, C, Lw, stream)
                                 : gates_fwd_planar_go<FmtB3>(X, H, SX, SH, Tc, W, bias, epi, post, fused, cin, nodes, C, Lw, stream);
+}
+
+// The first-step form: no state planes, no reset gate, no R*H (C = 32; the candidate's projection always rides along).
+int stc_cell_gates_fwd_first_x3(const float* X, const float* SX, const float* Tc, const float* W, const float* bias, float* U,
+                                const float* Wc, const float* bc, float* A, float* Bm, int fmt, float* zmax,
+                                long long nodes, int C, int Lw, hipStream_t stream) {
+    const int cin = Lw - 16;
+    if (C != 32 || !x3_cell_shape(2, C, cin == 16 ? 32 : 20, nodes) || !(cin == 16 || (cin >= 1 && cin <= 4))) return STC_NOT_HANDLED;
+    if (!(stc::aligned16(U) && stc::aligned16(A) && stc::aligned16(Bm))) return STC_NOT_HANDLED;
+    const PostArgs post{Wc, bc, A, Bm};
+    FwdEpi epi{};
+    epi.U_out = U; epi.cin = cin; epi.zmax = zmax;
+    const bool h2 = fmt == STC_FMT_F16X2;
+    if (cin == 16) {
+        const float* Z[4] = {X, SX, nullptr, nullptr};
+        if (!all_aligned16(Z, 2)) return STC_NOT_HANDLED;
+        return h2 ? launch_fwd<1, 2, 2, 32, EPI_GATES, 1, 1, FmtH2, 1>(Z, Tc, W, bias, nullptr, nodes, Lw, stream, epi, post)
+                  : launch_fwd<1, 2, 2, 32, EPI_GATES, 1, 1, FmtB3, 1>(Z, Tc, W, bias, nullptr, nodes, Lw, stream, epi, post);
+    }
+    const float* Z[4] = {nullptr, nullptr, X, SX};
+    return h2 ? launch_fwd<1, 2, 2, 20, EPI_GATES, 2, 1, FmtH2, 1>(Z, Tc, W, bias, nullptr, nodes, Lw, stream, epi, post)
+              : launch_fwd<1, 2, 2, 20, EPI_GATES, 2, 1, FmtB3, 1>(Z, Tc, W, bias, nullptr, nodes, Lw, stream, epi, post);
 }
 
 template <class F>

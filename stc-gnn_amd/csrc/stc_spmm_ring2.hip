@@ -55,16 +55,17 @@ struct Ring2Args {
 // What the first ring computes from the gathered sum and the slot's own operands, and which of it the second aggregation takes:
 //   R2_SUM    dH = sum + addends (stored for interior rows);            V = dH U (1 - Cand^2)              -> Z = S.V = dBm
 //   R2_BLEND  Cand = tanh(sum + A), Hnew = (1 - U) H + U Cand (both stored, Cand if Y is given: the forward of stc_spmm_blend_fwd_f32);  V = Hnew  -> Z = S.Hnew
+//   R2_BLEND0 the blend form on the zero initial state (a cell's first time step): Hnew = U Cand, no H operand
 //   R2_CHAIN  V = alpha1 sum + addends (stored for interior rows if Y is given)   -> Z = alpha2 S.V + sum_k scale0[k] add0[k]: two chained
 //             aggregations of the order-3 feature recurrence -- forward 2 S.(S.X) - X (STC_GNN.py:24-29 applied to the feature side, :37), and
 //             its transpose in Clenshaw form, d0 - d2 + S^T (d1 + 2 S^T d2)
-enum { R2_SUM = 0, R2_BLEND = 1, R2_CHAIN = 2 };
+enum { R2_SUM = 0, R2_BLEND = 1, R2_CHAIN = 2, R2_BLEND0 = 3 };
 
 __device__ __forceinline__ void lds_only_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int MODE, bool HAS_A2, int NADD, int N0 = 0>                 // NADD: addends of the first ring;  N0: of the interior (CHAIN)
 __global__ __launch_bounds__(R2_THREADS, 2) void ring2_sum_kernel(Ring2Args a) {
-    static_assert(MODE != R2_BLEND || (NADD == 1 && !HAS_A2), "the blend form: one addend (A), one gathered operand (Bm)");
+    static_assert((MODE != R2_BLEND && MODE != R2_BLEND0) || (NADD == 1 && !HAS_A2), "the blend forms: one addend (A), one gathered operand (Bm)");
     static_assert((MODE == R2_CHAIN) == (N0 > 0), "interior addends: the chain form, at least one");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     v4f* tile = reinterpret_cast<v4f*>(lds);                                           // [96][32] staged rows, then [64][32] dY
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(R2_THREADS, 2) void ring2_sum_kernel(Ring2Args a) {
     // The first ring's own operands (addends, U, Cand: NADD + 2 pieces per slot) are requested ONE SLOT AHEAD, and the next chunk's staged rows
     // only after the last slot's request: memory returns in issue order, so a slot's request made behind the staging request waits for 12 rows
     // from HBM (the first version: one exposed latency per slot; holding all eight slots' operands a chunk ahead spilled 120 registers).
-    constexpr int NOP = MODE == R2_CHAIN ? NADD : NADD + 2, NOPA = NOP > 0 ? NOP : 1;
+    constexpr int NOP = MODE == R2_CHAIN ? NADD : MODE == R2_BLEND0 ? NADD + 1 : NADD + 2, NOPA = NOP > 0 ? NOP : 1;
     auto slot_at = [&](int i, int chunk) { return l1_off[i] + (unsigned)(chunk * R2_Q); };
     auto request_slot = [&](v4f (&o)[NOPA], int i, int chunk) {
         const unsigned at = slot_at(i, chunk);
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(R2_THREADS, 2) void ring2_sum_kernel(Ring2Args a) {
         for (int k = 0; k < NADD; ++k) o[k] = a.add[k][at];
         if constexpr (MODE != R2_CHAIN) {
             o[NADD] = a.U[at];
-            o[NADD + 1] = a.Cand[at];
+            if constexpr (MODE != R2_BLEND0) o[NADD + 1] = a.Cand[at];
         }
     };
     v4f opn[NOPA];
@@ -165,11 +166,15 @@ __global__ __launch_bounds__(R2_THREADS, 2) void ring2_sum_kernel(Ring2Args a) {
                 if (interior) __builtin_nontemporal_store(dh, a.Y + slot_at(i, chunk));
 #pragma unroll
                 for (int c = 0; c < 4; ++c) dy[i][c] = dh[c] * u[c] * (1.f - cd[c] * cd[c]);
-            } else {                                                                   // cd = the previous state H
-                const v4f u = cur[NOPA - 2], cd = cur[NOPA - 1];
+            } else {                                                                   // cd = the previous state H (BLEND0: zero, not read)
+                const v4f u = cur[NADD], cd = MODE == R2_BLEND0 ? v4f{0.f, 0.f, 0.f, 0.f} : cur[NOPA - 1];
                 v4f cand;
 #pragma unroll
-                for (int c = 0; c < 4; ++c) { cand[c] = stc_tanh(dh[c]); dy[i][c] = (1.f - u[c]) * cd[c] + u[c] * cand[c]; }
+                for (int c = 0; c < 4; ++c) {
+                    cand[c] = stc_tanh(dh[c]);
+                    if constexpr (MODE == R2_BLEND0) dy[i][c] = u[c] * cand[c];           // (the blend's value at H = 0, whichever way it is contracted)
+                    else dy[i][c] = (1.f - u[c]) * cd[c] + u[c] * cand[c];
+                }
                 if (interior) {
                     if (a.Y != nullptr) __builtin_nontemporal_store(cand, a.Y + slot_at(i, chunk));      // (Cand is optional: only a backward reads it)
                     __builtin_nontemporal_store(dy[i], a.Y2 + slot_at(i, chunk));
@@ -219,8 +224,8 @@ int launch_ring2(const Ring2Args& a, int batch, hipStream_t s, int n_add0 = 0) {
     static_assert((size_t)R2_L2 * R2_Q * 16 + (size_t)(R2_L1 + R2_INT) * R2_W * sizeof(int2) <= 64 * 1024, "within the default dynamic-LDS limit: no attribute to set");
     using Kernel = void (*)(Ring2Args);
     Kernel kern = nullptr;
-    if constexpr (MODE == R2_BLEND) {
-        kern = ring2_sum_kernel<R2_BLEND, false, 1>;
+    if constexpr (MODE == R2_BLEND || MODE == R2_BLEND0) {
+        kern = ring2_sum_kernel<MODE, false, 1>;
     } else if constexpr (MODE == R2_CHAIN) {
         static constexpr Kernel table[3][R2_MAX_ADD] = {
 #define STC_R2_ROW(NA) {ring2_sum_kernel<R2_CHAIN, HAS_A2, NA, 1>, ring2_sum_kernel<R2_CHAIN, HAS_A2, NA, 2>, ring2_sum_kernel<R2_CHAIN, HAS_A2, NA, 3>, \
@@ -258,6 +263,10 @@ int check_ring2(const char* who, const void* l2_rows, const void* l1_rows, const
 }
 
 }  // namespace
+
+// The first-step blend lives in a translation unit of its own (stc_spmm_ring2_first.hip = this file with STC_RING2_FIRST_UNIT defined), as the
+// both-sides cell backward does: this unit keeps exactly the forms it had (tests/test_isa.py counts them: 12 sums, the blend, 30 chains).
+#if !defined(STC_RING2_FIRST_UNIT)
 
 extern "C" int stc_ring2_sum_f32(const int32_t* l2_rows, const int32_t* l1_rows, const int32_t* int_rows, const int32_t* t1, const int32_t* t2,
                                  int32_t n_patches, int32_t n_rows,
@@ -351,3 +360,34 @@ extern "C" int stc_ring2_chain_f32(const int32_t* l2_rows, const int32_t* l1_row
     hipStream_t s = static_cast<hipStream_t>(stream);
     return A2 ? launch_ring2<R2_CHAIN, true>(a, batch, s, n_add0) : launch_ring2<R2_CHAIN, false>(a, batch, s, n_add0);
 }
+
+#else      // STC_RING2_FIRST_UNIT
+
+extern "C" int stc_ring2_blend_first_f32(const int32_t* l2_rows, const int32_t* l1_rows, const int32_t* int_rows, const int32_t* t1, const int32_t* t2,
+                                         int32_t n_patches, int32_t n_rows,
+                                         const float* Bm, const float* A, const float* U,
+                                         float* Cand, float* Hnew, float* SHnew,
+                                         int32_t batch, int32_t C, int32_t h, void* stream) {
+    if (int rc = check_ring2("stc_ring2_blend_first_f32", l2_rows, l1_rows, int_rows, t1, t2, n_patches, n_rows, batch, C, h)) return rc;
+    if (batch == 0 || n_rows == 0) return STC_OK;
+    STC_REQUIRE(Bm && A && U && Hnew && SHnew, STC_EINVAL, "stc_ring2_blend_first_f32: null pointer");      // (Cand may be null: not stored)
+    for (const void* q : {(const void*)Bm, (const void*)A, (const void*)U, (const void*)Cand, (const void*)Hnew, (const void*)SHnew})
+        STC_REQUIRE(stc::aligned16(q), STC_EALIGN, "stc_ring2_blend_first_f32: planes must be 16-byte aligned");
+    for (const float* out : {Cand, Hnew, SHnew})
+        STC_REQUIRE(out != Bm && out != A && out != U, STC_EINVAL, "stc_ring2_blend_first_f32: a result aliases an operand (the first ring re-reads them)");
+    STC_REQUIRE(Cand != Hnew && Cand != SHnew && Hnew != SHnew, STC_EINVAL, "stc_ring2_blend_first_f32: results alias each other");
+    Ring2Args a{};
+    a.pl = Ring2Plan{l2_rows, l1_rows, int_rows, t1, t2, n_patches};
+    a.A = reinterpret_cast<const v4f*>(Bm);
+    a.n_add = 1;
+    a.add[0] = reinterpret_cast<const v4f*>(A);
+    a.U = reinterpret_cast<const v4f*>(U);
+    a.Y = reinterpret_cast<v4f*>(Cand);
+    a.Y2 = reinterpret_cast<v4f*>(Hnew);
+    a.Z = reinterpret_cast<v4f*>(SHnew);
+    a.n = n_rows;
+    a.F4 = C * h / 4;
+    return launch_ring2<R2_BLEND0, false>(a, batch, static_cast<hipStream_t>(stream));
+}
+
+#endif      // STC_RING2_FIRST_UNIT

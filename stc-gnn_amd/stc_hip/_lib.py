@@ -22,7 +22,7 @@ from .graph import is_full_pattern
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, 'libstc_hip.so')
 # Mirrors of include/stc_hip.h (#define STC_<name>; tests/test_abi.py compares each, and HipKernels.ACT_AMAX_SLOTS, with the header)
-ABI_VERSION = 36
+ABI_VERSION = 37
 FMT_BF16X3, FMT_F16X2 = 0, 1          # operand formats of the split-operand matrix-core kernels
 MAX_K = 4
 SPMM_SUM_MAX_ADD, SPMM_SUM_BF16_MAX_ADD, RING2_MAX_ADD = 8, 5, 5      # addends of stc_spmm_sum_f32 / _bf16 and of the two-ring launches
@@ -57,6 +57,7 @@ _ABI = {
     'stc_csr_sddmm_f32': (_int, [_p, _p, _i32, _i32, _p, _p, _p, _i32, _i32, _f32, _i32, _p]),
     'stc_ring2_sum_f32': (_int, [_p] * 5 + [_i32, _i32, _p, _p, _i32, _pp, _p, _p, _p, _p, _i32, _i32, _i32, _p]),
     'stc_ring2_blend_f32': (_int, [_p] * 5 + [_i32, _i32] + [_p] * 7 + [_i32, _i32, _i32, _p]),
+    'stc_ring2_blend_first_f32': (_int, [_p] * 5 + [_i32, _i32] + [_p] * 6 + [_i32, _i32, _i32, _p]),
     'stc_ring2_chain_f32': (_int, [_p] * 5 + [_i32, _i32, _p, _p, _f32, _i32, _pp, _p, _f32, _i32, _pp, _pf, _p, _i32, _i32, _i32, _p]),
     'stc_spmm_blend_fwd_f32': (_int, [_p] * 6 + [_i32, _i32] + [_p] * 6 + [_p, _i32, _i32, _p, _i32, _p, _i32, _i32] + [_i32] * 3 + [_p]),
     'stc_spmm_blend_fwd_bf16': (_int, [_p] * 6 + [_i32, _i32] + [_p] * 6 + [_i32] * 3 + [_p]),
@@ -86,6 +87,10 @@ _ABI = {
     'stc_cell_bwd_planar_supported': (_int, [_i32, _i32]),
     'stc_cell_bwd_planar_workspace_bytes': (_size, [_i32, _i32, _i32]),
     'stc_cell_bwd_planar_f32': (_int, [_p] * 20 + [_i32, _i32, _i32, _p, _p, _size, _i64, _i32, _i32, _i32, _p]),
+    'stc_cell_first_supported': (_int, [_i32, _i32]),
+    'stc_cell_gates_fwd_first_f32': (_int, [_p] * 10 + [_i32, _p, _i64, _i32, _i32, _i32, _p]),
+    'stc_cell_bwd_first_workspace_bytes': (_size, [_i32, _i32, _i32]),
+    'stc_cell_bwd_first_f32': (_int, [_p] * 15 + [_i32, _i32, _p, _p, _size, _i64, _i32, _i32, _i32, _p]),
     'stc_cell_planar_bf16_supported': (_int, [_i32, _i32, _i32, _i32]),
     'stc_cell_gates_fwd_planar_bf16': (_int, [_p] * 14 + [_i64, _i32, _i32, _i32, _p]),
     'stc_cell_gates_bwd_planar_bf16': (_int, [_p] * 11 + [_pp, _p, _p, _p, _p, _size, _i64, _i32, _i32, _i32, _p]),
@@ -237,6 +242,9 @@ class HipKernels:
     #: ``cell_gates_fwd_planar_k``, ``Cand`` of ``spmm_blend_fwd``, ``ring2_blend`` and ``cell_cand_fwd_planar_k`` -- what the forward-only route of
     #: ``ops.stc_cell_graph`` asks before it passes one (the bf16 set has no such attribute: its planes are all required)
     optional_gate_stores = True
+    #: the first-step forms exist (ABI v37): ``cell_gates_fwd_first``, ``ring2_blend_first`` and ``cell_bwd_first`` run a cell whose state is the
+    #: zero initial state without the H, S.H, R planes and their gradients -- what ``ops.stc_cell_graph`` asks before it routes a cell there
+    first_step_cells = True
 
     def __init__(self):
         self.lib = load_library()
@@ -498,6 +506,15 @@ class HipKernels:
         self._same_device(Bm, A, U, H, Cand, Hnew, SHnew)
         self._launch('stc_ring2_blend_f32', H, *self._ring2_ptrs('ring2_blend', ring2, H), n, _ptr(Bm), _ptr(A), _ptr(U), _ptr(H), _ptr(Cand), _ptr(Hnew), _ptr(SHnew),
                      B, Cc, h, nbytes=colidx.numel() * 8 + 4 * (n + 1) + 4 * B * n * Cc * h * (6 + (Cand is not None)))
+
+    def ring2_blend_first(self, rowptr, colidx, val, ring2, Bm, A, U, Cand, Hnew, SHnew):
+        """``ring2_blend`` on the zero initial state (stc_ring2_blend_first_f32): Cand = tanh(A + S.Bm), Hnew = U Cand, SHnew = S.Hnew; no H operand."""
+        B, n, Cc, h = U.shape
+        for name, t in (('Bm', Bm), ('A', A), ('U', U), ('Hnew', Hnew), ('SHnew', SHnew)) + ((('Cand', Cand),) if Cand is not None else ()):
+            _tensor('ring2_blend_first.' + name, t, (B, n, Cc, h))           # Cand None: not stored
+        self._same_device(Bm, A, U, Cand, Hnew, SHnew)
+        self._launch('stc_ring2_blend_first_f32', U, *self._ring2_ptrs('ring2_blend_first', ring2, U), n, _ptr(Bm), _ptr(A), _ptr(U), _ptr(Cand), _ptr(Hnew),
+                     _ptr(SHnew), B, Cc, h, nbytes=colidx.numel() * 8 + 4 * (n + 1) + 4 * B * n * Cc * h * (5 + (Cand is not None)))
 
     def ring2_chain(self, rowptr, colidx, val, ring2, X, X2, alpha1, add1, V, alpha2, add0, Z):
         """V = alpha1 S.(X [+ X2]) + sum(add1) and Z = alpha2 S.V + sum(scale * t for (t, scale) in add0) in one launch (stc_ring2_chain_f32): the
@@ -895,6 +912,69 @@ class HipKernels:
         self._launch('stc_cell_bwd_planar_f32', H, _ptr(X), _ptr(H), _ptr(SX), _ptr(SH), _ptr(Tc), _ptr(Wg), _ptr(Wc), _ptr(U), _ptr(Rg), _ptr(Cand),
                      _ptr(dHnew), _ptr(dBm), *[_ptr(z) for z in dZs], _ptr(dWg), _ptr(dbg), _ptr(dWc), _ptr(dbc), int(bool(accumulate_x)), int(bool(accumulate_h)),
                      self.operand_format, self._act_amax('cell_bwd', act_amax, 4, H), _ptr(ws), ws.numel(), R, Cc, cin + h, h, nbytes=nbytes, tag=tag)
+
+    # ---- first-step forms: the cell's state is the zero initial state (no H, S.H, R planes; no dH, dS.H) ----
+    def cell_first_supported(self, Cc, h) -> bool:
+        return bool(self.lib.stc_cell_first_supported(Cc, h))
+
+    def _first_planes(self, what, X, SX, like):
+        """Input planes (R, C, cin), cin = h or 1..4, beside the (R, C, h) plane ``like``."""
+        R, Cc, h = like.shape
+        cin = X.shape[-1]
+        if not (cin == h or 1 <= cin <= 4):
+            raise StcError(f'{what}: input plane width {cin} must be {h} or 1..4')
+        for name, t in (('X', X), ('SX', SX)):
+            _tensor(f'{what}.{name}', t, (R, Cc, cin))
+        return R, Cc, h, cin
+
+    def cell_gates_fwd_first(self, X, SX, Tc, W, bias, U, post, act_amax=None):
+        """``cell_gates_fwd_planar`` with its fused candidate projection on the zero initial state (stc_cell_gates_fwd_first_f32): writes U and
+        ``post`` = (Wc, bc, A, Bm)'s pair A, Bm; the reset gate is not formed.  ``act_amax``: the same (4, 256) rows, of which the H rows stay zero."""
+        R, Cc, h, cin = self._first_planes('gates_first', X, SX, U)
+        Wc, bc, A, Bm = post
+        _tensor('gates_first.Tc', Tc, (2, Cc, Cc))
+        _tensor('gates_first.W', W, (4 * (cin + h), 2 * h))
+        _tensor('gates_first.Wc', Wc, (4 * (cin + h), h))
+        if bias is not None:
+            _tensor('gates_first.bias', bias, (2 * h,))
+        if bc is not None:
+            _tensor('gates_first.bc', bc, (h,))
+        for name, t in (('U', U), ('A', A), ('Bm', Bm)):
+            _tensor('gates_first.' + name, t, (R, Cc, h))
+        self._same_device(X, SX, Tc, W, bias, U, Wc, bc, A, Bm)
+        self._launch('stc_cell_gates_fwd_first_f32', U, _ptr(X), _ptr(SX), _ptr(Tc), _ptr(W), _ptr(bias), _ptr(U), _ptr(Wc), _ptr(bc), _ptr(A), _ptr(Bm),
+                     self.operand_format, self._act_amax('gates_first', act_amax, 4, U), R, Cc, cin + h, h,
+                     nbytes=4 * R * Cc * (2 * cin + 3 * h))             # X, SX in; U, A, Bm out
+
+    def cell_bwd_first(self, X, SX, Tc, Wg, Wc, U, Cand, dHnew, dBm, dXs, dWg, dbg, dWc, dbc, accumulate_x=False, act_amax=None):
+        """``cell_bwd_planar`` on the zero initial state (stc_cell_bwd_first_f32): ``dXs`` = [dX, dSX] (None, None for a narrow input plane); the
+        weight gradients come at full shape, their H rows and the reset gate's columns exact zeros."""
+        R, Cc, h, cin = self._first_planes('cell_bwd_first', X, SX, U)
+        _tensor('cell_bwd_first.Tc', Tc, (2, Cc, Cc))
+        _tensor('cell_bwd_first.Wg', Wg, (4 * (cin + h), 2 * h))
+        _tensor('cell_bwd_first.Wc', Wc, (4 * (cin + h), h))
+        for name, t in (('U', U), ('Cand', Cand), ('dHnew', dHnew), ('dBm', dBm)):
+            _tensor('cell_bwd_first.' + name, t, (R, Cc, h))
+        if len(dXs) != 2:
+            raise StcError('cell_bwd_first: two gradient planes (dX, dSX)')
+        wide = cin == h
+        if wide:
+            for i, z in enumerate(dXs):
+                _tensor(f'cell_bwd_first.dX[{i}]', z, (R, Cc, h))
+        elif accumulate_x:
+            raise StcError('cell backward: accumulate_x with a narrow input plane (it gets no gradient)')
+        _tensor('cell_bwd_first.dWg', dWg, (4 * (cin + h), 2 * h))
+        _tensor('cell_bwd_first.dWc', dWc, (4 * (cin + h), h))
+        if dbg is not None:
+            _tensor('cell_bwd_first.dbg', dbg, (2 * h,))
+        if dbc is not None:
+            _tensor('cell_bwd_first.dbc', dbc, (h,))
+        self._same_device(X, SX, Tc, Wg, Wc, U, Cand, dHnew, dBm, *dXs, dWg, dbg, dWc, dbc)
+        ws = self._get_workspace(U.device, self.lib.stc_cell_bwd_first_workspace_bytes(Cc, 2 * h, h))
+        self._launch('stc_cell_bwd_first_f32', U, _ptr(X), _ptr(SX), _ptr(Tc), _ptr(Wg), _ptr(Wc), _ptr(U), _ptr(Cand), _ptr(dHnew), _ptr(dBm),
+                     *[_ptr(z) if wide else None for z in dXs], _ptr(dWg), _ptr(dbg), _ptr(dWc), _ptr(dbc), int(bool(accumulate_x)),
+                     self.operand_format, self._act_amax('cell_bwd_first', act_amax, 4, U), _ptr(ws), ws.numel(), R, Cc, cin + h, h,
+                     nbytes=4 * R * Cc * (2 * cin + 4 * h + (2 * h * (1 + bool(accumulate_x)) if wide else 0)), tag='wide' if wide else 'layer0')
 
     # ---- small graphs: one STC_Cell step per launch --------------------------------------------------------
     SMALL_MAX_ROWS = 65535       # N*C rows per sample the kernels take at all (16-bit row arithmetic)

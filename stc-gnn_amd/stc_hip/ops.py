@@ -528,6 +528,37 @@ _POST_AGG = True         # candidate convolution as Y = A + S.Bm (narrow SpMM af
 _SMALL = True            # small graphs (N*C rows per sample fit the caches, C <= 16): one launch per cell step and direction
 _RING2 = True            # state gradient + transpose aggregation of dY in one launch where the graph has a two-ring plan (no dY plane)
 _RING2_FWD = True        # ... and the forward's blend + aggregation of the new state (stc_ring2_blend_f32)
+_FIRST_STEP = True       # cells on the zero initial state (a layer's first time step) in their first-step forms: no H, S.H, R planes, no dH, dS.H
+
+_ZEROS = {}              # (device, dtype) -> one zero, never written: what ``zero_state`` views
+
+
+def _first_step_kernels(k, dtype, C: int, h: int) -> bool:
+    """The ONE test of whether kernel set ``k`` runs first-step forms on planes of ``dtype``: the switch, fp32 planes, the capability and the
+    library's own shape predicate.  The model (``first_step_route``) and the executor (``_ForwardPass``) both ask here."""
+    return bool(_FIRST_STEP and dtype == torch.float32 and getattr(k, 'first_step_cells', False) and k.cell_first_supported(C, h))
+
+
+def first_step_route(op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widths, dtype=torch.float32) -> bool:
+    """Whether ``stc_cell_graph`` runs the PLANAR_ONE_BWD cells of this problem whose state is a zero initial state in their first-step forms
+    (fp32 planes, order 2, a kernel set with ``first_step_cells``, not the few-category executor): the caller then passes ``zero_state`` views
+    instead of planes of zeros."""
+    k = kernels()
+    return Ks == 2 and _first_step_kernels(k, dtype, C, h) and not (_SMALL and small_graph_supported(k, op, Tc, Ks, C, h, x_widths, dtype))
+
+
+def zero_state(ref: torch.Tensor, shape, dtype=None) -> torch.Tensor:
+    """A zero initial state as a SHAPE: a stride-0 view of one cached zero on ``ref``'s device -- no plane is allocated or filled.  The executor
+    recognises it (``_is_zero_state``), runs its consumers in their first-step forms and builds the plane only for a launch that reads one."""
+    key = (ref.device, dtype or ref.dtype)
+    if key not in _ZEROS:
+        _ZEROS[key] = torch.zeros((), device=key[0], dtype=key[1])
+    return _ZEROS[key].expand(*shape)
+
+
+def _is_zero_state(t: torch.Tensor) -> bool:
+    z = _ZEROS.get((t.device, t.dtype))
+    return z is not None and t.dim() == 4 and not any(t.stride()) and t.untyped_storage().data_ptr() == z.untyped_storage().data_ptr()
 
 
 def cell_graph_supported(op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widths, dtype=torch.float32) -> bool:
@@ -635,9 +666,21 @@ class _ForwardPass(_Pass):
         self.ring2 = _RING2_FWD and not bf16 and op.fwd_ring2 is not None and k.ring2_fits(self.B, self.N, self.C, self.h)
         # forward only, on a kernel set that takes None for them: the planes only a backward reads (R, Cand, R*H at order 2) are not stored
         self.lean = forward_only and bool(getattr(k, 'optional_gate_stores', False))
+        # cells whose state is a zero initial state (``zero_state``), in the first-step forms where the cell's form and the kernel set have them
+        zero = {('ext', i) for i, t in enumerate(ext) if _is_zero_state(t)}
+        can = _first_step_kernels(k, ext[0].dtype, self.C, self.h)
+        self.first = [can and hs in zero and f is _Form.PLANAR_ONE_BWD for (_, _, hs), f in zip(schedule, forms)]
 
     def source(self, src):
-        return self.ext[src[1]] if src[0] == 'ext' else self.state[src[1]]
+        if src[0] != 'ext':
+            return self.state[src[1]]
+        t = self.ext[src[1]]
+        if not t.is_contiguous() and _is_zero_state(t):             # a zero initial state that some launch reads after all: its plane, at first touch
+            t = self.ext[src[1]] = t.new_zeros(t.shape)
+        return t
+
+    def plane(self):                                                # an uninitialised state-sized plane
+        return self.ext[0].new_empty(self.B, self.N, self.C, self.h)
 
     def rows_of(self, j):                                           # input rows of an interleaved cell, allocated at first touch
         if j not in self.XH:
@@ -710,20 +753,27 @@ class _ForwardPass(_Pass):
     def planar(self, j, Wg, bg, Wc, bc, Hprev, U, Rg, Cand, Hnew, copies, side):
         """PLANAR_ONE_BWD and PLANAR: the candidate's projection rides in the gates launch; only PLANAR stores the R*H plane."""
         k, op, rows, (_, x, hs) = self.k, self.op, self.rows, self.schedule[j]
-        Xp, SXp, SHp = self.source(x), self.aggregated(x), self.aggregated(hs)
-        RH = None if (self.forms[j] is _Form.PLANAR_ONE_BWD or self.lean) else torch.empty_like(Hprev)
-        A, Bm = torch.empty_like(Hprev), torch.empty_like(Hprev)
-        k.cell_gates_fwd_planar(*rows((Xp, Hprev, SXp, SHp)), self.Tc, Wg, bg, *rows((U, Rg, RH)), post=(Wc, bc, *rows((A, Bm))), **self.act_slots(j))
+        first = Hprev is None                                       # the state is the zero initial state: the first-step forms (``cell``)
+        Xp, SXp, SHp = self.source(x), self.aggregated(x), None if first else self.aggregated(hs)
+        RH = None if (self.forms[j] is _Form.PLANAR_ONE_BWD or self.lean) else self.plane()
+        A, Bm = self.plane(), self.plane()
+        if first:                                                   # no H, S.H operands; the reset gate only ever multiplies H = 0
+            k.cell_gates_fwd_first(*rows((Xp, SXp)), self.Tc, Wg, bg, *rows((U,)), (Wc, bc, *rows((A, Bm))), **self.act_slots(j))
+        else:
+            k.cell_gates_fwd_planar(*rows((Xp, Hprev, SXp, SHp)), self.Tc, Wg, bg, *rows((U, Rg, RH)), post=(Wc, bc, *rows((A, Bm))), **self.act_slots(j))
         # the blend and the aggregation of the new state in one launch where the graph has a two-ring plan and some planar cell will
         # ask for S.Hnew (stc_ring2_blend_f32: the new state is summed out of LDS instead of being read back by a launch of its own; on ring-bounded
         # clusters it measured 792 us against 548 + 203 for the two launches: tiles only)
         if (self.ring2 and not op.ring2_clusters and not copies and side is None
                 and any(self.forms[d].planar for d, _ in self.consumers[j])):
-            SHn = torch.empty_like(Hprev)
-            k.ring2_blend(*self.graph[:3], op.fwd_ring2, Bm, A, U, Hprev, Cand, Hnew, SHn)
+            SHn = self.plane()
+            if first:
+                k.ring2_blend_first(*self.graph[:3], op.fwd_ring2, Bm, A, U, Cand, Hnew, SHn)
+            else:
+                k.ring2_blend(*self.graph[:3], op.fwd_ring2, Bm, A, U, Hprev, Cand, Hnew, SHn)
             self.agg[('cell', j)] = SHn
-        else:
-            k.spmm_blend_fwd(*self.graph, Bm, A, U, Hprev, Cand, Hnew, copies=copies, side=side)
+        else:                                                       # (the row-blocked blend reads a plane of zeros: built here only)
+            k.spmm_blend_fwd(*self.graph, Bm, A, U, self.source(hs) if first else Hprev, Cand, Hnew, copies=copies, side=side)
         return [Xp, SXp, SHp] + ([] if RH is None else [RH])
 
     def rows_cell(self, j, Wg, bg, Wc, bc, Hprev, U, Rg, Cand, Hnew, copies, side):
@@ -754,12 +804,13 @@ class _ForwardPass(_Pass):
     def cell(self, j, stack, out=None):
         """Every launch of cell j, in its form; the new state goes to ``out`` (a slot of the output stack) or to a tensor of its own.  Returns
         what the cell saves for backward: [H, U, R, Cand, *the form's planes]."""
-        Hprev = self.source(self.schedule[j][2])
+        first = self.first[j]                                       # first-step forms: H and R are saved as None -- the planes do not exist
+        Hprev = None if first else self.source(self.schedule[j][2])
         copies, side, late_copies, late_rows = self.copy_plan(j)
         form = self.forms[j]
-        U = torch.empty_like(Hprev)
-        Rg, Cand = (None, None) if (self.lean and form.planar) else (torch.empty_like(Hprev), torch.empty_like(Hprev))
-        Hnew = torch.empty_like(Hprev) if out is None else out
+        U = self.plane()
+        Rg, Cand = (None, None) if (self.lean and form.planar) else (None if first else self.plane(), self.plane())
+        Hnew = self.plane() if out is None else out
         run = self.planar3 if form is _Form.PLANAR3 else self.planar if form.planar else self.rows_cell
         more = run(j, *stack, Hprev, U, Rg, Cand, Hnew, copies, side)
         self.finish(j, Hnew, late_copies, late_rows)
@@ -925,7 +976,7 @@ class _BackwardPass(_Pass):
             dHnew, dY = self.owed(j, (U, Cand))
             dBm = self.spmm(dY)
             del dY                                                  # (the kernel re-forms dY from dHnew, U, Cand)
-        new = lambda: torch.empty_like(Hprev)
+        new = lambda: torch.empty_like(U)
         dWg, dbg, dWc, dbc = self.grads_for(s_id)
         # A state has two consumers (next step as H, next layer as X): the first one processed writes the state's direct and
         # aggregated gradient planes, the second ADDS into them (accumulate_x / accumulate_h), so the state-gradient SpMM gathers
@@ -947,6 +998,10 @@ class _BackwardPass(_Pass):
             return d, a_, False
 
         dXd, dSX, acc_x = planes_of_state(x) if self.cin[j] == self.h else (None, None, False)
+        if Hprev is None:                                           # the forward ran the first-step forms: no H, S.H, R; nobody is owed dH, dS.H
+            k.cell_bwd_first(*self.rows((Xp, SXp)), self.Tc, Wg, Wc, *self.rows((U, Cand, dHnew, dBm)), self.rows((dXd, dSX)), dWg, dbg, dWc, dbc,
+                             accumulate_x=acc_x, **self.act_slots(j))
+            return
         dHd, dSH, acc_h = planes_of_state(hs)
         k.cell_bwd_planar(*self.rows((Xp, Hprev, SXp, SHp)), self.Tc, Wg, Wc, *self.rows((U, Rg, Cand, dHnew, dBm)),
                           self.rows((dXd, dSX, dHd, dSH)), dWg, dbg, dWc, dbc,
@@ -1021,7 +1076,8 @@ def _begin_forward(op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, T
     """What both routes of ``stc_cell_graph`` do before the first launch: kernel set, contiguous operands, one form per cell, the output stack.
     Returns (pass, parameter sets, output stack, output cell -> slot)."""
     k = kernels().for_graph(_amplification(op, Ks))              # (a heavy graph: the 24-bit operand format, _lib.HEAVY_ROW_SUM)
-    ext, stacks, Tc, fwd_val = _unpack(n_ext, Tc, fwd_val, tensors)
+    _, stacks, Tc, fwd_val = _unpack(0, Tc, fwd_val, tensors[n_ext:])
+    ext = [t if _is_zero_state(t) else _c(t) for t in tensors[:n_ext]]      # (zero initial states as shapes, ``zero_state``: not made contiguous)
     bf16 = ext[0].dtype == torch.bfloat16                       # bf16 state planes: the all-planar bf16 kernel set
     if bf16:
         k = k.bf16
