@@ -66,6 +66,56 @@ const char* stc_last_error(void);
  * points read no environment variables; apart from this setting and the thread-local error text the library keeps no state. */
 int stc_set_dispatch_level(int32_t level);
 
+/* ---- Non-finite values ------------------------------------------------------------------------------------------------------
+ * A NaN or +-Inf in a float operand (features, states, gates, gradients, weights, biases, category tables, graph values; never an index,
+ * count or plan array) is handed on as the reference's torch operations hand it on: not masked, and not spread beyond what is stated here.
+ * Every sentence is pinned by tests/test_nonfinite.py (named in brackets), one poisoned element at a time.  `want` is the float64 run of the
+ * operation's restatement (oracle/kernel_emul.py) under the PATTERN semantics of the entry point: entries absent from a sparse pattern
+ * do not take part; a dense operand is dense arithmetic (0 * NaN = NaN); T_0 is the identity whatever Tc[0] holds (no kernel multiplies
+ * by it: an Inf reaches the other categories of its node through T_c, c >= 1, only).  This is the one place where the kernels differ from the
+ * reference's torch operations on purpose: torch multiplies by the dense identity, so there an Inf in a slab is NaN in every category of its
+ * node (eye * Inf), at Kc = 1 as well, where the kernels keep it in its category.
+ *   A  No masking.  Wherever want is non-finite the result is non-finite.  NaN and +-Inf are not told apart (reassociated sums and the
+ *      two-piece operand split turn Inf into NaN).  An Inf that the math itself turns finite stays finite and exact: sigmoid(+-Inf) = 1 / 0,
+ *      tanh(+-Inf) = +-1, NaN -> NaN [test_gate_functions_on_the_kernels].  stc_mgp_softmax_fwd/bwd_f32 take relu and max as torch does
+ *      (a NaN difference stays NaN and passes the backward mask) [test_mgp_softmax_hands_non_finite_values_on,
+ *      test_generator_kernels_hand_a_nan_weight_on].
+ *   B  Containment.  Results outside the poison's reach equal, BIT FOR BIT, what the same call gives on the clean operands.  The reach is
+ *      what want marks or changes, plus the entry point's spread unit [test_contract_on_the_kernels and the tests named below]:
+ *        stc_csr_spmm_f32 / _bf16, stc_csr_sddmm_f32, gate / blend / head / axpy / concat / split / Adam kernels, stc_mgp_uv_*:  none.
+ *        stc_bcsr_spmm_f32 / _bf16, and stc_spmm_sum_f32 / stc_spmm_blend_fwd_f32 on a row-block plan:  the STC_SPMM_BLOCK_ROWS rows of
+ *          the block, column by column (the explicit zero of a block-mate times the poisoned source row).
+ *        stc_patch_spmm_f32 / _bf16:  the rows of the plan's patch, column by column (zero-weight repeats).
+ *        stc_ring2_sum_f32, stc_ring2_blend_f32, stc_ring2_blend_first_f32, stc_ring2_chain_f32:  the plan's patch for the first aggregation; the second is formed from the first as the
+ *          launch holds it, so it reaches the rows with an entry in ANY row of that patch, and their patches.
+ *        stc_dense_agg_f32, stc_cheby_dense_fwd/bwd_f32, stc_mgp_softmax_*, stc_mixed_fusion_*:  dense arithmetic -- want itself marks
+ *          every row (of the sample) that the poisoned element's row or column enters; nothing beyond it.
+ *        node kernels (stc_bdg_node_*, stc_bdg_node_post_*), fused and planar cell kernels, all dispatch levels and both operand
+ *          formats:  the node.  In the backward the pad columns [Lw, L) of THAT node's slab gradients come out non-finite where the
+ *          math has zeros [test_contract_on_the_node_kernels, test_contract_on_the_fused_cell_kernels,
+ *          test_contract_on_the_planar_cell_kernels: planar gates forward / backward, the one-launch backward with its accumulate forms, the
+ *          two-launch C = 64 backward, the order-3 forms with accumulate_x; test_contract_on_the_kernels: the bf16 planar forms].
+ *          The fp16 x 2 backward kernels (one-launch, two-launch C = 64, order 3) keep this with several nodes per wave: a node
+ *          with a non-finite gradient maximum takes the smallest scale and does not move the wave's reference, so every other node's
+ *          planes are bit-identical and accumulated planes receive their addend once [test_runscale_stop_path].
+ *        stc_cell_small_fwd/bwd_f32 (CSR and dense graphs, split form, order 3):  the sample.  stc_graph_grad_f32 / stc_mix_grad_f32:  none
+ *          (the row of the product that the poisoned row enters; an unselected cell reaches nothing).
+ *      A poison in batch element b never changes batch element b' of a per-sample output [test_module_hands_a_nan_sample_on_like_the_twin].
+ *   C  The finite part is still right: the elements asserted under B meet the tolerance of the kernel's parity test against want.
+ *   D  One unit.  The parameter-gradient / reduction outputs of a launch (dW, db, dTc, dwb, the uv partial sums) are one unit: with a
+ *      non-finite element in any of them in want, they are held to A only (the node's fragments are at the smallest scale: what it adds to
+ *      the launch's other sums is flushed).  So is every output of a launch when an INF sits in a table that all rows read (a weight,
+ *      a bias, T_c): the split-operand kernels scale a table by its own maximum.  A NaN in such a table is dropped by that maximum and is
+ *      held to B and C like any other poison, on every dispatch level.  A trainer discards such a step.
+ *   Pad columns [Lw, L) of the slabs are read by the matrix-core paths and must hold FINITE values (the host writes zeros); a NaN there
+ *   stays in its node [test_nan_in_the_pad_columns_stays_in_its_node_f32 / _bf16].
+ *   First-step forms (stc_cell_gates_fwd_first_f32, stc_cell_bwd_first_f32): the general entry points on explicit planes of zeros are the
+ *   restatement, with ONE exception to A.  The shortcut x * 0 := 0 leaves at the CLEAN run's value, bit for bit, what the general kernels
+ *   turn into NaN * 0 = NaN: the H rows of both weight gradients and the reset-gate half of dWg / dbg (exact zeros) for any non-finite
+ *   gradient; A and Bm for a poison that arrives through the reset gate only (S.X -> R -> R * H); dSX for one that arrives through d(R * H)
+ *   only (dBm).  (Pinned for a NaN.  An Inf gives its node the smallest activation scale of the fp16 x 2 format: the node's exempt entries
+ *   are then finite without meaning, while its U and new state are non-finite.)  Everything else follows A to D with the node as the unit [test_contract_on_the_planar_cell_kernels, first_step cases]. */
+
 /* ---- spatial aggregation -------------------------------------------------
  * Y[b,i,:] = alpha * sum_{j in row i} val[j] * X[b, colidx[j], :] + beta * Y0[b,i,:]
  *
@@ -83,7 +133,7 @@ int stc_csr_spmm_f32(const int32_t* rowptr, const int32_t* colidx, const float* 
 /* Same product on the row-blocked form of a FIXED graph (BCSR, STC_SPMM_BLOCK_ROWS x 1 blocks): the host
  * groups the rows 4 at a time and lists, per block, the distinct columns its rows touch (blk_ptr
  * (n_blocks+1), blk_cols) with the 4 values of each column, one per row of the block, zero where a row has
- * no such entry (blk_vals, nnzb x 4).  One wave produces the 4 rows of a block together, so a neighbour
+ * no such entry (blk_vals, nnzb x 4; the zero is multiplied: a non-finite source row reaches all 4 rows, "Non-finite values" above).  One wave produces the 4 rows of a block together, so a neighbour
  * row shared by several of them is fetched once: the 8-neighbour grid needs 18 instead of 36 row fetches
  * per 4 output rows (the direct kernel is bound by exactly that L2 -> CU gather traffic).  A graph without
  * locality degenerates to the same number of fetches as CSR.  Y0 / alpha / beta as stc_csr_spmm_f32. */
@@ -109,7 +159,8 @@ int stc_bcsr_spmm_f32(const int32_t* blk_ptr, const int32_t* blk_cols, const flo
  *   patch_val  (n_patches, STC_PATCH_ROWS, width)     per entry: its value; entries in the row's CSR order, the tail of the row
  *                                                     filled with zero-weight repeats of its last entry
  * width: 4, 8, 12, 16, 24 or 32 (<= STC_PATCH_MAX_WIDTH).  F: a multiple of 256 (STC_EUNSUPPORTED otherwise: use the row-blocked form).
- * Each row's sum runs over its entries in CSR order, one fmaf each: results equal stc_csr_spmm_f32 / stc_bcsr_spmm_f32 bit for bit.
+ * Each row's sum runs over its entries in CSR order, one fmaf each: on finite operands results equal stc_csr_spmm_f32 / stc_bcsr_spmm_f32
+ * bit for bit; a non-finite source row also reaches its patch-mates through the zero-weight repeats ("Non-finite values" above).
  * Y0 / alpha / beta as stc_csr_spmm_f32 (Y0 may alias Y). */
 #define STC_PATCH_ROWS 32
 #define STC_PATCH_MAX_SRC 64
@@ -134,7 +185,7 @@ int stc_bcsr_spmm_bf16(const int32_t* blk_ptr, const int32_t* blk_cols, const fl
                        const void* X, const void* Y0, void* Y,
                        int32_t batch, int32_t F, float alpha, float beta, void* stream);
 
-/* stc_patch_spmm_f32 on bf16 rows (X, Y0, Y bf16, F a multiple of 512; values and sums fp32, one rounding at the store: equal to
+/* stc_patch_spmm_f32 on bf16 rows (X, Y0, Y bf16, F a multiple of 512; values and sums fp32, one rounding at the store: on finite operands equal to
  * stc_bcsr_spmm_bf16 bit for bit).  The same plan arrays. */
 int stc_patch_spmm_bf16(const int32_t* patch_src, const int32_t* patch_rows, const int32_t* patch_cnt,
                         const uint8_t* patch_idx, const float* patch_val, int32_t n_patches, int32_t width,
@@ -300,7 +351,8 @@ int stc_cheby_dense_bwd_f32(const float* G, const float* T, float* dT, int32_t n
  * Z is a HOST array of Ks device pointers.
  * Lw <= L: the slabs may carry L - Lw trailing pad columns per row (the host pads L = in + hidden
  * up to a multiple of 4 so that every row is 16-byte aligned: 17 -> 20); W has Lw rows per block,
- * pad columns are ignored in the forward and receive zero gradient. */
+ * pad columns must hold finite values (the host writes zeros; the matrix-core paths multiply them by zero weight rows) and receive
+ * zero gradient. */
 int stc_bdg_node_fwd_f32(const float* const* Z, int32_t Ks, const float* Tc, int32_t Kc,
                          const float* W, const float* bias, float* Y,
                          int64_t nodes, int32_t C, int32_t L, int32_t Lw, int32_t Ho, void* stream);
@@ -490,11 +542,12 @@ int stc_cell_bwd_planar_f32(const float* X, const float* H, const float* SX, con
 /* ---- first-step forms of the planar cell launches (ABI v37; C = 32, h = 16: stc_cell_first_supported) --------------------
  * The first time step of every layer runs on the zero initial state (reference STC_GNN.py: init_hidden).  These forms take no H, S.H or Rg
  * plane and produce no Rg, R*H, dH or dS.H: R only ever multiplies H = 0 and dR carries the factor H.  What they do produce is what the
- * general entry points produce for explicit planes of zeros, from the same products in the same order.
+ * general entry points produce for explicit planes of zeros, from the same products in the same order -- for finite operands: the
+ * shortcut x * 0 := 0 writes 0 where the general kernels on zero planes form NaN * 0 = NaN ("Non-finite values" above).
  *   stc_cell_gates_fwd_first_f32: U, A, Bm of stc_cell_gates_fwd_planar_f32 (the candidate's input is [X | 0]); act_amax receives the maxima
  *     of |X|, |SX| in the rows that entry point uses, the H rows stay at the buffer's zero.
  *   stc_cell_bwd_first_f32: dX, dSX (wide input only; accumulate_x as above) and dWg, dbg, dWc, dbc of stc_cell_bwd_planar_f32 at full
- *     shape -- the H rows of both weight gradients and the reset-gate half of dWg / dbg are exact zeros.
+ *     shape -- the H rows of both weight gradients and the reset-gate half of dWg / dbg are exact zeros (also for non-finite inputs: the exception stated under "Non-finite values").
  *     workspace >= stc_cell_bwd_first_workspace_bytes(C, Lw, h) bytes, 16-byte aligned. */
 int stc_cell_first_supported(int32_t C, int32_t h);
 int stc_cell_gates_fwd_first_f32(const float* X, const float* SX, const float* Tc, const float* W, const float* bias, float* U,

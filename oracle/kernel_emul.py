@@ -174,11 +174,11 @@ class EmulatedKernels:
         for t in range(0, R, nw):
             idx = torch.arange(t, min(t + nw, R))
             w = idx - t
-            knt, zero = kn[idx], m[idx] == 0
+            knt, zero, wild = kn[idx], m[idx] == 0, ~torch.isfinite(m[idx])
             j = k[w] - knt
-            fresh = (j > 12) & ~zero                                   # first gradient of the wave, or a node that ends its pass: the new reference
+            fresh = (j > 12) & ~zero & ~wild                           # first gradient of the wave, or a node that ends its pass: the new reference
             k[w] = torch.where(fresh, knt, k[w])
-            j = torch.where(fresh | zero, torch.zeros_like(j), j)
+            j = torch.where(fresh | zero | wild, torch.zeros_like(j), j)      # (a non-finite maximum: smallest scale for the node, no new reference)
             up = (j - 8).clamp(min=0)
             a_exp[idx] = torch.where(zero, torch.zeros_like(j), knt + up).double()
             shift_exp[idx] = (j - up).clamp(min=-100).double()
@@ -314,7 +314,7 @@ class EmulatedKernels:
             U = torch.zeros(R, C, Ho, dtype=W.dtype)
             for n in range(Ks):
                 U += Zs[n][..., :Lw] @ Wv[n, c]
-            out += torch.einsum('pd,rpo->rdo', Tc[c], U)
+            out += U if c == 0 else torch.einsum('pd,rpo->rdo', Tc[c], U)      # T_0 is the identity whatever Tc[0] holds, as in the kernels
         if bias is not None:
             out += bias
         Y.copy_(out)
@@ -370,7 +370,7 @@ class EmulatedKernels:
         Wv = W.view(Ks, Kc, Lw, Ho)
         dWv = torch.zeros_like(Wv)
         # Q_c[r,c',:] = sum_d Tc[c][c',d] dY[r,d,:]
-        Q = [torch.einsum('pd,rdo->rpo', Tc[c], dY) for c in range(Kc)]
+        Q = [dY if c == 0 else torch.einsum('pd,rdo->rpo', Tc[c], dY) for c in range(Kc)]
         for n in range(Ks):
             acc = torch.zeros(R, C, L, dtype=W.dtype)            # pad columns get zero gradient
             for c in range(Kc):

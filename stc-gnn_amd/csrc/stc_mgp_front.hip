@@ -66,18 +66,22 @@ __global__ __launch_bounds__(MG_THREADS) void mgp_uv_bwd_kernel(const float* __r
     }
 }
 
+// relu and max as torch has them: a NaN operand comes out as NaN (fmaxf returns the other operand and would hand a diverged P on as a finite graph)
+__device__ __forceinline__ float relu_nan(float d) { return d <= 0.f ? 0.f : d; }
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || a > b) ? a : b; }
+
 // Ps[n][:] = softmax(relu(P[n][:] - P[:][n])): one wave per row n
 __global__ __launch_bounds__(64) void mgp_softmax_fwd_kernel(const float* __restrict__ P, float* __restrict__ Ps, int R) {
     const int n = blockIdx.x, lane = threadIdx.x;
     float mx = 0.f;                                                    // relu: every entry >= 0
-    for (int m = lane; m < R; m += 64) mx = fmaxf(mx, P[(long long)n * R + m] - P[(long long)m * R + n]);
+    for (int m = lane; m < R; m += 64) mx = max_nan(mx, P[(long long)n * R + m] - P[(long long)m * R + n]);
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    for (int off = 32; off > 0; off >>= 1) mx = max_nan(mx, __shfl_xor(mx, off, 64));
     float sum = 0.f;
-    for (int m = lane; m < R; m += 64) sum += expf(fmaxf(P[(long long)n * R + m] - P[(long long)m * R + n], 0.f) - mx);
+    for (int m = lane; m < R; m += 64) sum += expf(relu_nan(P[(long long)n * R + m] - P[(long long)m * R + n]) - mx);
     sum = stc_wave_sum(sum);
     const float inv = 1.f / sum;
-    for (int m = lane; m < R; m += 64) Ps[(long long)n * R + m] = expf(fmaxf(P[(long long)n * R + m] - P[(long long)m * R + n], 0.f) - mx) * inv;
+    for (int m = lane; m < R; m += 64) Ps[(long long)n * R + m] = expf(relu_nan(P[(long long)n * R + m] - P[(long long)m * R + n]) - mx) * inv;
 }
 
 // rowdot[n] = sum_m dPs[n][m] Ps[n][m]
@@ -89,7 +93,7 @@ __global__ __launch_bounds__(64) void mgp_softmax_dot_kernel(const float* __rest
     if (lane == 0) rowdot[n] = s;
 }
 
-// dD[n][m] = Ps[n][m] (dPs[n][m] - rowdot[n]) where P[n][m] - P[m][n] > 0, else 0;   dP[n][m] = dD[n][m] - dD[m][n]
+// dD[n][m] = Ps[n][m] (dPs[n][m] - rowdot[n]) unless P[n][m] - P[m][n] <= 0 (a NaN difference passes, as through torch's relu);   dP[n][m] = dD[n][m] - dD[m][n]
 __global__ __launch_bounds__(MG_THREADS) void mgp_softmax_bwd_kernel(const float* __restrict__ P, const float* __restrict__ Ps, const float* __restrict__ dPs,
                                                                      const float* __restrict__ rowdot, float* __restrict__ dP, int R) {
     const long long total = (long long)R * R;
@@ -97,8 +101,8 @@ __global__ __launch_bounds__(MG_THREADS) void mgp_softmax_bwd_kernel(const float
         const int m = (int)(o % R), n = (int)(o / R);
         const long long t = (long long)m * R + n;
         const float d = P[o] - P[t];
-        const float a = d > 0.f ? Ps[o] * (dPs[o] - rowdot[n]) : 0.f;
-        const float b = -d > 0.f ? Ps[t] * (dPs[t] - rowdot[m]) : 0.f;
+        const float a = !(d <= 0.f) ? Ps[o] * (dPs[o] - rowdot[n]) : 0.f;
+        const float b = !(-d <= 0.f) ? Ps[t] * (dPs[t] - rowdot[m]) : 0.f;
         dP[o] = a - b;
     }
 }

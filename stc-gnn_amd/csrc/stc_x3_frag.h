@@ -323,7 +323,8 @@ __device__ __forceinline__ void leave_max(float* __restrict__ row, int slot, flo
 //                     towards larger gradients, by at least 2^13 per pass: at most ~16 passes whatever the data.  Jumps of that size between the
 //                     nodes of one wave occur where gates saturate (factors e^-x: then by tens of binades).
 // A node whose gradients are all zero joins at any scale and leaves the reference alone.  The wave's final 1 / a goes into the combine.  All
-// bookkeeping is integer arithmetic on exponents (scalar unit); a non-finite maximum gives the smallest scale (the NaN goes where it has to).
+// bookkeeping is integer arithmetic on exponents (scalar unit); a non-finite maximum gives the node the smallest scale and leaves the reference
+// alone (the NaN goes where it has to: into this node's planes and into the sums, and nowhere else).
 __device__ __forceinline__ float exp2i(int k) { return __uint_as_float((unsigned)(k + 127) << 23); }
 struct RunScale {
     static constexpr int ROOM_ACT = 8, ROOM_GRAD = 4, EMPTY = 120;
@@ -341,6 +342,10 @@ struct RunScale {
         shift = 1.f;
         stop = false;
         if ((mbits & 0x7FFFFFFF) == 0) return 1.f;                        // no gradient at this node: zeros at any scale
+        // a non-finite maximum (exponent 255): the node's own fragments at the smallest scale -- an Inf stays one, and turns the sums it joins
+        // non-finite, which is all they have to be from here on -- and NO new reference: the wave's later nodes keep the scales they would
+        // have had without this node, so their gradient planes come out as if it were not there
+        if (((mbits >> 23) & 255) == 255) return exp2i(kn);
         int j = k - kn;
         if (j > ROOM_ACT + ROOM_GRAD) {
             if (k != EMPTY) { stop = true; shift = mute(); return exp2i(kn); }
