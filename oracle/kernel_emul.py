@@ -60,7 +60,11 @@ class _Bf16Emulated:
         def call(*args, **kw):
             out = fn(*[widen(a) for a in args], **{k: widen(v) for k, v in kw.items()})
             for orig, w in pairs:
-                orig.copy_(w)
+                # only what the launch wrote: a const operand is not touched (a copy of its own bits would still count as an in-place
+                # edit in autograd's books, and a second backward over tensors saved for it would be refused)
+                back = w.to(torch.bfloat16)
+                if not torch.equal(back.contiguous().view(torch.int16), orig.contiguous().view(torch.int16)):
+                    orig.copy_(back)
             pairs.clear()
             return out
         return call

@@ -32,7 +32,8 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .graph import SpatialOperand
-from .small import _alias, _check_guard, _guard, _out_slots, _stacks, _unpack, last_uses, small_graph_supported, stc_small_graph, wavefront
+from .small import (_alias, _check_guard, _guard, _out_slots, _refuse_differentiable, _stacks, _unpack, last_uses, small_graph_supported,
+                    stc_small_graph, wavefront)
 
 _kernels = None
 
@@ -48,6 +49,10 @@ def kernels():
 
 def _c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _cn(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if t is None else _c(t)                          # (an optional bias)
 
 
 # ----------------------------------------------------------------------------- Chebyshev set of Gc
@@ -257,7 +262,7 @@ def _bdg_backward(dY, Zs, W, Tc, op: SpatialOperand, Ks: int, has_bias: bool, ne
 class _BdgDif(Function):
     @staticmethod
     def forward(ctx, X, W, b, Tc, fwd_val, op: SpatialOperand, Ks: int):
-        X, W, Tc, fwd_val = _c(X), _c(W), _c(Tc), _c(fwd_val)
+        X, W, b, Tc, fwd_val = _c(X), _c(W), _cn(b), _c(Tc), _c(fwd_val)
         Y, Zs = _bdg_forward(X, W, b, Tc, fwd_val, op, Ks)
         ctx.save_for_backward(W, Tc, *Zs)
         ctx.op = op
@@ -295,7 +300,8 @@ def bdg_dif(X: torch.Tensor, op: SpatialOperand, Tc: torch.Tensor, W: torch.Tens
     if X.dtype == torch.bfloat16:
         # bf16 feature rows (BASELINE configuration 5): fixed graphs only, shapes of the bf16 matrix-core kernels, no fallback
         if Tc.requires_grad or op.fwd_val.requires_grad:
-            raise ValueError('BDG_Dif on bfloat16 features needs fixed graphs (no gradient for Gs / Gc)')
+            which = ' and '.join(n for n, t in (('Tc', Tc), ('op.fwd_val', op.fwd_val)) if t.requires_grad)
+            raise ValueError(f'BDG_Dif on bfloat16 features needs fixed graphs (no gradient for Gs / Gc): {which} requires grad')
         if not kernels().node_bf16_supported(Ks, Kc, C, L, W.shape[1]):
             raise ValueError(f'BDG_Dif on bfloat16 features: Ks=Kc<=3, C in (32, 64), L in (16, 32), Ho in (16, 32); got Ks={Ks} Kc={Kc} C={C} L={L} Ho={W.shape[1]}')
     return _BdgDif.apply(X, W, b, Tc, op.fwd_val, op, Ks)
@@ -425,6 +431,7 @@ class _StcCell(Function):
     def forward(ctx, Xt, H, Wg, bg, Wc, bc, Tc, fwd_val, op: SpatialOperand, Ks: int):
         k = kernels()
         Xt, H, Wg, Wc, Tc, fwd_val = _c(Xt), _c(H), _c(Wg), _c(Wc), _c(Tc), _c(fwd_val)
+        bg, bc = _cn(bg), _cn(bc)
         cin, h = Xt.shape[-1], H.shape[-1]
         pad = -(cin + h) % 4                      # rows padded to 16 bytes (17 -> 20); W keeps its reference shape
         lead = H.shape[:-1]
@@ -1179,11 +1186,25 @@ class _StcCellGraph(Function):
 def stc_cell_graph(op: SpatialOperand, Tc, Ks: int, schedule, outputs, ext, stacks):
     """Run a schedule of STC_Cells (see ``_StcCellGraph``).  ``ext``: external (B,N,C,*) tensors (inputs, initial states;
     they get no gradient); ``stacks``: [(Wg, bg, Wc, bc)] parameter sets; returns the new states of the ``outputs`` cells
-    stacked along a new leading axis, (len(outputs), B, N, C, h) -- written in place by the kernels, no stack pass."""
+    stacked along a new leading axis, (len(outputs), B, N, C, h) -- written in place by the kernels, no stack pass.
+
+    Only the parameter sets are differentiable on every route; the few-category executor (``small.stc_small_graph``) also differentiates
+    the graphs.  In grad mode an external tensor that requires grad -- and, outside the few-category executor, ``Tc`` or ``op.fwd_val``
+    that does -- raises ``ValueError`` naming the argument, before any launch: no gradient is ever dropped silently
+    (``cell_graph_supported`` tells beforehand for the graphs; ``stc_cell`` differentiates every input).
+
+    Which executor runs is decided per call, also by what requires grad: at Chebyshev order 3 a DENSE ``Gs`` takes the few-category executor
+    only while it requires grad, or with grad mode off (``small.small_graph_supported``).  In grad mode with that graph frozen the call
+    goes to the general executor, which has cell kernels for C in {16, 32, 64} only: on few categories it then fails in its first launch's
+    host check (``StcError``: shape not on the fused path) -- loud, but without naming the graph.  Ask ``cell_graph_supported`` first, as
+    the module does (it then runs one node per cell)."""
+    ext = list(ext)
+    _refuse_differentiable(ext=ext)
     k = kernels()
     if _SMALL and small_graph_supported(k, op, Tc, Ks, ext[0].shape[2], 16, {ext[x[1]].shape[-1] if x[0] == 'ext' else 16 for _, x, _ in schedule},
                                         ext[0].dtype):
         return stc_small_graph(k, op, Tc, Ks, schedule, outputs, ext, stacks)
+    _refuse_differentiable(Tc=Tc, fwd_val=op.fwd_val)
     flat = [p for st in stacks for p in st]
     if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (Tc, op.fwd_val, *ext, *flat)):
         with torch.no_grad():                                        # no backward will follow: nothing saved, nothing stored for one (``_forward_only``)
@@ -1206,6 +1227,7 @@ class _MixedFusion(torch.autograd.Function):
         return G
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dG):
         A, P, WA, WP, gate = ctx.saved_tensors
         want_dA = ctx.needs_input_grad[0]
@@ -1273,7 +1295,10 @@ def mgp_front_supported(X: torch.Tensor, Wu: torch.Tensor, Wv: torch.Tensor) -> 
 
 def mgp_front(X, Wu, Wv, rows_axis: int, alpha: float, reduce=None):
     """The learned graph of one branch of ``MGP_Gen.forward``: softmax(relu(P - P^T)) with P = sum over (sample, time) of U V^T.  ``reduce``: applied
-    to P before the softmax (the batch-sum all-reduce of a sharded batch)."""
+    to P before the softmax (the batch-sum all-reduce of a sharded batch).  The data window ``X`` gets no gradient: in grad mode an ``X`` that
+    requires grad raises ``ValueError`` (``mgp_front_supported`` tells beforehand)."""
+    if torch.is_grad_enabled() and X.requires_grad:
+        raise ValueError('mgp_front: X requires grad, and this operator returns no gradient for X (detach the data window, or use torch ops)')
     U, V = _MgpUV.apply(X, Wu, Wv, rows_axis, alpha)
     P = U.flatten(1) @ V.flatten(1).t()                                # one plain GEMM over the (slice, hidden) axis; its autograd is two more
     if reduce is not None:

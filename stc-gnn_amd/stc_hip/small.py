@@ -96,6 +96,20 @@ def _check_guard(ctx):
                            'backward share its storage (treat the stack as read-only, or clone it before editing)')
 
 
+def _refuse_differentiable(**named):
+    """Both cell-graph executors return no gradient for some of their arguments (the external tensors; on the general executor the graphs
+    too): in grad mode one of them that requires grad is refused here, before any launch, by name -- its gradient would otherwise be
+    dropped without a word while the output still requires grad.  ``named``: argument name -> tensor or sequence of tensors."""
+    if not torch.is_grad_enabled():
+        return
+    for name, value in named.items():
+        for i, t in enumerate(value if isinstance(value, (list, tuple)) else [value]):
+            if t is not None and t.requires_grad:
+                which = f'{name}[{i}]' if isinstance(value, (list, tuple)) else name
+                raise ValueError(f'stc_cell_graph: {which} requires grad, and this operator returns no gradient for {name} '
+                                 '(detach it, or run the cells one by one through stc_cell, which differentiates every input)')
+
+
 def wavefront(schedule):
     """The cells by level (longest path from the external tensors), schedule order inside a level: a topological order of the same graph in
     which a state's consumers follow it closely -- the encoder's schedule is layer-major, so in ITS order every state of a layer lives until
@@ -437,7 +451,9 @@ def _forward_only(k, op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int,
 
 def stc_small_graph(k, op: SpatialOperand, Tc, Ks: int, schedule, outputs, ext, stacks):
     """The schedule on the few-category cell kernels: the autograd node, or -- grad mode off, or nothing that requires grad (the predicate of
-    ``ops.stc_cell_graph``) -- the forward-only route."""
+    ``ops.stc_cell_graph``) -- the forward-only route.  The graphs (``Tc``, ``op.fwd_val``) and the parameter sets are differentiable; the
+    external tensors are not: in grad mode one that requires grad raises ``ValueError`` before any launch."""
+    _refuse_differentiable(ext=list(ext))
     flat = [p for st in stacks for p in st]
     dense3 = Ks == 3 and op.nnz == op.n * op.n and op.source is None
     if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (Tc, op.fwd_val, *ext, *flat)):

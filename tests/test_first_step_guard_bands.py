@@ -3,9 +3,9 @@ into a larger allocation, NaN / bit-pattern margins, the workspace at exactly th
 equal the launch on plain tensors bit for bit and lie within the family's bound of the float64 twin.
 
 The cases are run here, and importing this file also appends them to ``tests.test_guard_bands.CASES``: that file's coverage walk
-(``test_every_entry_point_has_a_banded_case``) goes over the whole ctypes table and wants every entry point named by a case of ITS table.  So
-that test passes when the suite is collected as a whole and FAILS when tests/test_guard_bands.py is run alone -- until its own table names the
-three entry points.  The follow-up is to move these cases into tests/test_guard_bands.py and delete this file."""
+(``test_every_entry_point_has_a_banded_case``) goes over the whole ctypes table and wants every entry point named by a case of ITS table; it
+imports this file itself, so it also passes when tests/test_guard_bands.py is run alone.  The follow-up is to move these cases into
+tests/test_guard_bands.py and delete this file."""
 import pytest
 import torch
 

@@ -22,7 +22,8 @@ NOT banded, on purpose: the integer index arrays (rowptr, colidx, the row-block 
 read from a margin would turn into a wild address, and this file must never be able to cause a fault.  The float tables that travel with a
 host-built plan (blk_vals, patch_val, t1 / t2 value bits) stay plain with their plan.
 
-Per case: every margin (operands and scratch) keeps its bits; every result the header says is written is finite; the results equal, bit
+Per case: every margin (operands and scratch) keeps its bits; the interior of every 'in' operand -- ``const`` in the header -- keeps its
+bits too (the one operand the header declares consumed, dT of stc_cheby_dense_bwd_f32, is 'io'); every result the header says is written is finite; the results equal, bit
 for bit, the same launch on plain tensors (no kernel may choose its path by alignment above 16 bytes; the dW / db / dTc sums are
 fixed-order); the results are within the family's existing tolerance of the CPU twin run in float64 (``TOL`` / ``BTOL`` / ``BOUND`` of the
 family's own test file -- no new numbers).
@@ -221,6 +222,7 @@ def run_case(case, k, device, monkeypatch, twin=None):
             monkeypatch.setattr(k, '_get_workspace', scratch, raising=False)
             monkeypatch.setattr(_lib, 'torch', _BandingTorch(bands))
         bands.snapshot()
+        const = [(name, x, _bits(x).clone()) for name, role, x in _flat(spec, banded, None) if role == 'in']    # const operands: their bits before the launch
         try:
             banded_ret = case.call(k, banded)
             if on_gpu:
@@ -233,6 +235,7 @@ def run_case(case, k, device, monkeypatch, twin=None):
         if on_gpu:
             k.set_dispatch_level(0)
     findings += [f'margin of {name} changed' for name in bands.violations()]
+    findings += [f'input {name} was modified by the launch' for name, x, before in const if not torch.equal(_bits(x), before)]
     got, ref = _flat(spec, banded, banded_ret), _flat(spec, plain, plain_ret)
     assert [g[0] for g in got] == [r[0] for r in ref]
     want = None
@@ -1352,12 +1355,28 @@ def test_negative_control_read_past_an_input_with_zero_weight(monkeypatch):
     assert run_case(c, _Overrunning(), 'cpu', monkeypatch) == ['Y: non-finite result on banded operands']
 
 
+class _Clobbering(EmulatedKernels):
+    """Negative control: a twin whose csr_spmm uses its const operand X as scratch (scales it in place and back: the result is right, one
+    element of X ends one ulp off)."""
+
+    def csr_spmm(self, rowptr, colidx, val, n_rows, n_cols, X, Y0, Y, alpha, beta, plan=None):
+        super().csr_spmm(rowptr, colidx, val, n_rows, n_cols, X, Y0, Y, alpha, beta, plan=plan)
+        first = X.view(-1)[:1]
+        first.copy_(torch.nextafter(first, torch.full_like(first, float('inf'))))
+
+
+def test_negative_control_a_const_operand_is_written(monkeypatch):
+    c = next(c for c in CASES if c.id.startswith('csr_spmm_f32') and c.cpu)
+    assert run_case(c, _Clobbering(), 'cpu', monkeypatch) == ['input X was modified by the launch']
+
+
 def _takes_device_buffers(argtypes):
     """More pointer arguments than the trailing stream."""
     return sum(a in (_lib._p, _lib._pp, _lib._pi, _lib._pf) for a in argtypes) >= 2
 
 
 def test_every_entry_point_has_a_banded_case():
+    from tests import test_first_step_guard_bands  # noqa: F401  (appends the first-step cases to CASES: also when this file is run alone)
     named = set().union(*[c.entries for c in CASES])
     assert named <= set(_lib._ABI), named - set(_lib._ABI)
     assert not named & set(NO_BANDED_CASE)

@@ -348,7 +348,8 @@ def test_learned_graph_gradients_when_a_sets_cells_are_unevenly_spaced(monkeypat
 
     def run(small):
         monkeypatch.setattr(ops, '_SMALL', small)
-        t = {k: _leaf(v) for k, v in base.items()}
+        # (the external tensors and the weights of the loss are data: the executor refuses an external tensor that requires grad)
+        t = {k: (v.clone().to(DEV) if k in ('X', 'H', 'R') else _leaf(v)) for k, v in base.items()}
         op, Tc = dense_operand(t['Gs']), ops.cheby_dense(t['Gc'], 2)
         stacks = [(t[f'Wg{s}'], t[f'bg{s}'], t[f'Wc{s}'], t[f'bc{s}']) for s in (0, 1)]
         if small:
@@ -746,6 +747,19 @@ def test_small_graph_general_schedules_match_autograd(dev, monkeypatch):
     assert taken
 
 
+# The schedule of ``_general_schedule`` (tests/autograd_contract.py runs it too): parameter set 0 = the wide cell (16 + 16 columns), 1 = the narrow
+# one (1 + 16); external tensors 0 = narrow input, 1 = wide input, 2 = initial state
+#                   stack, Xt source,   H source
+GENERAL_SCHEDULE = [(1, ('ext', 0), ('ext', 2)),      # 0: narrow cell on external input and state
+                    (0, ('ext', 1), ('cell', 0)),     # 1: wide, state from 0
+                    (0, ('cell', 0), ('cell', 0)),    # 2: wide, both sides from 0
+                    (0, ('cell', 0), ('cell', 1)),    # 3: wide, input from 0 (its third consumer), state from 1
+                    (1, ('ext', 0), ('cell', 0)),     # 4: narrow, state from 0 (fourth consumer)
+                    (0, ('cell', 2), ('cell', 3)),    # 5
+                    (0, ('cell', 4), ('cell', 5))]    # 6
+GENERAL_OUTPUTS = [6, 3]
+
+
 def _general_schedule(C, K, tol=3e-6):
     Hh, Ww, h, B = 4, 5, 16, 2
     N = Hh * Ww
@@ -757,15 +771,7 @@ def _general_schedule(C, K, tol=3e-6):
     x0 = torch.rand(B, N, C, 1).to(DEV)
     xw = torch.rand(B, N, C, h).to(DEV)
     h0 = torch.rand(B, N, C, h).to(DEV)
-    #        stack, Xt source,   H source
-    schedule = [(1, ('ext', 0), ('ext', 2)),      # 0: narrow cell on external input and state
-                (0, ('ext', 1), ('cell', 0)),     # 1: wide, state from 0
-                (0, ('cell', 0), ('cell', 0)),    # 2: wide, both sides from 0
-                (0, ('cell', 0), ('cell', 1)),    # 3: wide, input from 0 (its third consumer), state from 1
-                (1, ('ext', 0), ('cell', 0)),     # 4: narrow, state from 0 (fourth consumer)
-                (0, ('cell', 2), ('cell', 3)),    # 5
-                (0, ('cell', 4), ('cell', 5))]    # 6
-    outputs = [6, 3]
+    schedule, outputs = GENERAL_SCHEDULE, GENERAL_OUTPUTS
     cells = (wide, narrow)
     stacks = [(c.gates.W, c.gates.b, c.candi.W, c.candi.b) for c in cells]
     Rw = torch.randn(len(outputs), B, N, C, h).to(DEV)
