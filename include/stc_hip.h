@@ -359,6 +359,11 @@ int stc_bdg_node_fwd_f32(const float* const* Z, int32_t Ks, const float* Tc, int
 
 /* Backward of the node kernel.  dZ: HOST array of Ks device pointers (nodes,C,L),
  * overwritten.  dW (Ks*Kc*Lw, Ho), db (Ho) or NULL, dTc (Kc,C,C) or NULL: overwritten.
+ * dTc != NULL: the launch runs on the generic kernel at every dispatch level (the matrix-core kernels form no dT_c), whose
+ * LDS need grows with C^2 * Kc and Ks*L * Kc*Ho: beyond 160 KiB the call returns STC_ELIMIT and writes nothing -- of the
+ * matrix-core shapes that is C = 64 with Ho = 32 at Ks = Kc = 3.  The same gradients then come from calls that fit: this one
+ * with dTc = NULL, and per c >= 1 one with Kc = 2 on Tc = [I, T_c] and W's row blocks (n, 0), (n, c), whose dTc[1] is dT_c
+ * (stc_hip/_lib.py: HipKernels._node_bwd_dT_by_block does so).
  * workspace: >= stc_bdg_node_bwd_workspace_bytes(...) bytes, 16-byte aligned. */
 size_t stc_bdg_node_bwd_workspace_bytes(int32_t Ks, int32_t Kc, int32_t C, int32_t L, int32_t Ho,
                                         int32_t want_dTc);

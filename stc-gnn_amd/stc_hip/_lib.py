@@ -25,13 +25,15 @@ LIB_PATH = os.path.join(_PKG_ROOT, 'libstc_hip.so')
 ABI_VERSION = 37
 FMT_BF16X3, FMT_F16X2 = 0, 1          # operand formats of the split-operand matrix-core kernels
 MAX_K = 4
+STC_ELIMIT = -3            # include/stc_hip.h: a size beyond a kernel limit
 SPMM_SUM_MAX_ADD, SPMM_SUM_BF16_MAX_ADD, RING2_MAX_ADD = 8, 5, 5      # addends of stc_spmm_sum_f32 / _bf16 and of the two-ring launches
 PATCH_ROWS, PATCH_MAX_SRC = 32, 64
 RING2_INTERIOR, RING2_FIRST, RING2_SECOND, RING2_WIDTH = 32, 64, 96, 8     # rows of a two-ring patch and of its rings, entries per row
 
 
 class StcError(RuntimeError):
-    """A C-ABI call returned non-zero, or the HIP extension cannot be used."""
+    """A C-ABI call returned non-zero (``code``: its status), or the HIP extension cannot be used."""
+    code = None
 
 
 _p = C.c_void_p
@@ -295,7 +297,9 @@ class HipKernels:
 
     def _failed(self, what, rc):
         msg = self.lib.stc_last_error()
-        raise StcError(f'{what} failed with code {rc}: {msg.decode() if msg else "?"}')
+        err = StcError(f'{what} failed with code {rc}: {msg.decode() if msg else "?"}')
+        err.code = rc
+        raise err
 
     def _launch(self, name, on, *args, nbytes=0, tag=None):
         """Call C entry point ``name`` with ``args`` + the current stream of ``on``'s device.
@@ -646,7 +650,32 @@ class HipKernels:
         if bf16:                                                # (no dTc argument)
             self._launch('stc_bdg_node_bwd_bf16', dY, *grads, _ptr(ws), ws.numel(), R, Cc, L, Lw, Ho, nbytes=nbytes)
         else:
-            self._launch('stc_bdg_node_bwd_f32', dY, *grads, _ptr(dTc), _ptr(ws), ws.numel(), R, Cc, L, Lw, Ho, nbytes=nbytes)
+            try:
+                self._launch('stc_bdg_node_bwd_f32', dY, *grads, _ptr(dTc), _ptr(ws), ws.numel(), R, Cc, L, Lw, Ho, nbytes=nbytes)
+            except StcError as e:
+                if e.code != STC_ELIMIT or dTc is None or Kc < 3:
+                    raise
+                self._node_bwd_dT_by_block(Zs, Tc, W, dY, dTc, grads, ws, (Ks, Kc, R, Cc, L, Lw, Ho), nbytes)
+
+    def _node_bwd_dT_by_block(self, Zs, Tc, W, dY, dTc, grads, ws, dims, nbytes):
+        """The node backward with dT_c where ONE launch of it is beyond the library's limit.  dT_c is formed by the generic kernel alone (the
+        matrix-core kernels leave it out), whose LDS carve holds all Kc - 1 tables and their sums: at C = 64, Ho = 32, Ks = Kc = 3 that is
+        190 - 227 KB against 160, and the entry point answers STC_ELIMIT (nothing launched).  The same gradients from launches that fit: dZ, dW,
+        db from the launch without dT_c (the matrix-core kernels), then per block c >= 1 the generic kernel on the sub-problem of the two
+        blocks {0, c} -- T = [I, T_c], W's row blocks (n, 0), (n, c) -- whose dT[1] IS dT_c (dT_c[p, d] = sum_r sum_o U_c[r, p, o] dY[r, d, o] with
+        U_c = sum_n Z_n W_{n,c} reads no other block); its dZ / dW go to scratch.  A sub-launch beyond the limit itself raises as before."""
+        Ks, Kc, R, Cc, L, Lw, Ho = dims
+        self._launch('stc_bdg_node_bwd_f32', dY, *grads, None, _ptr(ws), ws.numel(), R, Cc, L, Lw, Ho, nbytes=nbytes)
+        dTc[0].zero_()                                                  # T_0 = I is a constant
+        Wv = W.view(Ks, Kc, Lw, Ho)
+        dZ_s = [torch.empty_like(Zs[0]) for _ in range(Ks)]
+        dW_s, dT_s = W.new_empty(Ks * 2 * Lw, Ho), Tc.new_empty(2, Cc, Cc)
+        for c in range(1, Kc):
+            W_c = Wv[:, [0, c]].reshape(Ks * 2 * Lw, Ho).contiguous()
+            T_c = Tc[[0, c]].contiguous()
+            self._launch('stc_bdg_node_bwd_f32', dY, self._ptr_array(Zs), Ks, _ptr(T_c), 2, _ptr(W_c), _ptr(dY), self._ptr_array(dZ_s), _ptr(dW_s), None,
+                         _ptr(dT_s), _ptr(ws), ws.numel(), R, Cc, L, Lw, Ho, nbytes=nbytes)
+            dTc[c].copy_(dT_s[1])
 
     def mix_dT_supported(self, Ks, Kc, Cc, L, Ho) -> bool:
         return bool(self.lib.stc_mix_dt_supported(Ks, Kc, Cc, L, Ho))

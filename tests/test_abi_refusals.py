@@ -348,6 +348,12 @@ case(fn, {'dA': MIS}, EALIGN, 'planes must be 16-byte aligned')
 case(fn, {'dX2': MIS}, EALIGN, 'planes must be 16-byte aligned')
 workspace_cases(fn, ws_bytes(2, 2, 32, 32, 16), EINVAL)
 
+# ---------------------------------------------------------------- added last: the ids above carry their position in the table
+# dT_c is formed by the generic kernel at every dispatch level: C = 64, Ho = 32 at order 3 exceeds its LDS limit in ONE call -- the code that
+# HipKernels._node_bwd_dT_by_block (stc_hip/_lib.py) answers with calls that fit
+for L in (32, 20):
+    case('stc_bdg_node_bwd_f32', {'C': 64, 'Ks': 3, 'Kc': 3, 'L': L, 'Lw': L, 'Z': PP(3), 'dZ': PP(3), 'dTc': P(), 'workspace_bytes': BIG}, ELIMIT, 'B of LDS', 'C=64', 'Ks=3')
+
 
 @pytest.fixture(scope='module')
 def lib():

@@ -267,7 +267,9 @@ def test_learned_graphs_on_the_small_graph_kernels(dev, monkeypatch, N, C, layer
             _close(got[n], per_cell[n], 5e-6, f'learned small-graph d{n} vs the per-cell path', gpu_tol=1e-5)
 
 
-@pytest.mark.parametrize('N,C,K,cin', [(10, 8, 2, 1), (12, 4, 2, 16), (9, 8, 3, 4), (8, 2, 2, 1), (7, 8, 2, 1), (10, 5, 2, 1)])
+@pytest.mark.parametrize('N,C,K,cin', [(10, 8, 2, 1), (12, 4, 2, 16), (9, 8, 3, 4), (8, 2, 2, 1), (7, 8, 2, 1), (10, 5, 2, 1)]
+                         # every C the packed kernels take (tests/shape_lattice.py): two tiles of 16 // C nodes and a ragged third, every input width
+                         + [(2 * (16 // C) + 1, C, 2 + C % 2, (1, 2, 3, 4, 16)[C % 5]) for C in range(1, 17)])
 def test_stc_cell_on_a_fixed_graph_packs_few_categories_into_the_fused_kernels(monkeypatch, N, C, K, cin):
     """One STC_Cell (STC_GNN.py:65-79) on a fixed sparse graph through the per-cell path: where C divides 16 (and the node count divides too) its
     FUSED kernels -- gate math in the node kernels' epilogues and prologues -- run 16 / C nodes per row tile (``ops._cell_pack``, asserted); C = 5
@@ -300,6 +302,40 @@ def test_stc_cell_on_a_fixed_graph_packs_few_categories_into_the_fused_kernels(m
     _close(Hd.grad, H64.grad.float().to(DEV), GRAD, f'packed cell dHt C={C} K={K}')
     for n, p_ in cell.named_parameters():
         _close(p_.grad, sd[n].grad.float().to(DEV), GRAD, f'packed cell d{n} C={C} K={K}')
+
+
+@pytest.mark.parametrize('cin', [16, 1])
+def test_stc_cell_with_a_learned_category_graph_at_64_categories_and_order_3(monkeypatch, cin):
+    """One STC_Cell (STC_GNN.py:65-79) at C = 64, K = 3 with a DIFFERENTIABLE category graph: its gates convolution (Ho = 32) asks the node
+    backward for dT_c at the one matrix-core shape where a single launch of the generic kernel is beyond its LDS limit -- the tensor front then
+    forms dT_c block by block (``HipKernels._node_bwd_dT_by_block``, asserted on the GPU).  New state and every gradient, dGc included, against
+    the float64 oracle."""
+    N, C, K, B, h = 5, 64, 3, 2, 16
+    split = []
+    if DEV == 'cuda':
+        from stc_hip._lib import HipKernels
+        real = HipKernels._node_bwd_dT_by_block
+        monkeypatch.setattr(HipKernels, '_node_bwd_dT_by_block', lambda self, *a: split.append(a[-2][:2]) or real(self, *a))
+    gen = torch.Generator().manual_seed(64 * K + cin)
+    Gs = torch.rand(N, N, generator=gen) * (torch.rand(N, N, generator=gen) < 0.6) / 3
+    Gc = torch.softmax(torch.randn(C, C, generator=gen), -1)
+    Xt, Ht = torch.randn(B, N, C, cin, generator=gen), torch.tanh(torch.randn(B, N, C, h, generator=gen))
+    R = torch.randn(B, N, C, h, generator=gen)
+    cell = M.STC_Cell(N, C, K, K, cin, h).to(DEV)
+    sd = {k: v.detach().cpu().double().requires_grad_() for k, v in cell.state_dict().items()}
+    Xd, Hd, Gcd = _leaf(Xt), _leaf(Ht), _leaf(Gc)
+    out = cell(CsrGraph.from_dense(Gs, device=DEV) if DEV == 'cuda' else CsrGraph.from_dense(Gs), Gcd, Xd, Hd)
+    (out * R.to(DEV)).sum().backward()
+    if DEV == 'cuda':
+        assert split == [(K, K)], split                              # the gates convolution alone: the candidate's (Ho = 16) fits one launch
+    X64, H64, Gc64 = Xt.double().requires_grad_(), Ht.double().requires_grad_(), Gc.double().requires_grad_()
+    want = O.stc_cell(Gs.double(), Gc64, X64, H64, sd['gates.W'], sd['gates.b'], sd['candi.W'], sd['candi.b'], K, K)
+    (want * R.double()).sum().backward()
+    _close(out, want.detach().float().to(DEV), FWD, f'C=64 K=3 learned Gc Hnew cin={cin}')
+    for name, got, ref in (('dXt', Xd.grad, X64.grad), ('dHt', Hd.grad, H64.grad), ('dGc', Gcd.grad, Gc64.grad)):
+        _close(got, ref.float().to(DEV), GRAD, f'C=64 K=3 learned Gc {name} cin={cin}')
+    for n, p_ in cell.named_parameters():
+        _close(p_.grad, sd[n].grad.float().to(DEV), GRAD, f'C=64 K=3 learned Gc d{n} cin={cin}')
 
 
 @pytest.mark.parametrize('N,C,K,layers,T,horizon,seed', [(12, 3, 2, 2, 4, 2, 7), (20, 5, 3, 1, 3, 3, 3), (10, 8, 2, 2, 3, 2, 13), (9, 4, 3, 1, 3, 2, 3)])
@@ -459,7 +495,9 @@ def test_bdg_dif_at_baseline_configuration_2(K):
 
 
 @pytest.mark.parametrize('C,N,K,L,Ho', [(8, 50, 2, 32, 32), (4, 36, 3, 32, 16), (2, 24, 2, 20, 32), (8, 25, 2, 32, 32), (5, 20, 2, 32, 32), (5, 100, 3, 20, 32),
-                                        (7, 13, 2, 32, 16), (12, 9, 3, 32, 32), (16, 10, 2, 20, 16)])
+                                        (7, 13, 2, 32, 16), (12, 9, 3, 32, 32), (16, 10, 2, 20, 16)]
+                         # every C the packed kernels take (tests/shape_lattice.py): two tiles of 16 // C nodes and a ragged third
+                         + [(C, 2 * (16 // C) + 1, 2 + C % 2, (32, 20)[(C // 2) % 2], (32, 16)[(C // 4) % 2]) for C in range(1, 17)])
 def test_bdg_dif_packs_few_categories_into_matrix_core_tiles(monkeypatch, C, N, K, L, Ho):
     """Few categories (C <= 16): floor(16 / C) consecutive nodes run as ONE node of up to 16 categories with a block-diagonal category graph
     on the matrix-core node kernels (``ops._node_pack``; reference STC_GNN.py:38-45 is node-local), dT_c from ``ops._mix_grad``.  Against the
