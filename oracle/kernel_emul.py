@@ -36,6 +36,7 @@ class _Bf16Emulated:
     GPU tests bound)."""
 
     name = 'emulated-cpu-bf16'
+    SPMM_SUM_BF16_MAX_ADD = 5                             # as ``_Bf16Planar``
 
     def __init__(self, em):
         self.em = em
@@ -665,7 +666,12 @@ class EmulatedKernels:
             if o is not None:
                 z.add_(o)
 
+    SPMM_SUM_MAX_ADD = 8                                  # as ``HipKernels``, refused beyond it as there
+
     def spmm_sum(self, rowptr, colidx, val, plan, X, X2, addends, Y, blend=None, alpha=1.0, amax=None):
+        if len(addends) > self.SPMM_SUM_MAX_ADD:
+            from stc_hip._lib import StcError
+            raise StcError(f'spmm_sum: at most {self.SPMM_SUM_MAX_ADD} addends, got {len(addends)}')
         B, n, Cc, h = Y.shape
         src = X if X2 is None else X + X2
         self.csr_spmm(rowptr, colidx, val, n, n, src.reshape(B, n, Cc * h), None, Y.view(B, n, Cc * h), float(alpha), 0.0)

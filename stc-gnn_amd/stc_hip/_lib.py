@@ -467,7 +467,7 @@ class HipKernels:
         self._launch('stc_spmm_sum_f32', Y, *g, n, n, _ptr(X), _ptr(X2), float(alpha), len(addends), ptrs, lds, offs, scales, _ptr(Y), _ptr(U), _ptr(Cand), _ptr(dY),
                      _ptr(amax), 0 if amax is None else amax.numel(), B, Cc, h, nbytes=nbytes)
 
-    RING2_MAX_ADD = RING2_MAX_ADD         # (the cell-graph executor reads it from the kernel set)
+    RING2_MAX_ADD, SPMM_SUM_MAX_ADD = RING2_MAX_ADD, SPMM_SUM_MAX_ADD     # (the cell-graph executor reads them from the kernel set)
 
     @staticmethod
     def ring2_fits(B, n, Cc, h) -> bool:
@@ -1603,6 +1603,7 @@ class _Bf16Planar:
     entry points refuse, and their argument lists (those of the fp32 entry points without format, maxima, accumulate flags, offsets)."""
 
     name = 'hip-gfx950-bf16'
+    SPMM_SUM_BF16_MAX_ADD = SPMM_SUM_BF16_MAX_ADD     # (as ``HipKernels.SPMM_SUM_MAX_ADD``)
 
     def __init__(self, base: HipKernels):
         self.b = base

@@ -25,12 +25,14 @@ first call raises ``StcError``.
 from __future__ import annotations
 
 import enum
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
+from ._lib import SPMM_SUM_BF16_MAX_ADD, SPMM_SUM_MAX_ADD          # addends of stc_spmm_sum_bf16 / _f32
 from .graph import SpatialOperand
 from .small import (_alias, _check_guard, _guard, _out_slots, _refuse_differentiable, _stacks, _unpack, last_uses, small_graph_supported,
                     stc_small_graph, wavefront)
@@ -536,6 +538,7 @@ _SMALL = True            # small graphs (N*C rows per sample fit the caches, C <
 _RING2 = True            # state gradient + transpose aggregation of dY in one launch where the graph has a two-ring plan (no dY plane)
 _RING2_FWD = True        # ... and the forward's blend + aggregation of the new state (stc_ring2_blend_f32)
 _FIRST_STEP = True       # cells on the zero initial state (a layer's first time step) in their first-step forms: no H, S.H, R planes, no dH, dS.H
+_SUM_GATHERS, _CHAIN_FIRST_ADD = 2, 2     # kernel limits, not switches: planes that stc_spmm_sum_* / the two-ring launches gather through S (X, X2); first-ring addends of stc_ring2_chain_f32
 
 _ZEROS = {}              # (device, dtype) -> one zero, never written: what ``zero_state`` views
 
@@ -607,6 +610,10 @@ class _Form(enum.Enum):
     def planar(self) -> bool:
         return self not in (_Form.ROWS_POST, _Form.ROWS_SLABS)
 
+
+# form -> the methods of (``_ForwardPass``, ``_BackwardPass``) that hold its launches
+_FORM_METHODS = {_Form.PLANAR3: ('planar3', 'planar3'), _Form.PLANAR_ONE_BWD: ('planar', 'planar_one_bwd'), _Form.PLANAR: ('planar', 'planar'),
+                 _Form.ROWS_POST: ('rows_cell', 'rows_cell'), _Form.ROWS_SLABS: ('rows_cell', 'rows_cell')}
 
 def _cell_forms(k, Ks: int, Kc: int, C: int, h: int, cin, bf16: bool):
     """The ``_Form`` of every cell from its input width ``cin[j]``: planar where the planar kernels take the shape -- 16 + 16 columns, or
@@ -818,19 +825,9 @@ class _ForwardPass(_Pass):
         U = self.plane()
         Rg, Cand = (None, None) if (self.lean and form.planar) else (None if first else self.plane(), self.plane())
         Hnew = self.plane() if out is None else out
-        run = self.planar3 if form is _Form.PLANAR3 else self.planar if form.planar else self.rows_cell
-        more = run(j, *stack, Hprev, U, Rg, Cand, Hnew, copies, side)
+        more = getattr(self, _FORM_METHODS[form][0])(j, *stack, Hprev, U, Rg, Cand, Hnew, copies, side)
         self.finish(j, Hnew, late_copies, late_rows)
         return [Hprev, U, Rg, Cand, *more]
-
-    # ---- forward only: the order the cells run in and what is dropped after each
-    def wavefront(self):
-        """The cells by level, schedule order inside a level (``small.wavefront``: shared with the few-category executor)."""
-        return wavefront(self.schedule)
-
-    def last_uses(self, order):
-        """source -> the cell after whose launches nothing in ``order`` reads it any more."""
-        return last_uses(self.schedule, order)
 
     def release(self, j, last, keep):
         """After cell j: its input rows, and every source it was the last consumer of -- the state (unless it is in ``keep``: the outputs live in
@@ -843,109 +840,143 @@ class _ForwardPass(_Pass):
                     self.state[src[1]] = None
 
 
+def _presum(ts, limit: int, tail: bool = False):
+    """The list ``ts`` folded down to ``limit`` tensors for a kernel that takes no more: the last two into one (``tail``) or the first two, until it fits."""
+    while len(ts) > limit:
+        ts = ts[:-2] + [ts[-1] + ts[-2]] if tail else [ts[0] + ts[1]] + ts[2:]
+    return ts
+
+
+class _Ledger(dict):
+    """cell -> what its state is still owed, for every state something downstream depends on: a record with the fields ``done``, a finished
+    gradient tensor (from the outputs and interleaved consumers) or None; ``d`` = (d0, d1, d2), lists of planes owed to the state, to S.state
+    and to T_2(S).state (from planar consumers); ``shared``, the (direct, aggregated) pair of ``claim`` or None (its planes are also in d0, d1).
+    Aggregation being linear, the state's gradient is  done + sum d0 - sum d2 + S^T (sum d1 + 2 S^T sum d2)  (Clenshaw form of sum_n T_n(S)^T d_n):
+    narrow SpMMs with the sums in their gather / epilogue instead of a wide transpose SpMM and a split pass per consuming cell.  An order-2
+    consumer leaves no d2: its state's gradient is the same formula with d2 empty, done + sum d0 + S^T sum d1, ONE SpMM."""
+
+    pending = dict.get                                              # the record of a state that is owed something, else None
+    take = dict.pop                                                 # ... which leaves the ledger: its own cell runs
+
+    def _rec(self, kid):
+        return self.setdefault(kid, SimpleNamespace(done=None, d=([], [], []), shared=None))
+
+    def finished(self, kid):
+        return self[kid].done if kid in self else None
+
+    def finish(self, kid, t):
+        self._rec(kid).done = t
+
+    def leave(self, kid, d0, d1, d2=()):
+        for have, more in zip(self._rec(kid).d, (d0, d1, d2)):
+            have += more
+
+    def claim(self, src, claimed: set, new, share: bool):
+        """(direct plane, aggregated plane, accumulate) of source ``src`` for a one-launch consumer.  The first consumer's fresh planes become
+        the state's shared pair; a later consumer gets them back with accumulate = True and ADDS into them, so the state-gradient SpMM gathers
+        one operand and reads one direct plane per state, not one per consumer.  ``share``: fp32 planes only (the bf16 kernels have no
+        accumulate flags).  One claim per consuming cell per state: ``claimed`` is the set of states whose pair that cell holds, so a cell
+        that reads one state on both sides takes the pair for its first side and fresh planes (``new()``) for the other."""
+        if src[0] != 'cell':
+            return new(), new(), False                              # an external tensor: gradients computed, nobody owed
+        rec = self._rec(src[1])
+        if share and rec.shared is not None and src[1] not in claimed:
+            claimed.add(src[1])
+            return (*rec.shared, True)
+        d, a = new(), new()
+        self.leave(src[1], [d], [a])
+        if share and rec.shared is None:
+            rec.shared = (d, a)
+            claimed.add(src[1])
+        return d, a, False
+
+
+class _ParamGrads:
+    """The parameter gradients of one backward.  Every planar cell writes its (dWg, dbg, dWc, dbc) into its own row of ONE buffer per parameter
+    set (``next_row``), summed once at the end -- not four accumulation passes per cell (176 five-microsecond launches per metric step);
+    the interleaved cells' gradients are accumulated as they come (``add``: reverse schedule order), the row sums after them."""
+
+    def __init__(self, stacks, schedule):
+        self.stacks, self.schedule, self.rows, self.acc = stacks, schedule, {}, [[None] * 4 for _ in stacks]   # rows: set -> (row buffer, its rows still to hand out)
+
+    def _views(self, s_id, row):                                    # (dWg, dbg, dWc, dbc) as views of one row of the set's buffer
+        st = self.stacks[s_id]
+        parts = row.split([0 if t is None else t.numel() for t in st])
+        return tuple(None if t is None else part.view_as(t) for t, part in zip(st, parts))
+
+    def next_row(self, s_id):
+        if s_id not in self.rows:
+            st = self.stacks[s_id]
+            buf = st[0].new_zeros(sum(1 for sc in self.schedule if sc[0] == s_id), sum(t.numel() for t in st if t is not None))
+            self.rows[s_id] = (buf, iter(buf))
+        return self._views(s_id, next(self.rows[s_id][1]))
+
+    def add(self, s_id, grads):
+        self.acc[s_id] = [a if t is None else t if a is None else a.add_(t) for a, t in zip(self.acc[s_id], grads)]
+
+    def result(self):
+        for s_id, (buf, _) in self.rows.items():
+            self.add(s_id, self._views(s_id, buf[0] if buf.shape[0] == 1 else buf.sum(0)))
+        return [None if prm is None else (g if g is not None else torch.zeros_like(prm)) for st, a in zip(self.stacks, self.acc) for prm, g in zip(st, a)]
+
+
 class _BackwardPass(_Pass):
-    """... and, in the backward, the gradients owed to every state -- finished tensors (``G``) from the outputs and interleaved consumers,
-    pieces from planar consumers -- and the parameter-gradient rows of the planar cells."""
+    """... and, in the backward, what every state is still owed (``owes``: one ``_Ledger`` record per state, filled by its consumers through ``finish`` /
+    ``leave`` / ``claim``, emptied by ``owed`` / ``owed_ring2`` when its own cell runs) and the parameter gradients (``params``: ``_ParamGrads``)."""
 
     def __init__(self, k, op: SpatialOperand, Ks: int, Tc, schedule, stacks, cin, forms, dims, bf16: bool, zmax_all):
         super().__init__(k, op, Ks, Tc, schedule, cin, forms, dims, bf16, zmax_all, (op.bwd_rowptr, op.bwd_colidx, op.bwd_val, op.bwd_plan))
-        self.stacks = stacks
         # state gradient sums fused with a transpose aggregation where the graph has a two-ring plan (stc_ring2_sum_f32 / _chain_f32)
         self.ring2 = _RING2 and not bf16 and op.bwd_ring2 is not None and k.ring2_fits(self.B, self.N, self.C, self.h)
-        self.G = {}                                                 # cell -> gradient its state is owed so far
-        # Planar consumers leave PIECES of a state's gradient instead of a finished tensor: direct planes (what the state
-        # is owed as a plane of their inputs) and aggregated planes (what its aggregation S.state is owed).  Aggregation
-        # being linear, the state's gradient is  sum(direct) + S^T sum(aggregated): ONE narrow SpMM per state with the
-        # sums in its gather / epilogue -- instead of a wide transpose SpMM and a split pass per consuming cell.
-        self.pieces = {}
-        # Parameter gradients of the planar cells: every cell writes its (dWg, dbg, dWc, dbc) into its own row of ONE buffer per parameter
-        # set, summed once at the end -- instead of four accumulation passes per cell (176 five-microsecond launches per metric step).
-        self.rows_of_set = {}
-
-    def grads_for(self, s_id):                                      # the next row of the set's buffer
-        if s_id not in self.rows_of_set:
-            Wg_, bg_, Wc_, bc_ = self.stacks[s_id]
-            sizes = [Wg_.numel(), 0 if bg_ is None else 2 * self.h, Wc_.numel(), 0 if bc_ is None else self.h]
-            self.rows_of_set[s_id] = [Wg_.new_zeros(sum(1 for sc in self.schedule if sc[0] == s_id), sum(sizes)), 0, sizes]
-        entry = self.rows_of_set[s_id]
-        entry[1] += 1
-        return self.param_views(s_id, entry[0][entry[1] - 1])
-
-    def param_views(self, s_id, row):                               # (dWg, dbg, dWc, dbc) as views of one row of the set's buffer
-        Wg_, bg_, Wc_, bc_ = self.stacks[s_id]
-        parts = row.split(self.rows_of_set[s_id][2])
-        return parts[0].view_as(Wg_), None if bg_ is None else parts[1], parts[2].view_as(Wc_), None if bc_ is None else parts[3]
-
-    def leave(self, kid, direct, aggregated):
-        pc = self.pieces.setdefault(kid, dict(direct=[], agg=[]))
-        pc['direct'] += direct
-        pc['agg'].append(aggregated)
+        self.owes, self.params = _Ledger(), _ParamGrads(stacks, schedule)
 
     def owed(self, kid, blend=None):
-        """The gradient of state ``kid`` from what its consumers left; with ``blend`` = (U, Cand) of its cell also dY = gradient * U * (1 - Cand^2)."""
-        base = self.G.pop(kid, None)                                # from interleaved consumers / the outputs: a finished tensor
-        pc = self.pieces.pop(kid, None)
-        if pc is None:
+        """The gradient of state ``kid`` from its record; with ``blend`` = (U, Cand) of its cell also dY = gradient * U * (1 - Cand^2)."""
+        rec = self.owes.take(kid)
+        base, (d0, d1, d2) = rec.done, rec.d
+        if not d1:                                                  # no planar consumer: the finished tensor is the gradient
             if blend is None:
                 return base
             dY = torch.empty_like(base)
             self.k.gru_blend_bwd(base, blend[0], None, blend[1], dY, None, None)
             return base, dY
-        if 'd2' in pc:                                              # pieces of order-3 consumers (``leave3``; their states need no blend)
-            return self.clenshaw(pc['d0'] + ([base] if base is not None else []), pc['d1'], pc['d2'])
-        add = pc['direct'] + ([base] if base is not None else [])
-        aggs = pc['agg']
-        while len(add) > 5:                                         # more consumers than the kernel takes addends for: pre-sum
-            add.append(add.pop() + add.pop())
-        while len(aggs) > 2:
-            aggs = [aggs[0] + aggs[1]] + aggs[2:]
-        out = torch.empty_like(aggs[0])
-        dY = torch.empty_like(out) if blend is not None else None
-        self.k.spmm_sum(*self.graph, aggs[0], aggs[1] if len(aggs) > 1 else None, [(t, 0) for t in add], out,
-                   blend=None if blend is None else (blend[0], blend[1], dY))
+        d0 = d0 + ([base] if base is not None else [])
+        if d2:                                                      # order-3 consumers (their states need no blend)
+            return self.clenshaw(d0, d1, d2)
+        # more consumers than the kernel takes addends for: pre-sum -- on fp32 planes too above the bf16 kernel's limit, below their own (SPMM_SUM_MAX_ADD)
+        add = _presum(d0, SPMM_SUM_BF16_MAX_ADD, tail=True)
+        aggs = _presum(d1, _SUM_GATHERS)
+        out, dY = torch.empty_like(aggs[0]), torch.empty_like(aggs[0]) if blend is not None else None
+        self.k.spmm_sum(*self.graph, aggs[0], aggs[1] if len(aggs) > 1 else None, [(t, 0) for t in add], out, blend=None if blend is None else (blend[0], blend[1], dY))
         return out if blend is None else (out, dY)
 
     def owed_ring2(self, kid, U_, Cand_):
         """(gradient of state ``kid``, S^T (gradient * U * (1 - Cand^2))) in one launch where the graph has a two-ring plan; None: the two
-        launches (``owed`` with its blend epilogue, then the narrow aggregation)."""
-        pc = self.pieces.get(kid)
-        if not self.ring2 or pc is None:
-            return None
-        add = pc['direct'] + ([self.G[kid]] if kid in self.G else [])
+        launches (``owed`` with its blend epilogue, then the narrow aggregation) -- the record is then left as it is."""
+        rec = self.owes.pending(kid)
+        add = [] if rec is None else rec.d[0] + ([rec.done] if rec.done is not None else [])
         # (the forms that fit the register file: one aggregated plane, up to two addends -- 590 / 680 us for the 555 + 185 they replace; with a
         #  second aggregated plane the kernel spills and takes 840 - 1 150 us: the two launches stay)
-        if len(add) > 2 or len(pc['agg']) != 1:
+        if not self.ring2 or rec is None or len(add) > 2 or len(rec.d[1]) != 1:
             return None
-        self.G.pop(kid, None)
-        self.pieces.pop(kid)
-        out, dBm_ = torch.empty_like(pc['agg'][0]), torch.empty_like(pc['agg'][0])
-        self.k.ring2_sum(*self.graph[:3], self.op.bwd_ring2, pc['agg'][0], None, add, U_, Cand_, out, dBm_)
+        agg = self.owes.take(kid).d[1][0]
+        out, dBm_ = torch.empty_like(agg), torch.empty_like(agg)
+        self.k.ring2_sum(*self.graph[:3], self.op.bwd_ring2, agg, None, add, U_, Cand_, out, dBm_)
         return out, dBm_
 
-    # Order 3: a consumer leaves direct planes d0 and the gradients d1, d2 of the S / T_2(S) planes; the source's gradient is
-    #   sum d0 - sum d2 + S^T (sum d1 + 2 S^T sum d2)          (Clenshaw form of sum_n T_n(S)^T d_n)
-    # = two narrow SpMMs with the sums in their gather / epilogue (alpha and signed addends of stc_spmm_sum_f32).
-    def leave3(self, kid, d0, d1, d2):
-        pc = self.pieces.setdefault(kid, dict(d0=[], d1=[], d2=[]))
-        pc['d0'] += list(d0); pc['d1'] += list(d1); pc['d2'] += list(d2)
-
     def clenshaw(self, d0, d1, d2):
-        """sum d0 - sum d2 + S^T (sum d1 + 2 S^T sum d2) from lists of planes (d2 non-empty)."""
-        k = self.k
-        while len(d2) > 2:                                          # the kernel gathers two operands: pre-sum the rest
-            d2 = [d2[0] + d2[1]] + d2[2:]
-        if self.ring2 and len(d1) <= 2 and 1 <= len(d0) + len(d2) <= k.RING2_MAX_ADD:
+        """sum d0 - sum d2 + S^T (sum d1 + 2 S^T sum d2) from lists of planes (d2 non-empty): two narrow SpMMs with the sums in their gather /
+        epilogue (alpha and signed addends of stc_spmm_sum_f32), each list pre-summed from its front to what the launch takes."""
+        k, d2 = self.k, _presum(d2, _SUM_GATHERS)
+        if self.ring2 and len(d1) <= _CHAIN_FIRST_ADD and 1 <= len(d0) + len(d2) <= k.RING2_MAX_ADD:
             # both transpose aggregations in one launch (stc_ring2_chain_f32): the inner sum d1 + 2 S^T d2 never leaves the chip
             out = torch.empty_like(d2[0])
             k.ring2_chain(*self.graph[:3], self.op.bwd_ring2, d2[0], d2[1] if len(d2) > 1 else None, 2.0, list(d1), None, 1.0,
                           [(a, 1.0) for a in d0] + [(a, -1.0) for a in d2], out)
             return out
         t = torch.empty_like(d2[0])
-        k.spmm_sum(*self.graph, d2[0], d2[1] if len(d2) > 1 else None, [(a, 0) for a in d1], t, alpha=2.0)
-        adds = [(a, 0) for a in d0] + [(a, 0, -1.0) for a in d2]
-        while len(adds) > 8:
-            (a, _), (b_, _) = adds.pop(0), adds.pop(0)
-            adds.insert(0, (a + b_, 0))
+        k.spmm_sum(*self.graph, d2[0], d2[1] if len(d2) > 1 else None, [(a, 0) for a in _presum(d1, SPMM_SUM_MAX_ADD)], t, alpha=2.0)
+        adds = [(a, 0) for a in _presum(d0, SPMM_SUM_MAX_ADD - len(d2))] + [(a, 0, -1.0) for a in d2]
         out = torch.empty_like(t)
         k.spmm_sum(*self.graph, t, None, adds, out, blend=None)
         return out
@@ -957,7 +988,7 @@ class _BackwardPass(_Pass):
         Zx, Zh = [Zx0, Zx1, Zx2], [Hprev, Zh1, Zh2]
         wide = self.cin[j] == self.h
         new = lambda: torch.empty_like(Hprev)
-        dWg, dbg, dWc, dbc = self.grads_for(s_id)                   # (parameter gradients: rows of the set's buffer, summed at the end)
+        dWg, dbg, dWc, dbc = self.params.next_row(s_id)             # (parameter gradients: rows of the set's buffer, summed at the end)
         dHnew = self.owed(j)
         dX, dR = ([new(), new(), new()] if wide else [None] * 3), [new(), new(), new()]
         k.cell_cand_bwd_planar_k(rows(Zx), rows(Zr), Tc, Wc, *rows((dHnew, U, Cand)), rows(dX), rows(dR), dWc, dbc, **self.act_slots(j, 1))
@@ -969,9 +1000,9 @@ class _BackwardPass(_Pass):
         k.cell_gates_bwd_planar_k(rows(Zx), rows(Zh), Tc, Wg, *rows((dRH, Cand, U, Rg, dHnew)), rows(dX), rows(dHg), dWg, dbg, None,
                                   accumulate_x=wide, **self.act_slots(j, 0))
         if wide and x[0] == 'cell':
-            self.leave3(x[1], dX[:1], dX[1:2], dX[2:])
+            self.owes.leave(x[1], dX[:1], dX[1:2], dX[2:])
         if hs[0] == 'cell':
-            self.leave3(hs[1], dHg[:1], dHg[1:2], dHg[2:])
+            self.owes.leave(hs[1], dHg[:1], dHg[1:2], dHg[2:])
 
     def planar_one_bwd(self, j, Wg, bg, Wc, bc, saved):
         k, (s_id, x, hs) = self.k, self.schedule[j]
@@ -983,33 +1014,15 @@ class _BackwardPass(_Pass):
             dHnew, dY = self.owed(j, (U, Cand))
             dBm = self.spmm(dY)
             del dY                                                  # (the kernel re-forms dY from dHnew, U, Cand)
-        new = lambda: torch.empty_like(U)
-        dWg, dbg, dWc, dbc = self.grads_for(s_id)
-        # A state has two consumers (next step as H, next layer as X): the first one processed writes the state's direct and
-        # aggregated gradient planes, the second ADDS into them (accumulate_x / accumulate_h), so the state-gradient SpMM gathers
-        # one operand instead of two and reads one direct plane instead of two.
-        taken = set()
-
-        def planes_of_state(src):
-            if src[0] != 'cell':
-                return new(), new(), False                          # an external tensor: gradients computed, nobody owed
-            pc = self.pieces.get(src[1])
-            if not self.bf16 and pc is not None and pc.get('own') is not None and src[1] not in taken:
-                taken.add(src[1])
-                return pc['own'][0], pc['own'][1], True
-            d, a_ = new(), new()
-            self.leave(src[1], (d,), a_)
-            if self.pieces[src[1]].get('own') is None:
-                self.pieces[src[1]]['own'] = (d, a_)
-                taken.add(src[1])
-            return d, a_, False
-
-        dXd, dSX, acc_x = planes_of_state(x) if self.cin[j] == self.h else (None, None, False)
+        dWg, dbg, dWc, dbc = self.params.next_row(s_id)
+        # (a state's second consumer ADDS into the planes its first one wrote: ``_Ledger.claim``; claimed: the states whose planes this cell holds)
+        new, claimed = (lambda: torch.empty_like(U)), set()
+        dXd, dSX, acc_x = self.owes.claim(x, claimed, new, not self.bf16) if self.cin[j] == self.h else (None, None, False)
         if Hprev is None:                                           # the forward ran the first-step forms: no H, S.H, R; nobody is owed dH, dS.H
             k.cell_bwd_first(*self.rows((Xp, SXp)), self.Tc, Wg, Wc, *self.rows((U, Cand, dHnew, dBm)), self.rows((dXd, dSX)), dWg, dbg, dWc, dbc,
                              accumulate_x=acc_x, **self.act_slots(j))
             return
-        dHd, dSH, acc_h = planes_of_state(hs)
+        dHd, dSH, acc_h = self.owes.claim(hs, claimed, new, not self.bf16)
         k.cell_bwd_planar(*self.rows((Xp, Hprev, SXp, SHp)), self.Tc, Wg, Wc, *self.rows((U, Rg, Cand, dHnew, dBm)),
                           self.rows((dXd, dSX, dHd, dSH)), dWg, dbg, dWc, dbc,
                           **(dict(accumulate_x=acc_x, accumulate_h=acc_h, **self.act_slots(j)) if not self.bf16 else {}))
@@ -1025,7 +1038,7 @@ class _BackwardPass(_Pass):
         post_kw, gates_kw = ({}, {}) if zr is None else (dict(act_amax=(zr[0], zr[2])), dict(act_amax=zr))
         dBm = self.spmm(dY)
         dRH = torch.empty_like(Hprev)
-        dWg, dbg, dWc, dbc = self.grads_for(s_id)
+        dWg, dbg, dWc, dbc = self.params.next_row(s_id)
         dHd, dSH = torch.empty_like(Hprev), torch.empty_like(Hprev)
         if wide:
             dXc, dXd, dSX = (torch.empty_like(Hprev) for _ in range(3))
@@ -1039,12 +1052,12 @@ class _BackwardPass(_Pass):
         # (dH = None: the kernel adds the prologue's share into the H plane's gradient)
         k.cell_gates_bwd_planar(*rows((Xp, Hprev, SXp, SHp)), Tc, Wg, *rows((dRH, Cand, U, Rg, dHnew)), planes, dWg, dbg, None, **gates_kw)
         if wide and x[0] == 'cell':
-            self.leave(x[1], (dXd, dXc), dSX)                       # as the X plane: gates' and candidate's direct shares
+            self.owes.leave(x[1], [dXd, dXc], [dSX])                # as the X plane: gates' and candidate's direct shares
         if hs[0] == 'cell':
-            self.leave(hs[1], (dHd,), dSH)                          # as the H plane, the gates prologue's share included
+            self.owes.leave(hs[1], [dHd], [dSH])                    # as the H plane, the gates prologue's share included
 
     def rows_cell(self, j, Wg, bg, Wc, bc, saved):
-        """ROWS_POST and ROWS_SLABS; the sources get finished gradient tensors.  Returns the cell's (dWg, dbg, dWc, dbc)."""
+        """ROWS_POST and ROWS_SLABS; the sources get finished gradient tensors, the parameter gradients are added to their set's as they come."""
         k, op, Ks, h, Tc, (s_id, x, hs) = self.k, self.op, self.Ks, self.h, self.Tc, self.schedule[j]
         Hprev, U, Rg, Cand, *Z = saved
         Zg, Zc = Z[:Ks], Z[Ks:]
@@ -1069,14 +1082,14 @@ class _BackwardPass(_Pass):
                 self.spmm(g[1], g[0], g[0], 1.0, 1.0)
             dXt = Hprev.new_empty(Hprev.shape[:-1] + (self.cin[j],))
             same = need_x and need_h and x[1] == hs[1]
-            owedA = self.G.get(x[1]) if need_x else None
-            owedB = self.G.get(hs[1]) if (need_h and not same) else None
+            owedA = self.owes.finished(x[1]) if need_x else None
+            owedB = self.owes.finished(hs[1]) if (need_h and not same) else None
             k.split2(g[0], dXt, dH, addA=dci, addB=dH, addA_ld=Zc[0].shape[-1], addA2=owedA, addB2=owedB)
             if need_h and not same:
-                self.G[hs[1]] = dH
+                self.owes.finish(hs[1], dH)
             if need_x:
-                self.G[x[1]] = dXt.add_(dH) if same else dXt
-        return dWg, dbg, dWc, dbc
+                self.owes.finish(x[1], dXt.add_(dH) if same else dXt)
+        self.params.add(s_id, (dWg, dbg, dWc, dbc))
 
 
 def _begin_forward(op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, tensors, forward_only: bool = False):
@@ -1107,8 +1120,8 @@ def _forward_only(op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc
     (``_ForwardPass.lean``; stc_hip.h, ABI v34).  Interleaved cells, the bf16 set and kernel sets without ``optional_gate_stores`` get the
     liveness only.  The states are bit for bit those of the autograd node."""
     p, stacks, out_stack, out_slot = _begin_forward(op, Ks, schedule, outputs, n_ext, Tc, fwd_val, tensors, forward_only=True)
-    order = p.wavefront()
-    last = p.last_uses(order)
+    order = wavefront(schedule)                                  # the cells by level, schedule order inside a level
+    last = last_uses(schedule, order)                            # source -> the cell after whose launches nothing reads it any more
     for j in order:
         p.cell(j, stacks[schedule[j][0]], out_stack[out_slot[j]] if j in out_slot else None)
         p.release(j, last, out_slot)
@@ -1117,7 +1130,6 @@ def _forward_only(op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc
 
 class _StcCellGraph(Function):
     """Encoder + decoder (any DAG of STC_Cells whose inputs are other cells' states) as one autograd node.
-
     Per cell the kernels are those of ``_StcCell``'s fused path.  What owning the whole schedule adds:
       * planar cells (inputs of 16 + 16 columns, i.e. every cell above layer 0): the [Xt | H] row of reference
         STC_GNN.py:68 is never built -- the kernels read the two state tensors as two planes, and the aggregation S.state is
@@ -1125,13 +1137,12 @@ class _StcCellGraph(Function):
       * interleaved cells (layer 0: 1 + 16 columns padded to 20): no concat pass either -- the producer's blend epilogue
         writes the new state straight into their input rows (state copies of ``stc_spmm_blend_fwd_f32`` / ``stc_cell_blend_fwd_f32``);
       * the candidate convolution in post-aggregation form where the kernels exist (``_POST_AGG``);
-      * no autograd accumulation passes: a state consumed by two cells (next step, next layer) gets its two gradient
-        contributions summed inside the consumers' final split (``stc_split2_f32`` addA2 / addB2), in schedule order.
+      * no autograd accumulation passes: what a state's consumers owe it is kept in ONE record per state (``_Ledger``) -- summed inside an
+        interleaved consumer's final split (``stc_split2_f32`` addA2 / addB2), or inside the state's own narrow SpMM for planar consumers.
     Every cell runs in one of five forms (``_Form``), chosen once before the forward's launches: PLANAR3 (order 3), PLANAR_ONE_BWD and
     PLANAR (order 2: one-launch or two-launch backward), ROWS_POST and ROWS_SLABS (interleaved rows; candidate as Y = A + S.Bm or on slabs).
-    The launches of each form are one method of ``_ForwardPass`` and one of ``_BackwardPass``.
-    schedule[j] = (stack, ('ext', i) | ('cell', k), ('ext', i) | ('cell', k)): parameter set, source of Xt, source of H.
-    """
+    The launches of each form are one method of ``_ForwardPass`` and one of ``_BackwardPass`` (``_FORM_METHODS``); the parameter gradients
+    of a backward are one ``_ParamGrads``.  schedule[j] = (stack, Xt source, H source), a source being ('ext', i) or ('cell', k)."""
 
     @staticmethod
     def forward(ctx, op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, *tensors):
@@ -1162,23 +1173,12 @@ class _StcCellGraph(Function):
         p = _BackwardPass(k, op, Ks, Tc, schedule, stacks, cin, forms, dims, bf16, ctx.zmax_all)
         grad_stack = _c(grad_stack)
         for i, j in enumerate(outputs):
-            p.G[j] = grad_stack[i]                                   # read-only here: sums go to fresh buffers
-        acc = [[None] * 4 for _ in stacks]                           # parameter gradients of the interleaved cells, then of the planar ones
-
-        def add_to(s_id, grads):
-            acc[s_id] = [a if t is None else t if a is None else a.add_(t) for a, t in zip(acc[s_id], grads)]
-
+            p.owes.finish(j, grad_stack[i])                          # read-only here: sums go to fresh buffers
         for j in range(len(schedule) - 1, -1, -1):
-            if j not in p.G and j not in p.pieces:
+            if not p.owes.pending(j):
                 continue                                             # nothing downstream depends on this cell
-            s_id, f = schedule[j][0], forms[j]
-            run = {_Form.PLANAR3: p.planar3, _Form.PLANAR_ONE_BWD: p.planar_one_bwd, _Form.PLANAR: p.planar}.get(f, p.rows_cell)
-            grads = run(j, *stacks[s_id], cells[j])
-            if not f.planar:
-                add_to(s_id, grads)
-        for s_id, (buf, _, _) in p.rows_of_set.items():
-            add_to(s_id, p.param_views(s_id, buf[0] if buf.shape[0] == 1 else buf.sum(0)))
-        flat = [None if prm is None else (g if g is not None else torch.zeros_like(prm)) for st, a in zip(stacks, acc) for prm, g in zip(st, a)]
+            getattr(p, _FORM_METHODS[forms[j]][1])(j, *stacks[schedule[j][0]], cells[j])
+        flat = p.params.result()
         n_ext = len(ctx.needs_input_grad) - 7 - len(flat)
         return (None,) * 7 + (None,) * n_ext + tuple(flat)
 

@@ -24,6 +24,7 @@ from oracle.kernel_emul import EmulatedKernels
 from stc_hip import CsrGraph, ops
 from tests.conftest import REPO, load_golden, rel_err, sub_dict
 from tests.golden.make_golden import SF_SHAPE, bench_path_inputs, synth_inputs
+from tests.launch_trace import FANOUT_OUTPUTS, FANOUT_SCHEDULE
 
 FWD = 2e-6       # CPU-emulated bound, forward
 GRAD = 5e-6      # CPU-emulated bound, gradients
@@ -798,7 +799,7 @@ GENERAL_SCHEDULE = [(1, ('ext', 0), ('ext', 2)),      # 0: narrow cell on extern
 GENERAL_OUTPUTS = [6, 3]
 
 
-def _general_schedule(C, K, tol=3e-6):
+def _general_schedule(C, K, tol=3e-6, schedule=GENERAL_SCHEDULE, outputs=GENERAL_OUTPUTS):
     Hh, Ww, h, B = 4, 5, 16, 2
     N = Hh * Ww
     torch.manual_seed(77)
@@ -809,7 +810,6 @@ def _general_schedule(C, K, tol=3e-6):
     x0 = torch.rand(B, N, C, 1).to(DEV)
     xw = torch.rand(B, N, C, h).to(DEV)
     h0 = torch.rand(B, N, C, h).to(DEV)
-    schedule, outputs = GENERAL_SCHEDULE, GENERAL_OUTPUTS
     cells = (wide, narrow)
     stacks = [(c.gates.W, c.gates.b, c.candi.W, c.candi.b) for c in cells]
     Rw = torch.randn(len(outputs), B, N, C, h).to(DEV)
@@ -836,6 +836,29 @@ def _general_schedule(C, K, tol=3e-6):
     _close(got, want, 2e-6, 'general schedule: states', gpu_tol=3e-6)
     for n in g0:
         _close(g1[n], g0[n], tol, f'general schedule: d{n}', gpu_tol=6e-6)
+
+
+@pytest.mark.parametrize('planar,post_agg,K,two_launch', [(True, True, 2, False), (True, True, 2, True), (False, True, 2, False), (False, False, 2, False),
+                                                          (True, True, 3, False), (False, True, 3, False)])
+def test_cell_graph_fan_out_matches_autograd(dev, monkeypatch, planar, post_agg, K, two_launch):
+    """``FANOUT_SCHEDULE`` (tests/launch_trace.py): ONE state consumed by eight cells, seven times as input and once as state, every consumer an
+    output -- the state's record holds more planes than the state-gradient launches take addends or gather operands for, on every list: 15
+    direct + 8 aggregated planes at order 2 with the two-launch backward, (8, 8, 8) at order 3.  Against the composition from ``ops.stc_cell``,
+    at the tolerances of ``test_cell_graph_general_schedules_match_autograd``."""
+    monkeypatch.setattr(ops, '_PLANAR', planar)
+    monkeypatch.setattr(ops, '_POST_AGG', post_agg)
+    monkeypatch.setattr(ops, '_SMALL', False)
+    if two_launch:
+        monkeypatch.setattr(type(ops.kernels()), 'cell_bwd_planar_supported', lambda self, Cc, hh: False)
+    _general_schedule(32 if DEV == 'cuda' else 4, K, schedule=FANOUT_SCHEDULE, outputs=FANOUT_OUTPUTS)
+
+
+def test_cell_graph_nine_order3_consumers(dev, monkeypatch):
+    """One consumer more: nine planes per list at order 3, more first-ring planes than ``spmm_sum`` takes addends -- pre-summed like the
+    other lists (without the pre-sum the launch is refused: ``StcError``).  Two-ring plans off: the sums go through ``spmm_sum``."""
+    monkeypatch.setattr(ops, '_SMALL', False)
+    monkeypatch.setattr(ops, '_RING2', False)
+    _general_schedule(32 if DEV == 'cuda' else 4, 3, schedule=FANOUT_SCHEDULE + [(0, ('cell', 0), ('ext', 2))], outputs=FANOUT_OUTPUTS + [9])
 
 
 @pytest.mark.parametrize('small', [False, True], ids=['wide', 'small'])
