@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define STC_ABI_VERSION 37
+#define STC_ABI_VERSION 38
 #define STC_MAX_K 4          /* highest Chebyshev order (Ks, Kc) the node kernels accept */
 
 /* Operand formats of the split-operand matrix-core kernels (C = 32 / 64, hidden 16).  Every fp32 operand is split into low-precision
@@ -725,6 +725,12 @@ int stc_graph_grad_f32(const float* A, const float* B, double* partials, int32_t
                        int32_t batch, int32_t N, int32_t F, int64_t chunk_stride, void* stream);
 int stc_mix_grad_f32(const float* A, const float* B, double* partials, int32_t n_chunks, int32_t cell0, int32_t cell_step, int32_t n_sel,
                      int32_t batch, int32_t N, int32_t Fa, int32_t Fb, int64_t chunk_stride, void* stream);
+/* Which kernel stc_graph_grad_f32 launches, process-wide and atomic like stc_set_dispatch_level (ABI v38; tests, A/B runs): 0 = by rule (default:
+ * an N threshold), 1 = tile per wave (a wave per 16 x 16 output tile, operands from L2), 2 = blocked (a workgroup per 64 x 64 output block, operand
+ * rows through LDS once per block and plane).  Both forms take every shape of the entry point and write the same partials bit for bit on finite
+ * operands (the same fp32 product chain per plane and tile, the same float64 fold order), so the setting changes time only.  Other values:
+ * STC_EINVAL, setting unchanged. */
+int stc_set_graph_grad_form(int32_t form);
 
 /* Gradient of the category graph through ONE BDG_Dif for FEW categories (ABI v33; reference STC_GNN.py:38-42 through autograd), on the
  * exact-fp32 matrix cores:  dTc[c][p][d] = sum_r sum_o U_c[r][p][o] * dY[r][d][o],  U_c[r] = sum_n Z_n[r] . W[(n, c, :), :]  (r: nodes).

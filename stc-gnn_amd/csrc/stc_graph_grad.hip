@@ -94,6 +94,136 @@ __global__ __launch_bounds__(GG_THREADS) void graph_grad_kernel(const float* __r
         }
 }
 
+// The same product for LARGER N, blocked: a workgroup (4 waves) owns 64 x 64 of the output = 4 x 4 tiles, a wave 2 x 2 of them, and the 64 A rows
+// and 64 B rows of every plane go through LDS in pieces of GB_KC columns, double-buffered (the next piece is in registers while this one is
+// multiplied; one barrier per piece): every operand row piece leaves L2 once per workgroup and plane and feeds four tiles -- tile per wave
+// above fetches both row strips of a plane once per TILE, T = N / 16 times over (13 x at N = 196).
+// Same bits as graph_grad_kernel on finite operands: per plane and tile an fp32 accumulator from zero takes the same chain of products (kb
+// ascending, s = 0..3, lane quarter kq supplying column 16 kb + 4 kq + s; a quad past F supplies zeros), is folded into the tile's float64
+// running sum once per plane, and the planes come in the order g = chunk, chunk + chunks, ...
+// LDS rows: GB_KC floats + TWO 16-byte slots.  A ds_read_b128 is served in four groups of 16 lanes ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}
+// and the same + 32), i.e. of an operand fragment (lane = 16 kq + j: row j, slot kq) the rows {0-3, 12-15} at slot kq with the rows 4-11 at
+// slot kq + 1: with a row stride of 10 slots these are the 16 distinct slots of a bank row (10 j mod 16 takes the even values once on either
+// row set); a stride of 9 slots (one slot of padding) collides two ways on ten of them.  2 x 128 rows x 160 B = 40 KiB: three workgroups per CU.
+constexpr int GB_THREADS = 256, GB_EDGE = 64, GB_KC = 32, GB_LD = GB_KC + 8, GB_ROWS = 2 * GB_EDGE, GB_PASSES = GB_ROWS * (GB_KC / 4) / GB_THREADS;
+static_assert(GB_PASSES * GB_THREADS == GB_ROWS * (GB_KC / 4) && GB_PASSES % 2 == 0 && GB_KC % 16 == 0, "staging: whole passes, A rows then B rows");
+
+__global__ __launch_bounds__(GB_THREADS) void graph_grad_blocked_kernel(const float* __restrict__ A, const float* __restrict__ B, double* __restrict__ part, Sel sel,
+                                                                        int N, int F, long long chunk_stride) {
+    __shared__ __attribute__((aligned(16))) float stage[2][GB_ROWS * GB_LD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, kq = lane >> 4;
+    const int NB = (N + GB_EDGE - 1) / GB_EDGE, bi = blockIdx.y / NB, bj = blockIdx.y - bi * NB, G = sel.n_sel * sel.batch;
+    const int ti0 = 2 * (wave >> 1), tj0 = 2 * (wave & 1);          // the wave's 2 x 2 tiles inside the block
+    bool live_i[2], live_j[2];                                      // (wave-uniform) a tile wholly past N is neither formed nor stored
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        live_i[u] = GB_EDGE * bi + 16 * (ti0 + u) < N;
+        live_j[u] = GB_EDGE * bj + 16 * (tj0 + u) < N;
+    }
+    // staging: thread -> column quad sq of the rows sr + 32 p; staged rows 0..63 are the block's A rows, 64..127 its B rows.  Rows past N
+    // are staged from row N - 1: they only reach outputs that are not stored
+    const int sq = threadIdx.x % (GB_KC / 4), sr = threadIdx.x / (GB_KC / 4);
+    constexpr int ROWS_PER_PASS = GB_THREADS / (GB_KC / 4);
+    size_t row_off[GB_PASSES];
+#pragma unroll
+    for (int p = 0; p < GB_PASSES; ++p) {
+        const int r = sr + ROWS_PER_PASS * p;
+        row_off[p] = (size_t)min(r < GB_EDGE ? GB_EDGE * bi + r : GB_EDGE * bj + r - GB_EDGE, N - 1) * F;
+    }
+    const int pieces = (F + GB_KC - 1) / GB_KC;
+    const int planes = (int)blockIdx.x < G ? (G - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
+    f32x4 held[GB_PASSES];
+    auto fetch = [&](int g, int piece) {                            // one piece of one plane: global -> registers (column quads past F: zeros)
+        const size_t plane = plane_of(sel, g) * N * F;
+        const int col = GB_KC * piece + 4 * sq;
+#pragma unroll
+        for (int p = 0; p < GB_PASSES; ++p)
+            held[p] = col < F ? *reinterpret_cast<const f32x4*>((p < GB_PASSES / 2 ? A : B) + plane + row_off[p] + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+    };
+    auto stash = [&](int buf) {                                     // registers -> LDS
+#pragma unroll
+        for (int p = 0; p < GB_PASSES; ++p) *reinterpret_cast<f32x4*>(&stage[buf][(sr + ROWS_PER_PASS * p) * GB_LD + 4 * sq]) = held[p];
+    };
+    double sum[2][2][4];
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            acc[u][v] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sum[u][v][r] = 0.0;
+        }
+    if (planes) {
+        fetch(blockIdx.x, 0);
+        stash(0);
+    }
+    __syncthreads();
+    int g = blockIdx.x, piece = 0;
+    for (int step = 0, steps = planes * pieces; step < steps; ++step) {
+        const int buf = step & 1;
+        int g_next = g, piece_next = piece + 1;
+        if (piece_next == pieces) {
+            piece_next = 0;
+            g_next = g + gridDim.x;
+        }
+        const bool more = step + 1 < steps;
+        if (more) fetch(g_next, piece_next);                        // in flight across this piece's products
+        const float* a_rows = &stage[buf][(16 * ti0 + j) * GB_LD + 4 * kq];
+        const float* b_rows = &stage[buf][(GB_EDGE + 16 * tj0 + j) * GB_LD + 4 * kq];
+#pragma unroll
+        for (int kbl = 0; kbl < GB_KC / 16; ++kbl) {
+            if (GB_KC * piece + 16 * kbl >= F) break;               // (the steps of graph_grad_kernel: kb < ceil(F / 16), no more)
+            f32x4 a[2], b[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                a[u] = *reinterpret_cast<const f32x4*>(a_rows + 16 * u * GB_LD + 16 * kbl);
+                b[u] = *reinterpret_cast<const f32x4*>(b_rows + 16 * u * GB_LD + 16 * kbl);
+            }
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+#pragma unroll
+                    for (int v = 0; v < 2; ++v)
+                        if (live_i[u] && live_j[v]) acc[u][v] = mfma4(a[u][s], b[v][s], acc[u][v]);
+        }
+        if (piece_next == 0) {                                      // the plane is complete: fold it
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int v = 0; v < 2; ++v) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sum[u][v][r] += (double)acc[u][v][r];
+                    acc[u][v] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+        }
+        if (more) stash(buf ^ 1);                                   // (its last readers passed the barrier that ended the previous step)
+        __syncthreads();
+        g = g_next;
+        piece = piece_next;
+    }
+    double* out = part + (size_t)blockIdx.x * chunk_stride;         // (a chunk without a plane writes its zeros)
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int v = 0; v < 2; ++v)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int n = GB_EDGE * bi + 16 * (ti0 + u) + 4 * kq + r, m = GB_EDGE * bj + 16 * (tj0 + v) + j;
+                if (n < N && m < N) out[(size_t)n * N + m] = sum[u][v][r];
+            }
+}
+
+// Which kernel stc_graph_grad_f32 launches (stc_set_graph_grad_form): 0 = by rule, 1 = tile per wave, 2 = blocked.  The two agree bit for bit,
+// so the rule is a matter of time alone: blocked from GG_BLOCKED_MIN_N nodes on (measured: profiles/r10/INDEX.md).
+std::atomic<int> g_graph_grad_form{0};
+constexpr int GG_BLOCKED_MIN_N = 64;
+bool graph_grad_blocked(int N) {
+    const int form = g_graph_grad_form.load(std::memory_order_relaxed);
+    return form == 2 || (form == 0 && N >= GG_BLOCKED_MIN_N);
+}
+
 __global__ __launch_bounds__(GG_THREADS) void mix_grad_kernel(const float* __restrict__ A, const float* __restrict__ B, double* __restrict__ part, Sel sel, int N,
                                                               int Fa, int Fb, long long chunk_stride) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, kq = lane >> 4;
@@ -173,10 +303,23 @@ extern "C" int stc_graph_grad_f32(const float* A, const float* B, double* partia
     STC_REQUIRE(N >= 1 && N <= 4096 && F >= 4 && F % 4 == 0, STC_EINVAL, "stc_graph_grad_f32: N=%d (1..4096), F=%d (a multiple of 4)", N, F);
     STC_REQUIRE(A && B && partials && stc::aligned16(A) && stc::aligned16(B), STC_EINVAL, "stc_graph_grad_f32: null or unaligned operand");
     STC_REQUIRE(chunk_stride == 0 || chunk_stride >= (int64_t)N * N, STC_EINVAL, "stc_graph_grad_f32: chunk stride %lld below the block of %d x %d", (long long)chunk_stride, N, N);
-    const int T = (N + 15) / 16, groups = (T * T + GG_NT_TPW * GG_WAVES - 1) / (GG_NT_TPW * GG_WAVES);
-    hipLaunchKernelGGL(graph_grad_kernel, dim3((unsigned)n_chunks, (unsigned)groups), dim3(GG_THREADS), 0, static_cast<hipStream_t>(stream), A, B, partials,
-                       Sel{cell0, cell_step, n_sel, batch}, N, F, (long long)(chunk_stride ? chunk_stride : (int64_t)N * N));
+    const long long stride = chunk_stride ? chunk_stride : (int64_t)N * N;
+    if (graph_grad_blocked(N)) {
+        const int NB = (N + GB_EDGE - 1) / GB_EDGE;
+        hipLaunchKernelGGL(graph_grad_blocked_kernel, dim3((unsigned)n_chunks, (unsigned)(NB * NB)), dim3(GB_THREADS), 0, static_cast<hipStream_t>(stream), A, B,
+                           partials, Sel{cell0, cell_step, n_sel, batch}, N, F, stride);
+    } else {
+        const int T = (N + 15) / 16, groups = (T * T + GG_NT_TPW * GG_WAVES - 1) / (GG_NT_TPW * GG_WAVES);
+        hipLaunchKernelGGL(graph_grad_kernel, dim3((unsigned)n_chunks, (unsigned)groups), dim3(GG_THREADS), 0, static_cast<hipStream_t>(stream), A, B, partials,
+                           Sel{cell0, cell_step, n_sel, batch}, N, F, stride);
+    }
     STC_LAUNCH_CHECK("stc_graph_grad_f32 launch");
+    return STC_OK;
+}
+
+extern "C" int stc_set_graph_grad_form(int32_t form) {
+    STC_REQUIRE(form >= 0 && form <= 2, STC_EINVAL, "stc_set_graph_grad_form: form %d (0 = by rule, 1 = tile per wave, 2 = blocked)", form);
+    g_graph_grad_form.store(form, std::memory_order_relaxed);
     return STC_OK;
 }
 

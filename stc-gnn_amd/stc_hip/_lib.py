@@ -22,7 +22,7 @@ from .graph import is_full_pattern
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, 'libstc_hip.so')
 # Mirrors of include/stc_hip.h (#define STC_<name>; tests/test_abi.py compares each, and HipKernels.ACT_AMAX_SLOTS, with the header)
-ABI_VERSION = 37
+ABI_VERSION = 38
 FMT_BF16X3, FMT_F16X2 = 0, 1          # operand formats of the split-operand matrix-core kernels
 MAX_K = 4
 STC_ELIMIT = -3            # include/stc_hip.h: a size beyond a kernel limit
@@ -117,6 +117,7 @@ _ABI = {
     'stc_cell_small_bwd_f32': (_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _i32, _p, _p, _i32, _i32] + [_p] * 12
                                + [_i32, _p, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _size, _i32, _i32, _i32, _i32, _p]),
     'stc_graph_grad_f32': (_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _p]),
+    'stc_set_graph_grad_form': (_int, [_i32]),
     'stc_mix_grad_f32': (_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _p]),
     'stc_mixed_fusion_workspace_bytes': (_size, [_i32, _i32]),
     'stc_mixed_fusion_fwd_f32': (_int, [_p] * 8 + [_i32, _p]),
@@ -294,6 +295,13 @@ class HipKernels:
         rc = self.lib.stc_set_dispatch_level(int(level))
         if rc != 0:
             self._failed(f'stc_set_dispatch_level({level})', rc)
+
+    def set_graph_grad_form(self, form: int):
+        """0 = by rule (default: the node count), 1 = tile per wave, 2 = blocked: which kernel ``graph_grad`` launches, process-wide
+        (stc_set_graph_grad_form), for tests and A/B runs -- both write the same partials bit for bit."""
+        rc = self.lib.stc_set_graph_grad_form(int(form))
+        if rc != 0:
+            self._failed(f'stc_set_graph_grad_form({form})', rc)
 
     def _failed(self, what, rc):
         msg = self.lib.stc_last_error()
@@ -1016,6 +1024,11 @@ class HipKernels:
     #: Chebyshev order 3 with a learned dense graph on these kernels (``graph2`` = T_2(S) as a dense matrix; split form only).  A kernel set
     #: without the attribute keeps that combination on the general path (``small.small_graph_supported``).
     small_dense_order3 = True
+    #: Dense graphs (learned, or evaluated with grad mode off) on samples of more than ``SMALL_STAGED_ROWS`` rows, up to ``SMALL_DENSE_ROWS``: the
+    #: split launches aggregate from global memory (never phase 0: ``_small_head``) and the graph gradient runs blocked (``set_graph_grad_form``).
+    #: A kernel set without the attribute keeps such graphs on the general path (``small.small_graph_supported``).
+    small_dense_split = True
+    SMALL_DENSE_ROWS = 1568      # the largest sample MEASURED to win on this route (profiles/r10/INDEX.md): never extrapolated
     #: ``cell_small_fwd`` takes ``R=None`` / ``Cand=None`` (ABI v36): planes that only ``cell_small_bwd`` reads, not stored when absent.  A kernel set
     #: without the attribute gets scratch planes from the forward-only executor (``small._forward_only``).
     small_optional_stores = True
@@ -1086,7 +1099,9 @@ class HipKernels:
         (B, N, Cc, _), cin, Kc = H.shape, X.shape[-1], Tc.shape[0]
         dense = int(is_full_pattern(colidx, N, N))
         g2, p2 = self._small_order3(what, Tc, graph2, (Zg2, Zc2), Zg, Zc, dense, N)
-        phases = (0,) if splits == 1 and not (dense and Kc == 3) else split_phases
+        # a dense graph at order 3, or on a sample too large to stage, has no whole-cell launch worth taking (there phase 0 gathers the full
+        # pattern as a CSR, ~100 us per phase): the split launches, with ``splits`` = 1 too
+        phases = (0,) if splits == 1 and not (dense and (Kc == 3 or N * Cc > self.SMALL_STAGED_ROWS)) else split_phases
         head = (rowptr.data_ptr(), colidx.data_ptr(), val.data_ptr(), N, val.numel(), dense, *g2, X.data_ptr(), cin, H.data_ptr(), Tc.data_ptr(), Kc, Kc)
         return (B, N, Cc, cin, Kc), phases, head, p2
 
@@ -1190,6 +1205,19 @@ class HipKernels:
             raise StcError(f'{what}: into = (contiguous float64 (chunks, total) ROCm buffer, column offset); block of {size} at {offset} in {tuple(part.shape)}')
         return part, part.data_ptr() + 8 * offset, part.shape[0], part.shape[1]
 
+    GRAPH_GRAD_WAVES_OF_BLOCKS = 6       # workgroups per compute unit that the chunks of a large graph-gradient product are sized for (its LDS holds three)
+
+    def graph_grad_chunks(self, planes, N, rows, device=None) -> int:
+        """Float64 partials of a ``graph_grad`` product over ``planes`` planes of ``rows`` = N * C rows.  Up to ``SMALL_STAGED_ROWS`` rows: one
+        workgroup per ~2 planes of the N x N block, at most 256 (the fold order of every run so far).  Above: chunks x 64 x 64 output blocks =
+        ``GRAPH_GRAD_WAVES_OF_BLOCKS`` workgroups per compute unit -- the partial buffer, written and re-read once, grows with N^2 per chunk
+        (256 chunks at N = 300: 184 MB per product)."""
+        if rows <= self.SMALL_STAGED_ROWS:
+            return max(1, min(256, planes))
+        blocks = ((N + 63) // 64) ** 2
+        cus = torch.cuda.get_device_properties(device).multi_processor_count
+        return max(1, min(256, planes, -(-self.GRAPH_GRAD_WAVES_OF_BLOCKS * cus // blocks)))
+
     def graph_grad(self, A, Bm, cell0, cell_step, n_sel, N, into=None):
         """(N, N) float64:  sum over the selected cells and samples of  A_g . B_g^T  with A, B (cells, batch, N*C, width) read as (N, C*width)
         per plane -- the dGs^T piece of a learned dense graph (``stc_graph_grad_f32``).  ``into`` = (partial buffer, column offset): the
@@ -1202,7 +1230,7 @@ class HipKernels:
             self._same_device(A, part)
             self._launch('stc_graph_grad_f32', A, A.data_ptr(), Bm.data_ptr(), ptr, chunks, cell0, cell_step, n_sel, batch, N, Cc * A.shape[3], stride)
             return None
-        chunks = max(1, min(256, n_sel * batch))          # (an N x N float64 partial is small: one workgroup per ~2 planes)
+        chunks = self.graph_grad_chunks(n_sel * batch, N, A.shape[2], A.device)
         part = torch.empty(chunks, N, N, dtype=torch.float64, device=A.device)
         self._launch('stc_graph_grad_f32', A, A.data_ptr(), Bm.data_ptr(), part.data_ptr(), chunks, cell0, cell_step, n_sel, batch, N, Cc * A.shape[3], 0)
         return part.sum(0)

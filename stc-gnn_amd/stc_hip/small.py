@@ -41,15 +41,22 @@ def small_graph_supported(k, op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_
     ``graph.dense_operand`` builds it) -- its gradient is formed as a dense product."""
     if dtype != torch.float32 or not hasattr(k, 'cell_small_supported') or (op.fwd_val.requires_grad and op.nnz != op.n * op.n):
         return False
+    full = op.nnz == op.n * op.n
+    # the graph as the learned mode hands it over: full pattern, requiring grad -- or, with grad mode off (evaluation: the generator's Gs does
+    # not require grad there), the same graph as it arrives then
+    as_learned = full and (op.fwd_val.requires_grad or (not torch.is_grad_enabled() and op.source is None))
+    # rows per sample that a dense graph may have: what the LDS stages -- or, where the kernel set runs the split launches on global memory and
+    # the blocked graph gradient (``small_dense_split``), its measured bound
+    dense_rows = max(k.SMALL_STAGED_ROWS, k.SMALL_DENSE_ROWS) if as_learned and getattr(k, 'small_dense_split', False) else k.SMALL_STAGED_ROWS
     if Ks == 3:                                                     # order 3: T_2(S) as a second graph --
-        # a learned full-pattern graph (T_2 dense, split launches) where the kernel set takes one; with grad mode off (evaluation: the generator's
-        # Gs does not require grad there) the same graph as it arrives then -- in grad mode a dense graph that needs no gradient keeps the general path
-        if op.fwd_val.requires_grad or (not torch.is_grad_enabled() and op.source is None and op.nnz == op.n * op.n):
-            if not getattr(k, 'small_dense_order3', False) or op.n * C > k.SMALL_STAGED_ROWS:
+        # a learned full-pattern graph (T_2 dense, split launches) where the kernel set takes one; with grad mode off the same graph as it
+        # arrives then -- in grad mode a dense graph that needs no gradient keeps the general path
+        if op.fwd_val.requires_grad or (not torch.is_grad_enabled() and op.source is None and full):
+            if not getattr(k, 'small_dense_order3', False) or op.n * C > dense_rows:
                 return False
-        elif op.source is None or op.nnz == op.n * op.n:            # else fixed sparse graphs (CsrGraph.second_order)
+        elif op.source is None or full:                             # else fixed sparse graphs (CsrGraph.second_order)
             return False
-    if op.nnz == op.n * op.n and op.n * C > k.SMALL_STAGED_ROWS:
+    if full and op.n * C > dense_rows:
         return False                                                # a dense graph aggregates as a matrix product on the STAGED plane: the sample must fit the LDS
     if op.n * C > k.SMALL_PREFERRED_ROWS or (C == 16 and op.n * C > 4096):
         return False                                                # (16 categories on large graphs: the general path's fp32-MFMA node kernels win, 13.4 vs 18.3 ms)
@@ -374,7 +381,10 @@ def _graph_gradients(bufs, k, Tc, stacks, schedule, cin, pos, need_Tc, need_val,
         kinds = int(bool(need_val)) + int(bool(need_t2))
         both = torch.zeros(kinds, N, N, dtype=torch.float64, device=Tc.device)
         if graph_jobs:
-            gpart = k.grad_partials(Tc, len(graph_jobs) * N * N, chunks=max(1, min(256, min(n for _, _, n in graph_jobs) * B)))
+            planes = min(n for _, _, n in graph_jobs) * B
+            # (a kernel set without the rule: the one that every sample of up to SMALL_STAGED_ROWS rows keeps)
+            chunks = k.graph_grad_chunks(planes, N, N * C, Tc.device) if hasattr(k, 'graph_grad_chunks') else max(1, min(256, planes))
+            gpart = k.grad_partials(Tc, len(graph_jobs) * N * N, chunks=chunks)
             for i, (A, Bm, n_sel) in enumerate(graph_jobs):
                 k.graph_grad(A, Bm, 0, 1, n_sel, N, into=(gpart, i * N * N))
             both = gpart.view(-1, kinds, len(graph_jobs) // kinds, N, N).sum((0, 2))       # ONE sum for the partials of both gradients
