@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define STC_ABI_VERSION 38
+#define STC_ABI_VERSION 39
 #define STC_MAX_K 4          /* highest Chebyshev order (Ks, Kc) the node kernels accept */
 
 /* Operand formats of the split-operand matrix-core kernels (C = 32 / 64, hidden 16).  Every fp32 operand is split into low-precision
@@ -785,6 +785,38 @@ int stc_mgp_softmax_bwd_f32(const float* P, const float* Ps, const float* dPs, f
  * n a multiple of 4, all tensors 16-byte aligned and distinct.  The hyper-parameters come as doubles: 1 - beta is formed in double, as torch forms it. */
 int stc_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, const float* step, double lr, double beta1, double beta2, double eps,
                  double weight_decay, void* stream);
+
+/* ComboLoss of the reference trainer (ABI v39; Model_Trainer.py:9-23 through nn.BCELoss: mean binary cross-entropy + per-sample Dice loss,
+ * averaged over the batch), forward and backward, fp32, without a copy of the prediction.
+ * Operands: p (prediction) and y (target) are (batch, segments, seg): sample b is `segments` contiguous runs of `seg` floats, run (b, s)
+ * starting at element b sb + s ss of its tensor (p and y have their own strides, >= 0; runs must not overlap).  A contiguous
+ * (B, horizon, N, C) tensor is segments = horizon, seg = N C; a contiguous (B, n) one segments = 1; the model's transposed view of a
+ * (horizon, B, N, C) tensor segments = horizon, sb = N C, ss = B N C.  M = batch segments seg.
+ *   stc_combo_loss_fwd_f32   two launches.  Partials: one workgroup per chunk of STC_LOSS_CHUNK elements of one run (a run's last chunk is
+ *                            ragged) sums the BCE terms -(y max(log p, -100) + (1 - y) max(log(1 - p), -100)), p y and p + y: fp32 per
+ *                            thread, float64 from the wave up, 3 doubles per (b, s, chunk) into the workspace; no atomics.  Finish: one
+ *                            workgroup folds them in a fixed order, per sample over (s, chunk), then over samples:
+ *                                sums[b] = (I_b, D_b) = (sum p y, sum (p + y)), float64, (batch, 2);
+ *                                *loss = (sum bce) / M + (1 / batch) sum_b (1 - 2 I_b / D_b), one fp32.
+ *                            The result is bitwise reproducible from run to run and between eager launches and HIP-graph replays.
+ *   stc_combo_loss_bwd_f32   one launch:  dp = g [ (p - y) / max(p (1 - p), 1e-12) / M  -  (2 / batch) (y D_b - I_b) / D_b^2 ],  g = *grad_out (a
+ *                            DEVICE float: no host sync, capturable), dp written at p's strides; dp must not alias p or y.
+ * 16-byte accesses when the base pointers are 16-byte aligned and seg and all four strides are multiples of 4, a scalar path of the same
+ * kernels otherwise (p, y, dp, loss, grad_out 4-byte aligned; sums and workspace 8-byte aligned).  workspace: at least
+ * stc_combo_loss_workspace_bytes(batch, segments, seg) = 8 (3 batch segments ceil(seg / STC_LOSS_CHUNK) + batch) bytes (0 for sizes the entry
+ * points refuse and for zero-size shapes, which launch nothing); the chunk count batch segments ceil(seg / STC_LOSS_CHUNK) must be below 2^31 (STC_ELIMIT).
+ * Non-finite values: both clamps hand a NaN on, and there are no device asserts (nn.BCELoss refuses what follows; here it reaches the loss):
+ * p that is NaN, below 0, above 1 or +-Inf gives a NaN loss through the logarithms.  The finish adds 0 * (the sample's BCE sum) to I_b and
+ * D_b, so such a sample's sums are NaN and its WHOLE dp is NaN; the other samples' sums and dp are what they are on clean operands (the loss
+ * is the only value shared across samples).  D_b = 0 gives NaN, as the reference does.  p = 0 with y = 1: the term is 100 and dp is finite. */
+#define STC_LOSS_CHUNK 4096
+size_t stc_combo_loss_workspace_bytes(int64_t batch, int64_t segments, int64_t seg);
+int stc_combo_loss_fwd_f32(const float* p, const float* y, int64_t batch, int64_t segments, int64_t seg,
+                           int64_t p_sb, int64_t p_ss, int64_t y_sb, int64_t y_ss,
+                           float* loss, double* sums, void* workspace, size_t workspace_bytes, void* stream);
+int stc_combo_loss_bwd_f32(const float* p, const float* y, const double* sums, const float* grad_out, float* dp,
+                           int64_t batch, int64_t segments, int64_t seg,
+                           int64_t p_sb, int64_t p_ss, int64_t y_sb, int64_t y_ss, void* stream);
 
 
 /* ---- small helpers ---------------------------------------------------------

@@ -22,13 +22,14 @@ from .graph import is_full_pattern
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, 'libstc_hip.so')
 # Mirrors of include/stc_hip.h (#define STC_<name>; tests/test_abi.py compares each, and HipKernels.ACT_AMAX_SLOTS, with the header)
-ABI_VERSION = 38
+ABI_VERSION = 39
 FMT_BF16X3, FMT_F16X2 = 0, 1          # operand formats of the split-operand matrix-core kernels
 MAX_K = 4
 STC_ELIMIT = -3            # include/stc_hip.h: a size beyond a kernel limit
 SPMM_SUM_MAX_ADD, SPMM_SUM_BF16_MAX_ADD, RING2_MAX_ADD = 8, 5, 5      # addends of stc_spmm_sum_f32 / _bf16 and of the two-ring launches
 PATCH_ROWS, PATCH_MAX_SRC = 32, 64
 RING2_INTERIOR, RING2_FIRST, RING2_SECOND, RING2_WIDTH = 32, 64, 96, 8     # rows of a two-ring patch and of its rings, entries per row
+LOSS_CHUNK = 4096          # STC_LOSS_CHUNK: elements of one run per workgroup of the ComboLoss kernels
 
 
 class StcError(RuntimeError):
@@ -127,6 +128,10 @@ _ABI = {
     'stc_mgp_softmax_fwd_f32': (_int, [_p, _p, _i32, _p]),
     'stc_mgp_softmax_bwd_f32': (_int, [_p, _p, _p, _p, _p, _i32, _p]),
     'stc_adam_f32': (_int, [_p] * 4 + [_i64, _p] + [C.c_double] * 5 + [_p]),
+    # ---- ComboLoss
+    'stc_combo_loss_workspace_bytes': (_size, [_i64, _i64, _i64]),
+    'stc_combo_loss_fwd_f32': (_int, [_p, _p] + [_i64] * 7 + [_p, _p, _p, _size, _p]),
+    'stc_combo_loss_bwd_f32': (_int, [_p] * 5 + [_i64] * 7 + [_p]),
     # ---- GRU gate math, output head, helpers
     'stc_gru_gates_fwd_f32': (_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p]),
     'stc_gru_gates_bwd_f32': (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p]),
@@ -1344,6 +1349,58 @@ class HipKernels:
         self._same_device(p, g, m, v, step)
         self._launch('stc_adam_f32', p, _ptr(p), _ptr(g), _ptr(m), _ptr(v), n, _ptr(step), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
                      nbytes=28 * n)
+
+    # ---- ComboLoss (reference Model_Trainer.py:9-23) -----------------------------------------------------------
+    #: the fused loss exists (ABI v39): what ``stc_hip.loss.combo_loss_supported`` asks before it routes ``ComboLoss`` here (the CPU twin has
+    #: no such attribute and keeps the torch path)
+    combo_loss = True
+
+    @staticmethod
+    def _loss_view(name, t, like=None):
+        """The host-side check of a (batch, segments, seg) operand of the loss kernels: a float32 ROCm tensor whose last dimension is
+        contiguous, strides >= 0; the other two strides are the caller's (``stc_hip.loss._as3`` builds such views without a copy)."""
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise StcError(f'{name}: expected a ROCm (cuda) tensor, got {type(t).__name__}'
+                           f'{"" if not isinstance(t, torch.Tensor) else " on " + str(t.device)}; no CPU fallback')
+        if t.dtype != torch.float32:
+            raise StcError(f'{name}: expected {torch.float32}, got {t.dtype}')
+        if t.dim() != 3 or (t.shape[2] > 1 and t.stride(2) != 1) or min(t.stride()) < 0:
+            raise StcError(f'{name}: a (batch, segments, seg) view with a contiguous last dimension expected, got shape {tuple(t.shape)}, strides {t.stride()}')
+        if like is not None and tuple(t.shape) != tuple(like.shape):
+            raise StcError(f'{name}: shape {tuple(t.shape)}, expected {tuple(like.shape)}')
+        return t
+
+    def combo_loss_fwd(self, p3, y3, loss, sums):
+        """loss (one float32) = mean BCE + mean per-sample Dice of the prediction ``p3`` against ``y3``, both (batch, segments, seg) strided
+        views, and sums (batch, 2) float64 = (sum p y, sum (p + y)) per sample for the backward (``stc_combo_loss_fwd_f32``: two launches)."""
+        self._loss_view('combo_loss.p', p3)
+        self._loss_view('combo_loss.y', y3, p3)
+        batch, segments, seg = p3.shape
+        _tensor('combo_loss.loss', loss)
+        if loss.numel() != 1:
+            raise StcError(f'combo_loss.loss: one element, got {tuple(loss.shape)}')
+        _tensor('combo_loss.sums', sums, (batch, 2), torch.float64)
+        self._same_device(p3, y3, loss, sums)
+        ws = self._get_workspace(p3.device, self.lib.stc_combo_loss_workspace_bytes(batch, segments, seg))
+        self._launch('stc_combo_loss_fwd_f32', p3, _ptr(p3), _ptr(y3), batch, segments, seg, p3.stride(0), p3.stride(1), y3.stride(0), y3.stride(1),
+                     _ptr(loss), _ptr(sums), _ptr(ws), ws.numel(), nbytes=8 * p3.numel())
+
+    def combo_loss_bwd(self, p3, y3, sums, grad_out, dp3):
+        """dp3 (p3's shape AND strides) from the loss's incoming gradient ``grad_out``, a one-element float32 device tensor, and the forward's
+        ``sums`` (``stc_combo_loss_bwd_f32``: one launch)."""
+        self._loss_view('combo_loss.p', p3)
+        self._loss_view('combo_loss.y', y3, p3)
+        self._loss_view('combo_loss.dp', dp3, p3)
+        batch, segments, seg = p3.shape
+        if any(n > 1 and a != b for n, a, b in zip(p3.shape, p3.stride(), dp3.stride())):
+            raise StcError(f'combo_loss.dp: strides {dp3.stride()}, expected those of the prediction {p3.stride()}')
+        _tensor('combo_loss.sums', sums, (batch, 2), torch.float64)
+        _tensor('combo_loss.grad_out', grad_out)
+        if grad_out.numel() != 1:
+            raise StcError(f'combo_loss.grad_out: one element, got {tuple(grad_out.shape)}')
+        self._same_device(p3, y3, sums, grad_out, dp3)
+        self._launch('stc_combo_loss_bwd_f32', p3, _ptr(p3), _ptr(y3), _ptr(sums), _ptr(grad_out), _ptr(dp3), batch, segments, seg,
+                     p3.stride(0), p3.stride(1), y3.stride(0), y3.stride(1), nbytes=12 * p3.numel())
 
     # ---- planar cell convolutions of Chebyshev order K = 3 ------------------------------------------------
     def cell_planar_k_supported(self, K, Cc, h) -> bool:
