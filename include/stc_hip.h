@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define STC_ABI_VERSION 39
+#define STC_ABI_VERSION 40
 #define STC_MAX_K 4          /* highest Chebyshev order (Ks, Kc) the node kernels accept */
 
 /* Operand formats of the split-operand matrix-core kernels (C = 32 / 64, hidden 16).  Every fp32 operand is split into low-precision
@@ -90,6 +90,9 @@ int stc_set_dispatch_level(int32_t level);
  *          launch holds it, so it reaches the rows with an entry in ANY row of that patch, and their patches.
  *        stc_dense_agg_f32, stc_cheby_dense_fwd/bwd_f32, stc_mgp_softmax_*, stc_mixed_fusion_*:  dense arithmetic -- want itself marks
  *          every row (of the sample) that the poisoned element's row or column enters; nothing beyond it.
+ *        stc_mixed_fusion_lr_fwd/bwd_f32:  no masking either; the result is non-finite wherever float64 torch operations on the same operands
+ *          are: a NaN in A reaches every entry of G through t_A, a NaN in one row of U_A only that row of gate and G; sigmoid(+-Inf) stays
+ *          1 / 0 [tests/test_mixed_fusion_lr.py test_non_finite_values_are_handed_on].
  *        node kernels (stc_bdg_node_*, stc_bdg_node_post_*), fused and planar cell kernels, all dispatch levels and both operand
  *          formats:  the node.  In the backward the pad columns [Lw, L) of THAT node's slab gradients come out non-finite where the
  *          math has zeros [test_contract_on_the_node_kernels, test_contract_on_the_fused_cell_kernels,
@@ -760,6 +763,38 @@ int stc_mixed_fusion_fwd_f32(const float* WA, const float* bA, const float* WP, 
 int stc_mixed_fusion_bwd_f32(const float* WA, const float* WP, const float* A, const float* P, const float* gate, const float* dG,
                              float* dWA, float* dWP, float* db, float* dP, float* dA,
                              void* workspace, size_t workspace_bytes, int32_t D, void* stream);
+/* Rank-r MixedFusion (ABI v40; STC_GNN.py FactorisedLinear: each Linear(D, D) above replaced by y = U (V^T x) + b).  U_A, V_A, U_P, V_P (D, r)
+ * row-major, b_A, b_P (D), a = vec(A), p = vec(P), D = n^2:
+ *     t_A = V_A^T a,  t_P = V_P^T p                                  (r each; t = t_A | t_P, 2r floats, kept for the backward)
+ *     gate = sigmoid(U_A t_A + b_A + U_P t_P + b_P),   G = gate * A + (1 - gate) * P
+ *   backward from dG:
+ *     db = dpre = dG (A - P) gate (1 - gate)                          (the gradient of both biases; always written)
+ *     dU_A = dpre (x) t_A,  dU_P = dpre (x) t_P
+ *     s_A = U_A^T dpre,  s_P = U_P^T dpre                             (r each)
+ *     dV_A = a (x) s_A,  dV_P = p (x) s_P
+ *     dA = dG gate + V_A s_A,   dP = dG (1 - gate) + V_P s_P
+ * dU_A, dV_A, dU_P, dV_P, dA and dP may each be NULL: not wanted -- not written, and not computed (s_A is formed for dV_A or dA only, s_P for
+ * dV_P or dP; with none of the four the second launch is left out).
+ *   stc_mixed_fusion_lr_fwd_f32   two launches: per chunk of STC_FUSION_LR_CHUNK rows the chunk's share of t (fp32 per thread, float64 from the
+ *                                 wave up, 2r doubles per chunk into the workspace, no atomics); then every workgroup folds the shares in one
+ *                                 fixed order and forms gate and G for its rows.
+ *   stc_mixed_fusion_lr_bwd_f32   at most two launches: dpre, db, the dU rows and the chunk's share of s, summed the same way; then the fold,
+ *                                 the dV rows, dA and dP.
+ * Bitwise reproducible from run to run and between eager launches and HIP-graph replays.  Accepted (stc_mixed_fusion_lr_supported): every
+ * D >= 1 (no D % 4 rule; STC_EINVAL below 1), 1 <= r <= 64 (STC_EUNSUPPORTED outside), D r < 2^31 (STC_ELIMIT).  r in {4, 8, 16, 32, 64}: r/4
+ * lanes hold a row as 16-byte pieces; other ranks take a plain form of the same kernels.  The four factors and their gradients 16-byte
+ * aligned, vectors 4-byte, the workspace 8-byte aligned and at least stc_mixed_fusion_lr_workspace_bytes(D, r) = 16 r ceil(D /
+ * STC_FUSION_LR_CHUNK) bytes (0 for shapes the entry points refuse).  No output may alias an input. */
+#define STC_FUSION_LR_CHUNK 512
+int stc_mixed_fusion_lr_supported(int32_t D, int32_t r);
+size_t stc_mixed_fusion_lr_workspace_bytes(int32_t D, int32_t r);
+int stc_mixed_fusion_lr_fwd_f32(const float* UA, const float* VA, const float* bA, const float* UP, const float* VP, const float* bP,
+                                const float* A, const float* P, float* gate, float* G, float* t,
+                                void* workspace, size_t workspace_bytes, int32_t D, int32_t r, void* stream);
+int stc_mixed_fusion_lr_bwd_f32(const float* UA, const float* VA, const float* UP, const float* VP, const float* A, const float* P,
+                                const float* gate, const float* t, const float* dG,
+                                float* dUA, float* dVA, float* dUP, float* dVP, float* db, float* dA, float* dP,
+                                void* workspace, size_t workspace_bytes, int32_t D, int32_t r, void* stream);
 /* ---- front end of the learned graph generator (ABI v31; reference STC_GNN.py:229-232 spatial branch, :237-240 category branch) -----------
  *   U = tanh(alpha X Wu), V = tanh(alpha X Wv);   P = sum_k U_k V_k^T (R x R);   Ps = softmax(relu(P - P^T), -1)        (the einsum pair of :231)
  * X is addressed as x[k][r][f] = X[k k_stride + r r_stride + f f_stride] (floats), k = 0..K-1 the (sample, time) slices, r the R rows, f the F

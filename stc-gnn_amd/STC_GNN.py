@@ -29,7 +29,7 @@ from typing import List, Optional, Sequence, Union
 import torch
 from torch import nn
 
-from stc_hip import ops
+from stc_hip import fusion, ops
 from stc_hip.graph import CsrGraph, SpatialOperand, csr_operand, dense_operand
 
 GraphLike = Union[torch.Tensor, CsrGraph, 'GraphPair']
@@ -236,7 +236,8 @@ class MixedFusion(nn.Module):
     Two ``Linear(n^2, n^2)`` layers: usable for small n only.  On the GPU (fp32, n^2 a multiple of 4) the gate's two matrix-vector
     products, the mix and their autograd are ``stc_mixed_fusion_fwd/bwd_f32`` -- the matrices are streamed once per direction; other
     shapes stay on torch.  ``rank`` (not in the reference) replaces the layers by rank-r factors so that a learned graph is affordable
-    beyond n ~ 300.
+    beyond n ~ 300; on the GPU (fp32, rank <= 64, any n) these run ``stc_mixed_fusion_lr_fwd/bwd_f32`` through ``stc_hip.fusion``, two
+    launches per direction; other cases stay on torch.
     """
 
     def __init__(self, in_dim: int, rank: Optional[int] = None):
@@ -256,6 +257,10 @@ class MixedFusion(nn.Module):
             params = (self.lin_A.weight, self.lin_A.bias, self.lin_P.weight, self.lin_P.bias)
             if ops.mixed_fusion_supported(A, P, *params):                # both 2 x n^4-byte matrices streamed once per direction
                 return ops.mixed_fusion(A, P, *params)
+        elif isinstance(self.lin_A, FactorisedLinear) and A.is_cuda:
+            params = (self.lin_A.U, self.lin_A.V, self.lin_A.bias, self.lin_P.U, self.lin_P.V, self.lin_P.bias)
+            if fusion.mixed_fusion_lr_supported(A, P, *params):          # two launches per direction (stc_mixed_fusion_lr_fwd/bwd_f32)
+                return fusion.mixed_fusion_lr(A, P, *params)
         gate = torch.sigmoid(self.lin_A(A.reshape(n * n)) + self.lin_P(P.reshape(n * n))).reshape(n, n)
         return gate * A + (1 - gate) * P
 

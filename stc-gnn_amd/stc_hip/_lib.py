@@ -22,7 +22,7 @@ from .graph import is_full_pattern
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, 'libstc_hip.so')
 # Mirrors of include/stc_hip.h (#define STC_<name>; tests/test_abi.py compares each, and HipKernels.ACT_AMAX_SLOTS, with the header)
-ABI_VERSION = 39
+ABI_VERSION = 40
 FMT_BF16X3, FMT_F16X2 = 0, 1          # operand formats of the split-operand matrix-core kernels
 MAX_K = 4
 STC_ELIMIT = -3            # include/stc_hip.h: a size beyond a kernel limit
@@ -30,6 +30,8 @@ SPMM_SUM_MAX_ADD, SPMM_SUM_BF16_MAX_ADD, RING2_MAX_ADD = 8, 5, 5      # addends 
 PATCH_ROWS, PATCH_MAX_SRC = 32, 64
 RING2_INTERIOR, RING2_FIRST, RING2_SECOND, RING2_WIDTH = 32, 64, 96, 8     # rows of a two-ring patch and of its rings, entries per row
 LOSS_CHUNK = 4096          # STC_LOSS_CHUNK: elements of one run per workgroup of the ComboLoss kernels
+FUSION_LR_CHUNK = 512      # STC_FUSION_LR_CHUNK: rows per partial-sum workgroup of the rank-r MixedFusion kernels
+FUSION_LR_MAX_RANK = 64    # the highest rank stc_mixed_fusion_lr_* accept
 
 
 class StcError(RuntimeError):
@@ -123,6 +125,10 @@ _ABI = {
     'stc_mixed_fusion_workspace_bytes': (_size, [_i32, _i32]),
     'stc_mixed_fusion_fwd_f32': (_int, [_p] * 8 + [_i32, _p]),
     'stc_mixed_fusion_bwd_f32': (_int, [_p] * 12 + [_size, _i32, _p]),
+    'stc_mixed_fusion_lr_supported': (_int, [_i32, _i32]),
+    'stc_mixed_fusion_lr_workspace_bytes': (_size, [_i32, _i32]),
+    'stc_mixed_fusion_lr_fwd_f32': (_int, [_p] * 12 + [_size, _i32, _i32, _p]),
+    'stc_mixed_fusion_lr_bwd_f32': (_int, [_p] * 17 + [_size, _i32, _i32, _p]),
     'stc_mgp_uv_fwd_f32': (_int, [_p, _i64, _i64, _i64, _p, _p, _f32, _p, _p, _i32, _i32, _i32, _i32, _p]),
     'stc_mgp_uv_bwd_f32': (_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _f32, _p, _i32, _i32, _i32, _i32, _p]),
     'stc_mgp_softmax_fwd_f32': (_int, [_p, _p, _i32, _p]),
@@ -1285,6 +1291,66 @@ class HipKernels:
         self._launch('stc_mixed_fusion_bwd_f32', A, _ptr(WA), _ptr(WP), _ptr(A), _ptr(P), _ptr(gate), _ptr(dG), _ptr(dWA), _ptr(dWP), _ptr(db), _ptr(dP), _ptr(dA),
                      _ptr(ws), ws.numel() * 4, D, nbytes=(4 + (8 if want_dW else 0) + (4 if want_dA else 0)) * D * D)
         return dWA, dWP, db, dP, dA
+
+    # ---- rank-r MixedFusion (STC_GNN.py FactorisedLinear; include/stc_hip.h stc_mixed_fusion_lr_*) ---------------------------
+    #: the rank-r kernels exist (ABI v40): what ``stc_hip.fusion.mixed_fusion_lr_supported`` asks before it routes ``MixedFusion(n, rank=r)``
+    #: here (the CPU twin has no such attribute and keeps the torch path)
+    mixed_fusion_lr = True
+
+    def mixed_fusion_lr_supported(self, D, r) -> bool:
+        return 0 < D < (1 << 31) and 0 < r < (1 << 31) and bool(self.lib.stc_mixed_fusion_lr_supported(D, r))
+
+    def mixed_fusion_lr_workspace_bytes(self, D, r) -> int:
+        return self.lib.stc_mixed_fusion_lr_workspace_bytes(D, r)
+
+    def _fusion_lr_operands(self, UA, VA, UP, VP, A, P):
+        """The checks both directions share; returns (D, r)."""
+        _tensor('mixed_fusion_lr.A', A)
+        D = A.numel()
+        _tensor('mixed_fusion_lr.P', P, tuple(A.shape))
+        _tensor('mixed_fusion_lr.UA', UA)
+        if UA.dim() != 2 or UA.shape[0] != D:
+            raise StcError(f'mixed_fusion_lr.UA: shape {tuple(UA.shape)}, expected ({D}, rank)')
+        r = UA.shape[1]
+        for name, t in (('VA', VA), ('UP', UP), ('VP', VP)):
+            _tensor('mixed_fusion_lr.' + name, t, (D, r))
+        if not self.mixed_fusion_lr_supported(D, r):
+            raise StcError(f'mixed_fusion_lr: D = {D}, rank {r} outside the kernels (D >= 1, 1 <= rank <= {FUSION_LR_MAX_RANK}, D rank < 2^31)')
+        return D, r
+
+    def mixed_fusion_lr_fwd(self, UA, VA, bA, UP, VP, bP, A, P):
+        """(gate, G, t): t = (V_A^T vec A | V_P^T vec P) (2r), gate = sigmoid(U_A t_A + b_A + U_P t_P + b_P), G = gate * A + (1 - gate) * P; A, P
+        (n, n), the factors (n^2, r) (``stc_mixed_fusion_lr_fwd_f32``: two launches)."""
+        D, r = self._fusion_lr_operands(UA, VA, UP, VP, A, P)
+        _tensor('mixed_fusion_lr.bA', bA, (D,))
+        _tensor('mixed_fusion_lr.bP', bP, (D,))
+        self._same_device(UA, VA, bA, UP, VP, bP, A, P)
+        gate, G = torch.empty_like(A), torch.empty_like(A)
+        t = torch.empty(2 * r, dtype=torch.float32, device=A.device)
+        ws = self._get_workspace(A.device, self.lib.stc_mixed_fusion_lr_workspace_bytes(D, r))
+        self._launch('stc_mixed_fusion_lr_fwd_f32', A, _ptr(UA), _ptr(VA), _ptr(bA), _ptr(UP), _ptr(VP), _ptr(bP), _ptr(A), _ptr(P), _ptr(gate), _ptr(G), _ptr(t),
+                     _ptr(ws), ws.numel(), D, r, nbytes=4 * (4 * D * r + 6 * D))
+        return gate, G, t
+
+    def mixed_fusion_lr_bwd(self, UA, VA, UP, VP, A, P, gate, t, dG, want):
+        """(dU_A, dV_A, dU_P, dV_P, db, dA, dP) from dG (``stc_mixed_fusion_lr_bwd_f32``: at most two launches); db is the gradient of both
+        biases and always formed.  ``want``: six flags, for dU_A, dV_A, dU_P, dV_P, dA, dP -- a gradient not wanted is neither allocated nor
+        written (None)."""
+        D, r = self._fusion_lr_operands(UA, VA, UP, VP, A, P)
+        for name, x in (('gate', gate), ('dG', dG)):
+            _tensor('mixed_fusion_lr.' + name, x, tuple(A.shape))
+        _tensor('mixed_fusion_lr.t', t, (2 * r,))
+        if len(want) != 6:
+            raise StcError(f'mixed_fusion_lr.want: six flags (dU_A, dV_A, dU_P, dV_P, dA, dP), got {len(want)}')
+        self._same_device(UA, VA, UP, VP, A, P, gate, t, dG)
+        dUA, dVA, dUP, dVP = (torch.empty_like(UA) if w else None for w in want[:4])
+        dA, dP = (torch.empty_like(A) if w else None for w in want[4:])
+        db = torch.empty(D, dtype=torch.float32, device=A.device)
+        ws = self._get_workspace(A.device, self.lib.stc_mixed_fusion_lr_workspace_bytes(D, r))
+        self._launch('stc_mixed_fusion_lr_bwd_f32', A, _ptr(UA), _ptr(VA), _ptr(UP), _ptr(VP), _ptr(A), _ptr(P), _ptr(gate), _ptr(t), _ptr(dG),
+                     _ptr(dUA), _ptr(dVA), _ptr(dUP), _ptr(dVP), _ptr(db), _ptr(dA), _ptr(dP), _ptr(ws), ws.numel(), D, r,
+                     nbytes=4 * ((2 + sum(map(bool, want[:4]))) * D * r + 6 * D))
+        return dUA, dVA, dUP, dVP, db, dA, dP
 
     # ---- front end of the learned graph generator (reference STC_GNN.py:229-232, 237-240) --------------------------
     @staticmethod

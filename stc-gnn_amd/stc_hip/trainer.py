@@ -53,11 +53,16 @@ class Trainer:
         import torch.distributed as tdist
         self.rank = tdist.get_rank() if tdist.is_available() and tdist.is_initialized() else 0
         self.world = tdist.get_world_size() if tdist.is_available() and tdist.is_initialized() else 1
+        # optional: rank-r factors in place of MixedFusion's two Linear(N^2, N^2) layers (2 N^4 parameters: beyond one GPU from N ~ 200)
+        fusion_rank = params.get('fusion_rank')
+        if fusion_rank is not None and graph_mode == 'csr-fixed':
+            raise ValueError("params['fusion_rank'] is for the learned graphs (graph_mode='dense-learned'); 'csr-fixed' has no MixedFusion")
         self.model = STCGNN(num_nodes=params['H'] * params['W'], num_categories=params['C'],
                             Ks=params['cheby_order'], Kc=params['cheby_order'], input_dim=1,
                             hidden_dim=params['hidden_dim'], num_layers=params['nn_layers'],
                             out_horizon=params['pred_len'], graph_mode=graph_mode,
-                            batch_sharded=self.world > 1 and graph_mode == 'dense-learned').to(dev)
+                            batch_sharded=self.world > 1 and graph_mode == 'dense-learned',
+                            fusion_rank=None if fusion_rank is None else int(fusion_rank)).to(dev)
         sdist.broadcast_parameters(self.model)                          # every replica starts from rank 0's draw
         self.criterion = ComboLoss()
         self.bucket = sdist.GradBucket(self.model.parameters())        # every .grad is a view into one flat buffer

@@ -31,17 +31,21 @@ ap.add_argument('--graph', action='store_true', help='capture the whole train st
 ap.add_argument('--fused-adam', action='store_true', help='torch.optim.Adam(fused=True): one multi-tensor kernel per step instead of ~10 passes')
 ap.add_argument('--infer', action='store_true', help='time the forward alone under torch.no_grad(): no loss, no optimizer')
 ap.add_argument('--profile', action='store_true', help='print the kernels of 3 steps by GPU time (torch.profiler)')
+ap.add_argument('--fusion-rank', type=int, default=None, help="dense-learned: MixedFusion(N, rank=R), rank-R factors in place of the two Linear(N^2, N^2) layers")
+ap.add_argument('--grid', type=int, nargs=2, metavar=('H', 'W'), default=[10, 10], help='the queen grid (default: the SF shape, 10 x 10)')
+ap.add_argument('--categories', type=int, default=5, help='incident categories C (default: the SF shape, 5)')
 a = ap.parse_args()
 dev = torch.device('cuda')
 torch.manual_seed(0)
-B, T, N, C, h, K, layers, hor = 32, 9, 100, 5, 16, a.order, 2, 3
-model = M.STCGNN(N, C, K, K, 1, h, layers, hor, graph_mode=a.mode).to(dev)
+(GH, GW), C = a.grid, a.categories
+B, T, N, h, K, layers, hor = 32, 9, GH * GW, 16, a.order, 2, 3
+model = M.STCGNN(N, C, K, K, 1, h, layers, hor, graph_mode=a.mode, **({} if a.fusion_rank is None else {'fusion_rank': a.fusion_rank})).to(dev)
 X = (torch.rand(B, T, N, C, device=dev) < 0.1635).float()
 Y = (torch.rand(B, hor, N, C, device=dev) < 0.1635).float()
 if a.mode == 'csr-fixed':
-    As = CsrGraph.queen_grid(10, 10, normalize=True, device=dev)
+    As = CsrGraph.queen_grid(GH, GW, normalize=True, device=dev)
 else:
-    As = CsrGraph.queen_grid(10, 10, normalize=False).to_dense().to(dev)
+    As = CsrGraph.queen_grid(GH, GW, normalize=False).to_dense().to(dev)
 Ac = torch.rand(C, C, device=dev)
 crit = ComboLoss()
 opt = None if a.infer else torch.optim.Adam(model.parameters(), lr=2e-3, weight_decay=1e-4, capturable=a.graph, **({'fused': True} if a.fused_adam else {}))
@@ -98,7 +102,7 @@ print(f'SF shape {a.mode}{" K=3" if K == 3 else ""}{" hipGraph" if a.graph else 
       + (f'peak {peak_bytes / 2 ** 20:.1f} MiB, checksum {result["checksum"]:.6f}, ' if a.infer else f'loss {result["loss"]:.4f}, ')
       + f'{sum(p.numel() for p in model.parameters())} parameters', flush=True)
 if a.json:
-    print(json.dumps(dict(shape='sf', mode=a.mode, order=K, batch=B, hip_graph=a.graph, fused_adam=a.fused_adam, steps=a.steps, ms_per_step=1e3 * dt,
+    print(json.dumps(dict(shape='sf', mode=a.mode, order=K, batch=B, **({} if a.fusion_rank is None else dict(fusion_rank=a.fusion_rank, grid=[GH, GW], categories=C)), hip_graph=a.graph, fused_adam=a.fused_adam, steps=a.steps, ms_per_step=1e3 * dt,
                           repeats_ms=[1e3 * t for t in times], spread_ms=1e3 * (max(times) - min(times)), samples_per_s=B / dt,
                           cells_on_small_graph_kernels=bool(small_calls), **result)), flush=True)
 if a.profile:

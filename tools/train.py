@@ -40,7 +40,11 @@ ap.add_argument('-synthetic', '--synthetic', type=int, nargs=4, metavar=('H', 'W
                 help='train on a Bernoulli(0.1635) incident series of T steps on an H x W queen grid with C categories instead of a city file')
 ap.add_argument('-stride', '--time_slice', type=int, default=None, help=argparse.SUPPRESS)
 ap.add_argument('-hipgraph', '--hip_graph', type=int, default=0, choices=[0, 1], help='replay the train step as a captured HIP graph (one rank; launch-bound shapes)')
+ap.add_argument('-rank', '--fusion_rank', type=int, default=None,
+                help="learned graphs: rank-r factors in place of MixedFusion's two Linear(N^2, N^2) layers (2 N^4 parameters: NYC and CHI do not fit one GPU without)")
 params = vars(ap.parse_args())
+if params['fusion_rank'] is None:
+    del params['fusion_rank']                                   # the key exists only when given: the CSV parameter line of a run without it is unchanged
 rank, world, local = sdist.init_from_env()                      # under torchrun: one rank per GPU, each on its own device
 if world > 1:
     params['device'] = f'cuda:{local}'
