@@ -812,7 +812,7 @@ int stc_mgp_uv_bwd_f32(const float* X, int64_t k_stride, int64_t r_stride, int64
                        const float* dU, const float* dV, float alpha, float* partials, int32_t K, int32_t R, int32_t F, int32_t h, void* stream);
 int stc_mgp_softmax_fwd_f32(const float* P, float* Ps, int32_t R, void* stream);
 int stc_mgp_softmax_bwd_f32(const float* P, const float* Ps, const float* dPs, float* rowdot, float* dP, int32_t R, void* stream);
-/* Adam on one large fp32 parameter (ABI v29; the optimizer of the reference's harness step, Model_Trainer.py:71-87: torch.optim.Adam with
+/* Adam on one large fp32 parameter (csrc/stc_adam.hip; ABI v29; the optimizer of the reference's harness step, Model_Trainer.py:71-87: torch.optim.Adam with
  * L2 weight decay, no amsgrad), one streaming launch: the two MixedFusion matrices above are 2 x 400 MB at the SF shape.
  *     g' = g + weight_decay p;   m = m + (1 - beta1)(g' - m);   v = beta2 v + (1 - beta2) g'^2
  *     p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)

@@ -28,7 +28,11 @@ inline int hip_status(hipError_t e, const char* what) {
     return (int)e;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// the end of a launch helper: the status of the launch just made
+inline int launched(const char* what) { return hip_status(hipGetLastError(), what); }
+
+inline bool aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }      // bytes: a power of two
+inline bool aligned16(const void* p) { return aligned(p, 16); }
 
 // MI355X: 256 CUs in 8 XCDs; workgroups are dealt round-robin to the XCDs.
 constexpr int kNumXcd = 8;
@@ -133,7 +137,8 @@ __device__ __forceinline__ float stc_tanh(float v) {
     return fabsf(v) < 0.25f ? small : big;
 }
 
-__device__ __forceinline__ float stc_wave_sum(float v) {
+template <class T>      // float or double
+__device__ __forceinline__ T stc_wave_sum(T v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;

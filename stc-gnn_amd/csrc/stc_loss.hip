@@ -17,12 +17,6 @@ constexpr int LOSS_WAVES = LOSS_THREADS / stc::kWave;
 
 __device__ __forceinline__ float clamp_below(float v, float lo) { return v < lo ? lo : v; }      // NaN stays NaN
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 struct Sums3 {
     float bce, py, sum;
     __device__ __forceinline__ void add(float p, float y) {
@@ -69,7 +63,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_partials_kernel(const float
         for (int i = threadIdx.x; i < ck.len; i += LOSS_THREADS) acc.add(pp[i], yy[i]);
     }
     __shared__ double red[LOSS_WAVES][3];
-    const double v0 = wave_sum_f64((double)acc.bce), v1 = wave_sum_f64((double)acc.py), v2 = wave_sum_f64((double)acc.sum);
+    const double v0 = stc_wave_sum((double)acc.bce), v1 = stc_wave_sum((double)acc.py), v2 = stc_wave_sum((double)acc.sum);
     const int lane = threadIdx.x % stc::kWave, wave = threadIdx.x / stc::kWave;
     if (lane == 0) {
         red[wave][0] = v0;
@@ -101,9 +95,9 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_finish_kernel(const double*
             I += pb[i * 3 + 1];
             D += pb[i * 3 + 2];
         }
-        bce = wave_sum_f64(bce);
-        I = wave_sum_f64(I);
-        D = wave_sum_f64(D);
+        bce = stc_wave_sum(bce);
+        I = stc_wave_sum(I);
+        D = stc_wave_sum(D);
         const double flag = 0.0 * bce;
         if (lane == 0) {
             bce_b[b] = bce;
@@ -118,8 +112,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_finish_kernel(const double*
         dice += 1.0 - 2.0 * sums[b * 2] / sums[b * 2 + 1];
     }
     __shared__ double red[LOSS_WAVES][2];
-    bce = wave_sum_f64(bce);
-    dice = wave_sum_f64(dice);
+    bce = stc_wave_sum(bce);
+    dice = stc_wave_sum(dice);
     if (lane == 0) {
         red[wave][0] = bce;
         red[wave][1] = dice;
@@ -163,8 +157,6 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(const float* __r
     }
 }
 
-inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // chunks per run and workgroups of a launch; -1 for negative sizes, -2 beyond the grid limit
 inline long long loss_grid(int64_t batch, int64_t segments, int64_t seg, long long* chunks) {
     if (batch < 0 || segments < 0 || seg < 0) return -1;
@@ -205,8 +197,8 @@ extern "C" int stc_combo_loss_fwd_f32(const float* p, const float* y, int64_t ba
     if (int rc = loss_checked("stc_combo_loss_fwd_f32", batch, segments, seg, p_sb, p_ss, y_sb, y_ss, &chunks, &blocks)) return rc;
     if (blocks == 0) return STC_OK;
     STC_REQUIRE(p && y && loss && sums && workspace, STC_EINVAL, "stc_combo_loss_fwd_f32: null pointer");
-    STC_REQUIRE(aligned_to(p, 4) && aligned_to(y, 4) && aligned_to(loss, 4), STC_EALIGN, "stc_combo_loss_fwd_f32: p, y and loss must be 4-byte aligned");
-    STC_REQUIRE(aligned_to(sums, 8) && aligned_to(workspace, 8), STC_EALIGN, "stc_combo_loss_fwd_f32: sums and workspace must be 8-byte aligned");
+    STC_REQUIRE(stc::aligned(p, 4) && stc::aligned(y, 4) && stc::aligned(loss, 4), STC_EALIGN, "stc_combo_loss_fwd_f32: p, y and loss must be 4-byte aligned");
+    STC_REQUIRE(stc::aligned(sums, 8) && stc::aligned(workspace, 8), STC_EALIGN, "stc_combo_loss_fwd_f32: sums and workspace must be 8-byte aligned");
     const size_t need = stc_combo_loss_workspace_bytes(batch, segments, seg);
     STC_REQUIRE(workspace_bytes >= need, STC_EINVAL, "stc_combo_loss_fwd_f32: workspace of %zu bytes, %zu needed", workspace_bytes, need);
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -232,9 +224,9 @@ extern "C" int stc_combo_loss_bwd_f32(const float* p, const float* y, const doub
     if (int rc = loss_checked("stc_combo_loss_bwd_f32", batch, segments, seg, p_sb, p_ss, y_sb, y_ss, &chunks, &blocks)) return rc;
     if (blocks == 0) return STC_OK;
     STC_REQUIRE(p && y && sums && grad_out && dp, STC_EINVAL, "stc_combo_loss_bwd_f32: null pointer");
-    STC_REQUIRE(aligned_to(p, 4) && aligned_to(y, 4) && aligned_to(grad_out, 4) && aligned_to(dp, 4), STC_EALIGN,
+    STC_REQUIRE(stc::aligned(p, 4) && stc::aligned(y, 4) && stc::aligned(grad_out, 4) && stc::aligned(dp, 4), STC_EALIGN,
                 "stc_combo_loss_bwd_f32: p, y, grad_out and dp must be 4-byte aligned");
-    STC_REQUIRE(aligned_to(sums, 8), STC_EALIGN, "stc_combo_loss_bwd_f32: sums must be 8-byte aligned");
+    STC_REQUIRE(stc::aligned(sums, 8), STC_EALIGN, "stc_combo_loss_bwd_f32: sums must be 8-byte aligned");
     STC_REQUIRE(dp != p && dp != y, STC_EINVAL, "stc_combo_loss_bwd_f32: dp must not alias p or y");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)blocks), block(LOSS_THREADS);

@@ -25,8 +25,8 @@ using v4f = __attribute__((ext_vector_type(4))) float;
 constexpr int LR_THREADS = 256, LR_WAVES = LR_THREADS / stc::kWave, LR_MAX_RANK = 64;
 static_assert(STC_FUSION_LR_CHUNK % LR_THREADS == 0, "a chunk is whole passes of a workgroup in every form (256 >> lg rows per pass)");
 
-// sum over the lanes `from`, 2 `from`, ... 32 apart (from = 1: the whole wave)
-__device__ __forceinline__ double lane_sum_f64(double v, int from) {
+// sum over the lanes `from`, 2 `from`, ... 32 apart: the partial sum that leaves one total per group of `from` neighbouring lanes
+__device__ __forceinline__ double lr_strided_lane_sum(double v, int from) {
     for (int off = 32; off >= from; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
@@ -37,7 +37,7 @@ __device__ __forceinline__ void lr_store_partials(const v4f sa, const v4f sp, in
     const int R4 = 1 << lg, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        const double a = lane_sum_f64((double)sa[c], R4), p = lane_sum_f64((double)sp[c], R4);
+        const double a = lr_strided_lane_sum((double)sa[c], R4), p = lr_strided_lane_sum((double)sp[c], R4);
         if (lane < R4) {                                     // lane = its column group q here
             red[wave][4 * lane + c] = a;
             red[wave][r + 4 * lane + c] = p;
@@ -65,7 +65,7 @@ __device__ __forceinline__ void lr_plain_colsums(const float* __restrict__ MA, c
             const float* w = is_p ? wp : wa;
             for (int i = lane; i < rows; i += 64) acc = fmaf(M[(size_t)i * r], w[i], acc);
         }
-        const double tot = lane_sum_f64((double)acc, 1);
+        const double tot = stc_wave_sum((double)acc);
         if (lane == 0) part[j] = tot;
     }
 }
@@ -274,8 +274,6 @@ __global__ __launch_bounds__(LR_THREADS) void lr_bwd_rows_kernel(const float* __
     }
 }
 
-inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // log2(r / 4) where the vector form takes the rank, -1 for the plain form
 inline int lr_form(int32_t r) {
     for (int lg = 0; lg <= 4; ++lg)
@@ -310,9 +308,9 @@ extern "C" int stc_mixed_fusion_lr_fwd_f32(const float* UA, const float* VA, con
     STC_REQUIRE(UA && VA && bA && UP && VP && bP && A && P && gate && G && t && workspace, STC_EINVAL, "stc_mixed_fusion_lr_fwd_f32: null pointer");
     STC_REQUIRE(stc::aligned16(UA) && stc::aligned16(VA) && stc::aligned16(UP) && stc::aligned16(VP), STC_EALIGN,
                 "stc_mixed_fusion_lr_fwd_f32: U_A / V_A / U_P / V_P must be 16-byte aligned");
-    STC_REQUIRE(aligned_to(bA, 4) && aligned_to(bP, 4) && aligned_to(A, 4) && aligned_to(P, 4) && aligned_to(gate, 4) && aligned_to(G, 4) && aligned_to(t, 4),
+    STC_REQUIRE(stc::aligned(bA, 4) && stc::aligned(bP, 4) && stc::aligned(A, 4) && stc::aligned(P, 4) && stc::aligned(gate, 4) && stc::aligned(G, 4) && stc::aligned(t, 4),
                 STC_EALIGN, "stc_mixed_fusion_lr_fwd_f32: vectors must be 4-byte aligned");
-    STC_REQUIRE(aligned_to(workspace, 8), STC_EALIGN, "stc_mixed_fusion_lr_fwd_f32: workspace must be 8-byte aligned");
+    STC_REQUIRE(stc::aligned(workspace, 8), STC_EALIGN, "stc_mixed_fusion_lr_fwd_f32: workspace must be 8-byte aligned");
     const size_t need = stc_mixed_fusion_lr_workspace_bytes(D, r);
     STC_REQUIRE(workspace_bytes >= need, STC_EINVAL, "stc_mixed_fusion_lr_fwd_f32: workspace of %zu bytes, %zu needed", workspace_bytes, need);
     STC_REQUIRE(gate != A && gate != P && G != A && G != P && G != gate, STC_EINVAL, "stc_mixed_fusion_lr_fwd_f32: gate and G must not alias A, P or each other");
@@ -336,10 +334,10 @@ extern "C" int stc_mixed_fusion_lr_bwd_f32(const float* UA, const float* VA, con
     STC_REQUIRE(stc::aligned16(UA) && stc::aligned16(VA) && stc::aligned16(UP) && stc::aligned16(VP) && stc::aligned16(dUA) && stc::aligned16(dVA) &&
                     stc::aligned16(dUP) && stc::aligned16(dVP),
                 STC_EALIGN, "stc_mixed_fusion_lr_bwd_f32: the factors and their gradients must be 16-byte aligned");
-    STC_REQUIRE(aligned_to(A, 4) && aligned_to(P, 4) && aligned_to(gate, 4) && aligned_to(t, 4) && aligned_to(dG, 4) && aligned_to(db, 4) && aligned_to(dA, 4) &&
-                    aligned_to(dP, 4),
+    STC_REQUIRE(stc::aligned(A, 4) && stc::aligned(P, 4) && stc::aligned(gate, 4) && stc::aligned(t, 4) && stc::aligned(dG, 4) && stc::aligned(db, 4) && stc::aligned(dA, 4) &&
+                    stc::aligned(dP, 4),
                 STC_EALIGN, "stc_mixed_fusion_lr_bwd_f32: vectors must be 4-byte aligned");
-    STC_REQUIRE(aligned_to(workspace, 8), STC_EALIGN, "stc_mixed_fusion_lr_bwd_f32: workspace must be 8-byte aligned");
+    STC_REQUIRE(stc::aligned(workspace, 8), STC_EALIGN, "stc_mixed_fusion_lr_bwd_f32: workspace must be 8-byte aligned");
     const size_t need = stc_mixed_fusion_lr_workspace_bytes(D, r);
     STC_REQUIRE(workspace_bytes >= need, STC_EINVAL, "stc_mixed_fusion_lr_bwd_f32: workspace of %zu bytes, %zu needed", workspace_bytes, need);
     for (const float* out : {(const float*)dUA, (const float*)dVA, (const float*)dUP, (const float*)dVP, (const float*)db, (const float*)dA, (const float*)dP})

@@ -12,9 +12,6 @@ struct GraphArgs {      // either form of the same matrix; BCSR is used when blk
     const int32_t *blk_ptr, *blk_cols; const float* blk_vals;
 };
 
-// ---- the end of a launch helper: the status of the launch just made
-inline int launched(const char* what) { return hip_status(hipGetLastError(), what); }
-
 // batch is grid.y
 inline int check_batch(const char* who, int batch) {
     STC_REQUIRE(batch <= 65535, STC_ELIMIT, "%s: batch %d > 65535 (grid.y)", who, batch);

@@ -21,14 +21,14 @@ def mixed_fusion_lr_supported(A, P, UA, VA, bA, UP, VP, bP) -> bool:
     No (n, r) is excluded by measurement: the kernels' replayed forward + backward was faster than the torch route at every pair
     measured (profiles/r12/mixed_fusion_lr_ab.txt)."""
     ts = (A, P, UA, VA, bA, UP, VP, bP)
-    if not (_FUSED and all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.device == A.device for t in ts)):
+    if not (_FUSED and all(isinstance(t, torch.Tensor) for t in ts) and ops._f32_on_gpu(ts) and all(t.device == A.device for t in ts)):
         return False
     if A.dim() != 2 or A.shape[0] != A.shape[1] or P.shape != A.shape or A.numel() == 0 or UA.dim() != 2:
         return False
     D, r = A.numel(), UA.shape[1]
     if not (1 <= r <= FUSION_LR_MAX_RANK and all(t.shape == (D, r) for t in (UA, VA, UP, VP)) and bA.shape == (D,) and bP.shape == (D,)):
         return False
-    if not all(t.is_contiguous() for t in ts[2:]) or any(t.data_ptr() % 16 for t in ts):      # (a view into a flat parameter buffer may not be)
+    if not ops._laid_out(ts, ts[2:]):
         return False
     k = ops.kernels()
     return bool(getattr(k, 'mixed_fusion_lr', False)) and k.mixed_fusion_lr_supported(D, r)

@@ -5,6 +5,7 @@
     gru_blend    tanh + GRU blend (STC_GNN.py:76-78)
     concat2      torch.cat([Xt, Ht_1], -1) (STC_GNN.py:68)
     cheby_dense  BDG_Dif.cheby_poly on the small category graph (STC_GNN.py:24-29)
+    mixed_fusion, mgp_front   the learned graph generator MGP_Gen (STC_GNN.py:210-261), at the end of the file; its rank-r fusion is ``stc_hip.fusion``
 
 Decomposition of one BDG_Dif (K = Ks = Kc in the reference, kept separate here):
 
@@ -1212,7 +1213,16 @@ def stc_cell_graph(op: SpatialOperand, Tc, Ks: int, schedule, outputs, ext, stac
     return _StcCellGraph.apply(op, Ks, list(schedule), list(outputs), len(ext), Tc, op.fwd_val, *ext, *flat)
 
 
-# ---- MixedFusion of the learned graph generator ---------------------------------------------------------------------------------------
+# ---- the learned graph generator (MGP_Gen): dense MixedFusion and the front end; the rank-r MixedFusion is fusion.py ----------------------------
+# What the three ``*_supported`` predicates share: float32 on a ROCm device; contiguous parameters, every tensor 16-byte aligned.
+def _f32_on_gpu(ts) -> bool:
+    return all(t.is_cuda and t.dtype == torch.float32 for t in ts)
+
+
+def _laid_out(ts, params) -> bool:
+    return all(t.is_contiguous() for t in params) and all(t.data_ptr() % 16 == 0 for t in ts)      # (a view into a flat parameter buffer may not be)
+
+
 class _MixedFusion(torch.autograd.Function):
     """G = gate * A + (1 - gate) * P with gate = sigmoid(lin_A(vec A) + lin_P(vec P)) (reference STC_GNN.py:253-260) in one streaming launch per
     direction (``stc_mixed_fusion_fwd/bwd_f32``): the two (n^2, n^2) weight matrices are read once forward and once backward, their
@@ -1240,9 +1250,7 @@ class _MixedFusion(torch.autograd.Function):
 def mixed_fusion_supported(A: torch.Tensor, P: torch.Tensor, *params: torch.Tensor) -> bool:
     """Whether ``mixed_fusion`` takes these operands: float32 on a GPU, contiguous weights, 16-byte aligned, n^2 a multiple of 4."""
     ts = (A, P) + params
-    return (all(t.is_cuda and t.dtype == torch.float32 for t in ts) and all(t.is_contiguous() for t in params)
-            and all(t.data_ptr() % 16 == 0 for t in ts)               # (a slice / a view into a flat parameter buffer may not be: torch ops then)
-            and kernels().mixed_fusion_supported(A.numel()))
+    return _f32_on_gpu(ts) and _laid_out(ts, params) and kernels().mixed_fusion_supported(A.numel())
 
 
 def mixed_fusion(A, P, WA, bA, WP, bP):
@@ -1289,7 +1297,7 @@ class _MgpSoftmax(torch.autograd.Function):
 
 def mgp_front_supported(X: torch.Tensor, Wu: torch.Tensor, Wv: torch.Tensor) -> bool:
     """Whether ``mgp_front`` takes these operands: a float32 window (B, T, N, C) and float32 (F, h) parameters on a GPU, no gradient wanted for X."""
-    return (X.is_cuda and X.dim() == 4 and all(t.is_cuda and t.dtype == torch.float32 for t in (X, Wu, Wv)) and not X.requires_grad
+    return (X.dim() == 4 and _f32_on_gpu((X, Wu, Wv)) and not X.requires_grad
             and Wu.dim() == 2 and Wu.shape == Wv.shape and hasattr(kernels(), 'mgp_uv_fwd'))
 
 

@@ -1,22 +1,27 @@
 """The autograd contract of every operator ("Autograd contract"): what the twelve ``torch.autograd.Function``s of ``stc_hip.ops`` and
 ``stc_hip.small`` promise outside the one pattern the parity tests drive them in (fresh contiguous tensors, everything differentiable, one
-forward, one backward).
+forward, one backward).  The Functions of the package without a case here are listed in ``CONTRACT_ELSEWHERE``.
 
 One parametrised test per property P1..P11 over the case table of tests/autograd_contract.py, each on the CPU twin (``cpu-emulated``: the host logic
 of the Functions over oracle/kernel_emul.py) and on the GPU (``cuda``: the same through libstc_hip.so -- what the twin cannot say is what a HIP
 kernel does to a plane it is handed).  A case the twin has no kernels for runs on the GPU only; a property that cannot apply to a case is listed
 in ``NOT_APPLICABLE`` with its reason.  The negative controls show, on the CPU, that P2, P4, P5 and P10 can fail.
 """
+import importlib
+import os
+import pkgutil
+
 import pytest
 import torch
 from torch.autograd.function import once_differentiable
 
 import STC_GNN as M
+import stc_hip
 from oracle.kernel_emul import EmulatedKernels
-from stc_hip import ops, small
+from stc_hip import ops
 from tests import autograd_contract as A
-from tests.autograd_contract import BY_ID, CASES, NOT_APPLICABLE, NOT_BITWISE_WHEN_FROZEN, REFUSALS, ContractFailure
-from tests.conftest import rel_err
+from tests.autograd_contract import BY_ID, CASES, CONTRACT_ELSEWHERE, NOT_APPLICABLE, NOT_BITWISE_WHEN_FROZEN, REFUSALS, ContractFailure
+from tests.conftest import REPO, rel_err
 
 
 @pytest.fixture
@@ -175,11 +180,20 @@ def _functions_of(mod):
 
 
 def test_every_function_is_named_by_a_case():
-    defined = _functions_of(ops) | _functions_of(small)
-    assert len(defined) == 12, sorted(f.__name__ for f in defined)
+    """Every Function of every module of the ``stc_hip`` package has a case here, or is in ``CONTRACT_ELSEWHERE`` with the file that holds its properties."""
+    defined = set().union(*[_functions_of(importlib.import_module(f'stc_hip.{m.name}')) for m in pkgutil.iter_modules(stc_hip.__path__)])
+    by_name = {f'{f.__module__}.{f.__name__}': f for f in defined}
+    assert len(CONTRACT_ELSEWHERE) == 3
+    for name, path in CONTRACT_ELSEWHERE.items():
+        assert name in by_name, f'{name} is no autograd Function of stc_hip'
+        assert os.path.isfile(os.path.join(REPO, path)), path
+    elsewhere = {by_name[name] for name in CONTRACT_ELSEWHERE}
     named = {f for c in CASES for f in c.functions}
     assert named <= defined
-    assert not defined - named, f'autograd Functions without a case in tests/autograd_contract.py: {sorted(f.__name__ for f in defined - named)}'
+    assert not named & elsewhere, sorted(f.__name__ for f in named & elsewhere)
+    assert len(named) == 12, sorted(f.__name__ for f in named)
+    missing = defined - named - elsewhere
+    assert not missing, f'autograd Functions without a case in tests/autograd_contract.py: {sorted(f.__name__ for f in missing)}'
 
 
 def test_the_exception_tables_are_closed_and_name_real_cases():

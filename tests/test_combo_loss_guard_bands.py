@@ -3,10 +3,8 @@ into a larger allocation, NaN / bit-pattern margins, the workspace at exactly th
 equal the launch on plain tensors bit for bit and lie within ``TOL`` of the float64 twin.
 
 The cases are run here, and importing this file also appends them to ``tests.test_guard_bands.CASES``: that file's coverage walk
-(``test_every_entry_point_has_a_banded_case``) goes over the whole ctypes table and wants every entry point named by a case of ITS table.  It
-therefore passes in any run that collects the whole ``tests`` directory (this file is then imported before the walk runs), and it cannot pass
-when tests/test_guard_bands.py is run alone: that file does not import this one.  The follow-up is to move these cases into
-tests/test_guard_bands.py and delete this file."""
+(``test_every_entry_point_has_a_banded_case``) goes over the whole ctypes table and wants every entry point named by a case of ITS table; it
+imports every tests/test_*_guard_bands.py itself, so it also passes when tests/test_guard_bands.py is run alone."""
 import pytest
 import torch
 

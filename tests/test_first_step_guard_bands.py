@@ -4,7 +4,7 @@ equal the launch on plain tensors bit for bit and lie within the family's bound 
 
 The cases are run here, and importing this file also appends them to ``tests.test_guard_bands.CASES``: that file's coverage walk
 (``test_every_entry_point_has_a_banded_case``) goes over the whole ctypes table and wants every entry point named by a case of ITS table; it
-imports this file itself, so it also passes when tests/test_guard_bands.py is run alone.  The follow-up is to move these cases into
+imports every tests/test_*_guard_bands.py itself, so it also passes when tests/test_guard_bands.py is run alone.  The follow-up is to move these cases into
 tests/test_guard_bands.py and delete this file."""
 import pytest
 import torch

@@ -36,7 +36,9 @@ a constant) where the twin's first matrix is the plain product -- compared from 
 own results are banded through the substituted ``torch``; each case states how many such buffers it expects (``fronts=``) and fails when another
 number was banded, and a front that allocates through any other torch factory raises.
 """
+import importlib
 import math
+import pkgutil
 
 import pytest
 import torch
@@ -1376,7 +1378,12 @@ def _takes_device_buffers(argtypes):
 
 
 def test_every_entry_point_has_a_banded_case():
-    from tests import test_first_step_guard_bands  # noqa: F401  (appends the first-step cases to CASES: also when this file is run alone)
+    import tests                                    # every tests/test_*_guard_bands.py appends its cases to CASES on import: also when this file is run alone
+    for m in pkgutil.iter_modules(tests.__path__):
+        if m.name.startswith('test_') and m.name.endswith('_guard_bands'):
+            importlib.import_module(f'tests.{m.name}')
+    ids = [c.id for c in CASES]
+    assert len(ids) == len(set(ids)), sorted(i for i in set(ids) if ids.count(i) > 1)
     named = set().union(*[c.entries for c in CASES])
     assert named <= set(_lib._ABI), named - set(_lib._ABI)
     assert not named & set(NO_BANDED_CASE)

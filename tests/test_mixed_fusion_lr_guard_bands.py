@@ -5,7 +5,7 @@ the float64 twin of tests/test_mixed_fusion_lr.py.
 
 The cases are run here, and importing this file also appends them to ``tests.test_guard_bands.CASES``, exactly as
 tests/test_combo_loss_guard_bands.py does: that file's coverage walk (``test_every_entry_point_has_a_banded_case``) goes over the whole ctypes
-table and wants every entry point named by a case of ITS table."""
+table and wants every entry point named by a case of ITS table; it imports every tests/test_*_guard_bands.py itself."""
 import pytest
 import torch
 
