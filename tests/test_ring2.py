@@ -25,17 +25,14 @@ def _renumbered(H, W, seed=1234):
     return graph
 
 
-@pytest.mark.parametrize('H,W,renumbered', [(12, 20, False), (9, 33, False), (31, 8, False), (24, 30, True), (40, 17, True)])
-def test_two_ring_plan_reproduces_the_matrix(H, W, renumbered):
-    """The plan's tables ARE the matrix: level 2 rebuilds every row of S over the first ring's slots, level 1 every first-ring row over the
-    staged rows; every row of S is some patch's own row exactly once; rings within their sizes.  Lattices (4 x 8 tiles) and a grid whose
-    numbering is not a lattice (ring-bounded clusters)."""
-    graph = _renumbered(H, W) if renumbered else CsrGraph.queen_grid(H, W, normalize=True)
-    h = graph._host
-    assert 'bwd_r2_l2' in h
-    S = _dense(graph)                                                 # Gs itself: the backward operand
-    l2, l1, own, t1, t2 = (h[f'bwd_r2_{k}'] for k in ('l2', 'l1', 'own', 't1', 't2'))
-    n = H * W
+def check_two_ring_plan(graph, side='bwd'):
+    """The plan's tables ARE the matrix (``side``: 'bwd' = Gs, 'fwd' = Gs^T): level 2 rebuilds every row of S over the first ring's slots, level 1
+    every first-ring row over the staged rows; every row of S is some patch's own row exactly once; rings within their sizes.  Shared with
+    tests/test_aggregation_graphs.py, which runs it on weighted, ragged and one-way graphs."""
+    h, n = graph._host, graph.n
+    assert f'{side}_r2_l2' in h
+    S = _dense(graph) if side == 'bwd' else _dense(graph).T          # Gs itself: the backward operand; its transpose: the forward's
+    l2, l1, own, t1, t2 = (h[f'{side}_r2_{k}'] for k in ('l2', 'l1', 'own', 't1', 't2'))
     seen = np.zeros(n, dtype=int)
     for p in range(l2.shape[0]):
         rows = own[p][own[p] >= 0]
@@ -57,8 +54,17 @@ def test_two_ring_plan_reproduces_the_matrix(H, W, renumbered):
             assert np.allclose(got, S[u], atol=1e-7)
     assert (seen == 1).all()
     assert l1.shape[1] == RING2_FIRST and l2.shape[1] == RING2_SECOND and own.shape[1] == RING2_INTERIOR
+    return l2.shape[0]
+
+
+@pytest.mark.parametrize('H,W,renumbered', [(12, 20, False), (9, 33, False), (31, 8, False), (24, 30, True), (40, 17, True)])
+def test_two_ring_plan_reproduces_the_matrix(H, W, renumbered):
+    """The plan's tables ARE the matrix (``check_two_ring_plan``).  Lattices (4 x 8 tiles) and a grid whose numbering is not a lattice
+    (ring-bounded clusters)."""
+    graph = _renumbered(H, W) if renumbered else CsrGraph.queen_grid(H, W, normalize=True)
+    n_patches = check_two_ring_plan(graph, 'bwd')
     if renumbered:
-        assert 'bwd_pt_src' in h and n / l2.shape[0] >= 16          # the patch form's clusters did not fit the rings; these do, at a useful size
+        assert 'bwd_pt_src' in graph._host and H * W / n_patches >= 16    # the patch form's clusters did not fit the rings; these do, at a useful size
 
 
 def test_graphs_whose_rings_do_not_fit_get_no_two_ring_plan():
