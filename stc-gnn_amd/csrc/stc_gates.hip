@@ -2,6 +2,7 @@
 // small category graph (STC_GNN.py:24-29) and the pointwise helpers -- gfx950.
 // All of these are streaming, HBM-bound kernels: one pass over each operand.
 #include "stc_common.h"
+#include "stc_spmm_piece.h"
 
 #include <initializer_list>
 
@@ -285,18 +286,8 @@ __global__ __launch_bounds__(EW_THREADS) void head_bwd_kernel(const float* __res
 
 // bf16 state rows, hidden 16 (the bf16-storage configuration): a row is 32 bytes, two lanes share it with one 16-byte piece of
 // 8 bf16 each; y, dy and the weight gradient stay fp32
-using head_u4 = __attribute__((ext_vector_type(4))) unsigned;
-using head_bf2 = __attribute__((ext_vector_type(2))) __bf16;
-__device__ __forceinline__ void head_unpack8(const head_u4 v, float (&r)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { r[2 * i] = __uint_as_float(v[i] << 16); r[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u); }
-}
-__device__ __forceinline__ unsigned head_pk(float a, float b) {
-    const head_bf2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
-
-__global__ __launch_bounds__(EW_THREADS) void head_fwd_bf16_kernel(const head_u4* __restrict__ H, const float* __restrict__ w,
+// (widen / pack of the 8 bf16 of a piece: stc_spmm_piece.h)
+__global__ __launch_bounds__(EW_THREADS) void head_fwd_bf16_kernel(const u32x4* __restrict__ H, const float* __restrict__ w,
                                                                     const float* __restrict__ b, float* __restrict__ y, long long rows) {
     constexpr int RPB = EW_THREADS / 2;
     const int q = threadIdx.x & 1;
@@ -306,7 +297,7 @@ __global__ __launch_bounds__(EW_THREADS) void head_fwd_bf16_kernel(const head_u4
     const float bias = b[0];
     for (long long r = (long long)blockIdx.x * RPB + threadIdx.x / 2; r < rows; r += (long long)gridDim.x * RPB) {
         float v[8];
-        head_unpack8(H[2 * r + q], v);
+        unpack8(H[2 * r + q], v);
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) s = fmaf(v[i], wq[i], s);
@@ -315,9 +306,9 @@ __global__ __launch_bounds__(EW_THREADS) void head_fwd_bf16_kernel(const head_u4
     }
 }
 
-__global__ __launch_bounds__(EW_THREADS) void head_bwd_bf16_kernel(const head_u4* __restrict__ H, const float* __restrict__ w,
+__global__ __launch_bounds__(EW_THREADS) void head_bwd_bf16_kernel(const u32x4* __restrict__ H, const float* __restrict__ w,
                                                                     const float* __restrict__ y, const float* __restrict__ dy,
-                                                                    head_u4* __restrict__ dH, float* __restrict__ partial, long long rows) {
+                                                                    u32x4* __restrict__ dH, float* __restrict__ partial, long long rows) {
     constexpr int RPB = EW_THREADS / 2, h = 16;
     __shared__ float red[EW_THREADS][9];
     const int q = threadIdx.x & 1;
@@ -329,8 +320,8 @@ __global__ __launch_bounds__(EW_THREADS) void head_bwd_bf16_kernel(const head_u4
         const float g = dy[r] * yy * (1.f - yy);
         if (q == 0) accg += g;
         float v[8];
-        head_unpack8(H[2 * r + q], v);
-        dH[2 * r + q] = head_u4{head_pk(g * wq[0], g * wq[1]), head_pk(g * wq[2], g * wq[3]), head_pk(g * wq[4], g * wq[5]), head_pk(g * wq[6], g * wq[7])};
+        unpack8(H[2 * r + q], v);
+        dH[2 * r + q] = u32x4{pk_bf16(g * wq[0], g * wq[1]), pk_bf16(g * wq[2], g * wq[3]), pk_bf16(g * wq[4], g * wq[5]), pk_bf16(g * wq[6], g * wq[7])};
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i] = fmaf(g, v[i], acc[i]);
     }
@@ -550,7 +541,7 @@ extern "C" int stc_head_fwd_bf16(const void* H, const float* w, const float* b, 
     STC_REQUIRE(h == 16, STC_EUNSUPPORTED, "stc_head_fwd_bf16: hidden width %d (built for 16)", h);
     STC_EW_PROLOGUE("stc_head_fwd_bf16", rows, H && w && b && y);
     STC_REQUIRE(stc::aligned16(H), STC_EALIGN, "stc_head_fwd_bf16: H not 16-byte aligned");
-    hipLaunchKernelGGL(head_fwd_bf16_kernel, ew_grid(rows * 2), dim3(EW_THREADS), 0, s, static_cast<const head_u4*>(H), w, b, y, (long long)rows);
+    hipLaunchKernelGGL(head_fwd_bf16_kernel, ew_grid(rows * 2), dim3(EW_THREADS), 0, s, static_cast<const u32x4*>(H), w, b, y, (long long)rows);
     STC_LAUNCH_CHECK("stc_head_fwd_bf16 launch");
     return STC_OK;
 }
@@ -568,8 +559,8 @@ extern "C" int stc_head_bwd_bf16(const void* H, const float* w, const float* y, 
     long long blocks = (rows * 2 + EW_THREADS - 1) / EW_THREADS;
     const int grid = (int)(blocks < HEAD_PARTS ? blocks : HEAD_PARTS);
     float* partial = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(head_bwd_bf16_kernel, dim3(grid), dim3(EW_THREADS), 0, s, static_cast<const head_u4*>(H), w, y, dy,
-                       static_cast<head_u4*>(dH), partial, (long long)rows);
+    hipLaunchKernelGGL(head_bwd_bf16_kernel, dim3(grid), dim3(EW_THREADS), 0, s, static_cast<const u32x4*>(H), w, y, dy,
+                       static_cast<u32x4*>(dH), partial, (long long)rows);
     hipLaunchKernelGGL(head_reduce_kernel, dim3(h + 1), dim3(EW_THREADS), 0, s, partial, grid, h + 1, dwb);
     STC_LAUNCH_CHECK("stc_head_bwd_bf16 launch");
     return STC_OK;

@@ -23,15 +23,14 @@
 // Shapes: C = 32 * NB2 in {32, 64}, Ho = 16 * HB in {16, 32}, L in {16, 32} bf16 per row (Lw <= L real columns, pad columns
 // must hold finite values), Ks = Kc = K <= 3.  Everything else: STC_EUNSUPPORTED.
 #include "stc_node_frag.h"
+#include "stc_spmm_piece.h"      // pk_bf16, unpack8, pack8 of eight floats
 
 #include <cstdlib>
 
 namespace {
 
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
 typedef unsigned short bf16_t;          // storage only
 
 struct BPtrs { const bf16_t* p[STC_MAX_K]; };
@@ -40,10 +39,6 @@ struct BDPtrs { bf16_t* p[STC_MAX_K]; };
 #define kZero4 (f32x4{0.f, 0.f, 0.f, 0.f})
 #define kZeroU4 (u32x4{0u, 0u, 0u, 0u})
 
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {     // v_cvt_pk_bf16_f32 (RNE): a in the low half
-    const bf16x2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
 __device__ __forceinline__ u32x4 pack8(const f32x4 a, const f32x4 b) {      // slots 0..3 from a, 4..7 from b
     return u32x4{pk_bf16(a[0], a[1]), pk_bf16(a[2], a[3]), pk_bf16(b[0], b[1]), pk_bf16(b[2], b[3])};
 }
@@ -402,13 +397,6 @@ struct GatesPro { const bf16_t *dRH, *Cand, *H, *U, *R, *dHnew; bf16_t* dH; };
 struct BPtrs2 { const bf16_t* p[STC_MAX_K]; const bf16_t* q[STC_MAX_K]; };
 struct BDPtrs2 { bf16_t* p[STC_MAX_K]; bf16_t* q[STC_MAX_K]; };
 
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&r)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { r[2 * i] = __uint_as_float(v[i] << 16); r[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u); }
-}
-__device__ __forceinline__ u32x4 pack8f(const float (&r)[8]) {
-    return u32x4{pk_bf16(r[0], r[1]), pk_bf16(r[2], r[3]), pk_bf16(r[4], r[5]), pk_bf16(r[6], r[7])};
-}
 
 template <int NB2, int HB, int K, int L, int PL = 0, int PRO = 0, int WAVES = BwdWaves<NB2, K>::v>
 __global__ __launch_bounds__(MF_THREADS, WAVES) void node_bwd_bf16_kernel(
@@ -521,10 +509,10 @@ __global__ __launch_bounds__(MF_THREADS, WAVES) void node_bwd_bf16_kernel(
                     gy[i] = g < 2 ? gu : gr;
                     dh[i] = fmaf(dr[i], rr[i], gn[i] * (1.f - uu[i]));
                 }
-                dyr[rb] = pack8f(gy);
+                dyr[rb] = pack8(gy);
                 if (g < 2) {
                     if (pro.dH) {
-                        stc_st_once(reinterpret_cast<u32x4*>(pro.dH + (r0 + 16 * rb + x) * 16 + 8 * g), pack8f(dh));
+                        stc_st_once(reinterpret_cast<u32x4*>(pro.dH + (r0 + 16 * rb + x) * 16 + 8 * g), pack8(dh));
                     } else {                                    // park the share: row x, columns 8g .. 8g+7 of block rb
                         float4* slot = reinterpret_cast<float4*>(stash + (rb * 16 + x) * 16 + 8 * g);
                         slot[0] = make_float4(dh[0], dh[1], dh[2], dh[3]);
@@ -792,7 +780,7 @@ __global__ __launch_bounds__(256) void blend_bwd_bf16_kernel(const u32x4* __rest
         unpack8(dHnew[i], gn); unpack8(U[i], u); unpack8(Cand[i], c);
 #pragma unroll
         for (int k = 0; k < 8; ++k) gn[k] = gn[k] * u[k] * (1.f - c[k] * c[k]);
-        dY[i] = pack8f(gn);
+        dY[i] = pack8(gn);
     }
 }
 
@@ -942,7 +930,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void cell_bwd_bf16_kernel(CellBwdB16
                 unpack8(cur.gn[rb], gn); unpack8(cur.cd[rb], cd); unpack8(cur.uu[rb], uu); unpack8(cur.rr[rb], rr); unpack8(h_cols(rb), hh);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) { dy[i] = gn[i] * uu[i] * (1.f - cd[i] * cd[i]); rh[i] = rr[i] * hh[i]; }
-                const u32x4 dyp = pack8f(dy), rhp = pack8f(rh);
+                const u32x4 dyp = pack8(dy), rhp = pack8(rh);
                 dyr[rb] = g < 2 ? dyp : cur.bm[rb];               // the [dY | dBm] row
                 zc[rb] = NARROW ? (g < 2 ? rhp : (g == 2 ? xin[NARROW ? rb : 0] : kZeroU4)) : (g < 2 ? cur.zx[rb] : rhp);      // [X | R*H]; narrow: [R*H | x | 0]
             }
@@ -1020,7 +1008,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void cell_bwd_bf16_kernel(CellBwdB16
                 gy[i] = g < 2 ? gu : gr;
                 dh[i] = fmaf(dr[i], rr[i], gn[i] * (1.f - uu[i]));
             }
-            dyr[rb] = pack8f(gy);
+            dyr[rb] = pack8(gy);
             if (g < 2) {
                 float4* slot = reinterpret_cast<float4*>(stash_h + (rb * 16 + x) * 16 + 8 * g);
                 slot[0] = make_float4(dh[0], dh[1], dh[2], dh[3]);

@@ -9,393 +9,104 @@
 // (its identity matrix is fp32-only); the contract here is "the fp32 kernel on the same bf16-valued inputs,
 // rounded once", which the parity tests check to one bf16 ulp.
 //
-// Skeleton as the fp32 kernels: a workgroup owns a run of consecutive output rows of one batch element, stages their
-// row pointers and (col, val) segment in LDS in one coalesced pass, (col, val) go to SGPRs so the neighbour-row base is
-// scalar, each lane streams 16-byte pieces (8 bf16, 1 KiB per wave instruction) with 4 neighbour rows in flight, blocks
-// are remapped so each XCD walks a contiguous band of rows, output / Y0 are non-temporal.  HBM-bound: a node row of
-// C*L = 2048 bf16 is the same 4 KiB as the fp32 row of the C = 32 configuration.
-#include "stc_spmm_host.h"
+// The kernels are the gather kernels of stc_spmm_gather.h (skeleton described there) with the bf16 format below: each lane streams 16-byte
+// pieces of 8 bf16 (1 KiB per wave instruction), output / Y0 / addend pieces are non-temporal.  HBM-bound: a node row of C*L = 2048 bf16 is the
+// same 4 KiB as the fp32 row of the C = 32 configuration.
+#include "stc_spmm_gather.h"
 
 namespace {
 
-using stc::GraphArgs;
-
-constexpr int SPMM_THREADS = 256;
-constexpr int SPMM_WAVES = SPMM_THREADS / 64;
-constexpr int SPMM_ROWS = 8;         // CSR kernel: output rows per workgroup
-constexpr int SPMM_SEG_CAP = 1024;   // CSR entries staged in LDS per workgroup
-constexpr int BR = STC_SPMM_BLOCK_ROWS;
-constexpr int BC_CAP = 512;          // block entries staged in LDS per workgroup
-
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-
-__device__ __forceinline__ float uniform_f(float v) {
-    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
-}
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {     // v_cvt_pk_bf16_f32 (RNE): a in the low half
-    const bf16x2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float lo_f(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float hi_f(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-
-struct Acc8 {                       // one 16-byte piece = 8 bf16 columns, accumulated in fp32
-    float v[8];
-    __device__ __forceinline__ void zero() {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = 0.f;
-    }
-    __device__ __forceinline__ void fma(float s, const u32x4 x) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = fmaf(s, lo_f(x[i]), v[2 * i]);
-            v[2 * i + 1] = fmaf(s, hi_f(x[i]), v[2 * i + 1]);
-        }
-    }
-};
-
-enum { EP_PLAIN = 0, EP_BLEND = 1, EP_SUM = 2, EP_SUM2 = 3 };
-
 struct Epi {
-    const u32x4* Y0;                 // PLAIN: optional base term (scaled by beta); BLEND: A (bias included)
-    u32x4* Y;                        // PLAIN / SUM output
+    const Raw* Y0;                   // PLAIN: optional base term (scaled by beta); BLEND: A (bias included)
+    Raw* Y;                          // PLAIN / SUM output
     float alpha, beta;               // PLAIN
     // BLEND (forward of the candidate convolution in post-aggregation form, STC_GNN.py:76-78): rows are state rows,
     // Cand = tanh(A + S.Bm), Hnew = (1-U)*H + U*Cand
-    const u32x4 *U, *H;
-    u32x4 *Cand, *Hnew;
+    const Raw *U, *H;
+    Raw *Cand, *Hnew;
     // SUM / SUM2 (gradient of a state from its consumers' pieces): Y = sum_i add[i] + S.(X [+ X2]); optional
     // dY = Y * U * (1 - Cand^2), the blend backward of the cell that owns the state (U, gCand: that cell's saved gates)
-    const u32x4* X2;
-    const u32x4* add[5]; int n_add;
-    const u32x4* gCand; u32x4* dY;
+    const Raw* X2;
+    const Raw* add[5]; int n_add;
+    const Raw* gCand; Raw* dY;
 };
-static_assert(sizeof(Epi::add) / sizeof(const u32x4*) == STC_SPMM_SUM_BF16_MAX_ADD, "the addend slots of the kernel argument are the ABI's limit");
+static_assert(sizeof(Epi::add) / sizeof(const Raw*) == STC_SPMM_SUM_BF16_MAX_ADD, "the addend slots of the kernel argument are the ABI's limit");
 
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&r)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { r[2 * i] = lo_f(v[i]); r[2 * i + 1] = hi_f(v[i]); }
-}
-__device__ __forceinline__ u32x4 pack8(const float (&r)[8]) {
-    return u32x4{pk_bf16(r[0], r[1]), pk_bf16(r[2], r[3]), pk_bf16(r[4], r[5]), pk_bf16(r[6], r[7])};
-}
-__device__ __forceinline__ float tanh_fast(float v) { return stc_tanh(v); }      // hardware exp2 / rcp, polynomial below 1/4 (stc_common.h)
+// bf16 rows on the gather kernels (stc_spmm_gather.h names the members): whole-plane operands, piece o = rowg * F8 + ch of every plane
+struct RowsBf16 {
+    using Acc = Piece<true>;
+    using Epi = ::Epi;
+    static constexpr int MAX_VPT = 2;
+    static constexpr bool ONE_WAVE_BLOCKS = true, PIPELINED = false, BLEND_AHEAD_WAVE_ROW = true;
 
-// BLEND: the epilogue's own operands, requested before the gather so that they arrive under it
-struct BlendIn { u32x4 a, u, h; };
-__device__ __forceinline__ void blend_piece(const Epi& ep, size_t o, const Acc8& acc, const BlendIn& in) {
-    float a[8], u[8], h[8], c[8], hn[8];
-    unpack8(in.a, a); unpack8(in.u, u); unpack8(in.h, h);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        c[i] = tanh_fast(acc.v[i] + a[i]);
-        hn[i] = (1.f - u[i]) * h[i] + u[i] * c[i];
+    template <bool TWO>
+    struct Operand { Raw x[TWO ? 2 : 1]; };      // X and X2 side by side: each product is rounded into the sum on its own, two fmas
+    template <bool TWO>
+    static __device__ __forceinline__ Operand<TWO> gather(const Raw* X, const Raw* X2, size_t at) {
+        Operand<TWO> o;
+        o.x[0] = X[at];
+        if (TWO) o.x[TWO ? 1 : 0] = X2[at];
+        return o;
     }
-    __builtin_nontemporal_store(pack8(c), ep.Cand + o);
-    __builtin_nontemporal_store(pack8(hn), ep.Hnew + o);
-}
+    template <bool TWO>
+    static __device__ __forceinline__ void accumulate(Acc& acc, float s, const Operand<TWO>& o) {
+        acc.fma(s, o.x[0]);
+        if (TWO) acc.fma(s, o.x[TWO ? 1 : 0]);
+    }
 
-template <int MODE>
-__device__ __forceinline__ void finish(const Epi& ep, size_t o, const Acc8& acc) {
-    float r[8];
-    if (MODE == EP_PLAIN) {
+    static __device__ __forceinline__ BlendIn blend_operands(const Epi& ep, size_t o) {
+        return BlendIn{stc_ld_once(ep.Y0 + o), stc_ld_once(ep.U + o), stc_ld_once(ep.H + o)};
+    }
+    template <bool ROW_BLOCK>
+    static __device__ __forceinline__ void blend(const Epi& ep, size_t rowg, int F8, int ch, const Acc& acc, const BlendIn& in) {
+        const size_t o = rowg * F8 + ch;
+        float a[8], u[8], h[8], c[8], hn[8];
+        unpack8(in.a, a); unpack8(in.u, u); unpack8(in.h, h);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) r[i] = ep.alpha * acc.v[i];
-        if (ep.beta != 0.f) {
-            float y0[8];
-            unpack8(__builtin_nontemporal_load(ep.Y0 + o), y0);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) r[i] = fmaf(ep.beta, y0[i], r[i]);
+        for (int i = 0; i < 8; ++i) {
+            c[i] = tanh_fast(acc.v[i] + a[i]);
+            hn[i] = (1.f - u[i]) * h[i] + u[i] * c[i];
         }
-        __builtin_nontemporal_store(pack8(r), ep.Y + o);
-        return;
+        stc_st_once(ep.Cand + o, pack8_raw(c));
+        stc_st_once(ep.Hnew + o, pack8_raw(hn));
     }
-    // SUM / SUM2
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r[i] = acc.v[i];
-    for (int k = 0; k < ep.n_add; ++k) {
-        float t[8];
-        unpack8(__builtin_nontemporal_load(ep.add[k] + o), t);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r[i] += t[i];
-    }
-    __builtin_nontemporal_store(pack8(r), ep.Y + o);
-    if (ep.dY) {
-        float u[8], c[8];
-        unpack8(__builtin_nontemporal_load(ep.U + o), u); unpack8(__builtin_nontemporal_load(ep.gCand + o), c);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r[i] = r[i] * u[i] * (1.f - c[i] * c[i]);
-        __builtin_nontemporal_store(pack8(r), ep.dY + o);
-    }
-}
 
-// ---- CSR: one wave per output row (learned dense graphs, graphs without a row-block plan)
-template <int VPT, int MODE>
-__global__ __launch_bounds__(SPMM_THREADS) void spmm_wave_row_bf16_kernel(
-    const int* __restrict__ rowptr, const int* __restrict__ colidx, const float* __restrict__ val,
-    int n_rows, int n_cols, const u32x4* __restrict__ X, int F8, int n_tiles, Epi ep) {
-    __shared__ int s_rp[SPMM_ROWS + 1];
-    __shared__ int s_col[SPMM_SEG_CAP];
-    __shared__ float s_val[SPMM_SEG_CAP];
-
-    const int tile = stc_xcd_tile(blockIdx.x, n_tiles);
-    if (tile < 0) return;                       // whole workgroup leaves together
-    const int b = blockIdx.y;
-    const int row0 = tile * SPMM_ROWS;
-    const int nr = min(SPMM_ROWS, n_rows - row0);
-    if ((int)threadIdx.x <= nr) s_rp[threadIdx.x] = rowptr[row0 + threadIdx.x];
-    __syncthreads();
-    const int seg0 = s_rp[0];
-    const int seg_n = min(s_rp[nr] - seg0, SPMM_SEG_CAP);
-    for (int t = threadIdx.x; t < seg_n; t += SPMM_THREADS) {
-        s_col[t] = colidx[seg0 + t];
-        s_val[t] = val[seg0 + t];
-    }
-    __syncthreads();
-
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const u32x4* Xb = X + (size_t)b * n_cols * F8;
-    const u32x4* X2b = MODE == EP_SUM2 ? ep.X2 + (size_t)b * n_cols * F8 : nullptr;
-    const u32x4 zero = {0u, 0u, 0u, 0u};
-
-    for (int r = wave; r < nr; r += SPMM_WAVES) {
-        const int js = s_rp[r] - seg0, je = s_rp[r + 1] - seg0;
-        const size_t rowg = (size_t)b * n_rows + row0 + r;
-        for (int cb = 0; cb < F8; cb += 64 * VPT) {
-            Acc8 acc[VPT];
+    template <int MODE>      // EP_PLAIN, EP_SUM, EP_SUM2
+    static __device__ __forceinline__ void finish(const Epi& ep, size_t rowg, int F8, int ch, const Acc& acc, float&) {
+        const size_t o = rowg * F8 + ch;
+        float r[8];
+        if (MODE == EP_PLAIN) {
 #pragma unroll
-            for (int p = 0; p < VPT; ++p) acc[p].zero();
-            BlendIn bin[VPT];
-            if (MODE == EP_BLEND) {
+            for (int i = 0; i < 8; ++i) r[i] = ep.alpha * acc.v[i];
+            if (ep.beta != 0.f) {
+                float y0[8];
+                unpack8(stc_ld_once(ep.Y0 + o), y0);
 #pragma unroll
-                for (int p = 0; p < VPT; ++p) {
-                    const int ch = cb + lane + 64 * p;
-                    if (ch < F8) {
-                        const size_t o = rowg * F8 + ch;
-                        bin[p].a = __builtin_nontemporal_load(ep.Y0 + o); bin[p].u = __builtin_nontemporal_load(ep.U + o); bin[p].h = __builtin_nontemporal_load(ep.H + o);
-                    }
-                }
+                for (int i = 0; i < 8; ++i) r[i] = fmaf(ep.beta, y0[i], r[i]);
             }
-            auto entry = [&](int j, int& c, float& v) {
-                if (j < SPMM_SEG_CAP) { c = s_col[j]; v = s_val[j]; }
-                else { c = colidx[seg0 + j]; v = val[seg0 + j]; }      // rows longer than the staged segment
-                c = __builtin_amdgcn_readfirstlane(c);
-                v = uniform_f(v);
-            };
-            int j = js;
-            for (; j + 4 <= je; j += 4) {
-                int c[4];
-                float v[4];
+            stc_st_once(ep.Y + o, pack8_raw(r));
+            return;
+        }
 #pragma unroll
-                for (int u = 0; u < 4; ++u) entry(j + u, c[u], v[u]);
-                u32x4 x[4][VPT], x2[MODE == EP_SUM2 ? 4 : 1][VPT];
+        for (int i = 0; i < 8; ++i) r[i] = acc.v[i];
+        for (int k = 0; k < ep.n_add; ++k) {
+            float t[8];
+            unpack8(stc_ld_once(ep.add[k] + o), t);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const u32x4* xr = Xb + (size_t)c[u] * F8;
+            for (int i = 0; i < 8; ++i) r[i] += t[i];
+        }
+        stc_st_once(ep.Y + o, pack8_raw(r));
+        if (ep.dY) {
+            float u[8], c[8];
+            unpack8(stc_ld_once(ep.U + o), u); unpack8(stc_ld_once(ep.gCand + o), c);
 #pragma unroll
-                    for (int p = 0; p < VPT; ++p) {
-                        const int ch = cb + lane + 64 * p;
-                        x[u][p] = ch < F8 ? xr[ch] : zero;
-                        if (MODE == EP_SUM2) x2[MODE == EP_SUM2 ? u : 0][p] = ch < F8 ? (X2b + (size_t)c[u] * F8)[ch] : zero;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int p = 0; p < VPT; ++p) {
-                        acc[p].fma(v[u], x[u][p]);
-                        if (MODE == EP_SUM2) acc[p].fma(v[u], x2[MODE == EP_SUM2 ? u : 0][p]);
-                    }
-            }
-            for (; j < je; ++j) {
-                int c;
-                float v;
-                entry(j, c, v);
-                const u32x4* xr = Xb + (size_t)c * F8;
-#pragma unroll
-                for (int p = 0; p < VPT; ++p) {
-                    const int ch = cb + lane + 64 * p;
-                    if (ch < F8) {
-                        acc[p].fma(v, xr[ch]);
-                        if (MODE == EP_SUM2) acc[p].fma(v, (X2b + (size_t)c * F8)[ch]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int p = 0; p < VPT; ++p) {
-                const int ch = cb + lane + 64 * p;
-                if (ch < F8) {
-                    if (MODE == EP_BLEND) blend_piece(ep, rowg * F8 + ch, acc[p], bin[p]);
-                    else finish<MODE>(ep, rowg * F8 + ch, acc[p]);
-                }
-            }
+            for (int i = 0; i < 8; ++i) r[i] = r[i] * u[i] * (1.f - c[i] * c[i]);
+            stc_st_once(ep.dY + o, pack8_raw(r));
         }
     }
-}
-
-// ---- row-blocked (BCSR 4x1): one wave (pair) produces 4 consecutive output rows, each distinct neighbour row fetched once
-// BC_BLOCKS row blocks per workgroup: 2 (two waves share a block and split its column blocks of 64*VPT pieces) or, for rows
-// of at most 64 pieces (state planes at C = 32: 1 KiB), 4 (one wave per block) -- otherwise half the waves would idle.
-template <int VPT, int MODE, int BC_BLOCKS>
-__global__ __launch_bounds__(SPMM_THREADS) void spmm_bcsr_bf16_kernel(
-    const int* __restrict__ blk_ptr, const int* __restrict__ blk_cols, const float* __restrict__ blk_vals,
-    int n_rows, int n_cols, const u32x4* __restrict__ X, int F8, int n_blocks, int n_tiles, Epi ep) {
-    __shared__ int s_bp[BC_BLOCKS + 1];
-    __shared__ int s_col[BC_CAP];
-    __shared__ float s_val[BC_CAP * BR];
-
-    const int tile = stc_xcd_tile(blockIdx.x, n_tiles);
-    if (tile < 0) return;
-    const int b = blockIdx.y;
-    const int blk0 = tile * BC_BLOCKS;
-    const int nb = min(BC_BLOCKS, n_blocks - blk0);
-    if ((int)threadIdx.x <= nb) s_bp[threadIdx.x] = blk_ptr[blk0 + threadIdx.x];
-    __syncthreads();
-    const int seg0 = s_bp[0];
-    const int seg_n = min(s_bp[nb] - seg0, BC_CAP);
-    for (int t = threadIdx.x; t < seg_n; t += SPMM_THREADS) s_col[t] = blk_cols[seg0 + t];
-    for (int t = threadIdx.x; t < seg_n * BR; t += SPMM_THREADS) s_val[t] = blk_vals[(size_t)seg0 * BR + t];
-    __syncthreads();
-
-    constexpr int WPB = SPMM_WAVES / BC_BLOCKS;      // waves sharing one row block
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const u32x4* Xb = X + (size_t)b * n_cols * F8;
-    const u32x4* X2b = MODE == EP_SUM2 ? ep.X2 + (size_t)b * n_cols * F8 : nullptr;
-    const u32x4 zero = {0u, 0u, 0u, 0u};
-
-    for (int bi = wave / WPB; bi < nb; bi += SPMM_WAVES / WPB) {
-        const int js = s_bp[bi] - seg0, je = s_bp[bi + 1] - seg0;
-        const int row_base = (blk0 + bi) * BR;
-        const int rows_here = min(BR, n_rows - row_base);
-        for (int cb = (wave % WPB) * 64 * VPT; cb < F8; cb += WPB * 64 * VPT) {
-            Acc8 acc[BR][VPT];
-#pragma unroll
-            for (int r = 0; r < BR; ++r)
-#pragma unroll
-                for (int p = 0; p < VPT; ++p) acc[r][p].zero();
-            BlendIn bin[MODE == EP_BLEND ? BR : 1][VPT];
-            if (MODE == EP_BLEND) {
-#pragma unroll
-                for (int r = 0; r < BR; ++r)
-#pragma unroll
-                    for (int p = 0; p < VPT; ++p) {
-                        const int ch = cb + lane + 64 * p;
-                        if (r < rows_here && ch < F8) {
-                            const size_t o = ((size_t)b * n_rows + row_base + r) * F8 + ch;
-                            BlendIn& t = bin[MODE == EP_BLEND ? r : 0][p];
-                            t.a = __builtin_nontemporal_load(ep.Y0 + o); t.u = __builtin_nontemporal_load(ep.U + o); t.h = __builtin_nontemporal_load(ep.H + o);
-                        }
-                    }
-            }
-            auto entry = [&](int j, int& c, float (&v)[BR]) {
-                if (j < BC_CAP) {
-                    c = s_col[j];
-#pragma unroll
-                    for (int r = 0; r < BR; ++r) v[r] = s_val[j * BR + r];
-                } else {                       // block lists longer than the staged segment
-                    c = blk_cols[seg0 + j];
-#pragma unroll
-                    for (int r = 0; r < BR; ++r) v[r] = blk_vals[(size_t)(seg0 + j) * BR + r];
-                }
-                c = __builtin_amdgcn_readfirstlane(c);
-#pragma unroll
-                for (int r = 0; r < BR; ++r) v[r] = uniform_f(v[r]);
-            };
-            int j = js;
-            for (; j + 4 <= je; j += 4) {
-                int c[4];
-                float v[4][BR];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) entry(j + u, c[u], v[u]);
-                u32x4 x[4][VPT], x2[MODE == EP_SUM2 ? 4 : 1][VPT];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const u32x4* xr = Xb + (size_t)c[u] * F8;
-#pragma unroll
-                    for (int p = 0; p < VPT; ++p) {
-                        const int ch = cb + lane + 64 * p;
-                        x[u][p] = ch < F8 ? xr[ch] : zero;
-                        if (MODE == EP_SUM2) x2[MODE == EP_SUM2 ? u : 0][p] = ch < F8 ? (X2b + (size_t)c[u] * F8)[ch] : zero;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int r = 0; r < BR; ++r)
-#pragma unroll
-                        for (int p = 0; p < VPT; ++p) {
-                            acc[r][p].fma(v[u][r], x[u][p]);
-                            if (MODE == EP_SUM2) acc[r][p].fma(v[u][r], x2[MODE == EP_SUM2 ? u : 0][p]);
-                        }
-            }
-            for (; j < je; ++j) {
-                int c;
-                float v[BR];
-                entry(j, c, v);
-                const u32x4* xr = Xb + (size_t)c * F8;
-#pragma unroll
-                for (int p = 0; p < VPT; ++p) {
-                    const int ch = cb + lane + 64 * p;
-                    if (ch < F8) {
-                        const u32x4 xv = xr[ch];
-#pragma unroll
-                        for (int r = 0; r < BR; ++r) acc[r][p].fma(v[r], xv);
-                        if (MODE == EP_SUM2) {
-                            const u32x4 xw = (X2b + (size_t)c * F8)[ch];
-#pragma unroll
-                            for (int r = 0; r < BR; ++r) acc[r][p].fma(v[r], xw);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < BR; ++r) {
-                if (r < rows_here) {
-                    const size_t rowg = (size_t)b * n_rows + row_base + r;
-#pragma unroll
-                    for (int p = 0; p < VPT; ++p) {
-                        const int ch = cb + lane + 64 * p;
-                        if (ch < F8) {
-                            if (MODE == EP_BLEND) blend_piece(ep, rowg * F8 + ch, acc[r][p], bin[MODE == EP_BLEND ? r : 0][p]);
-                            else finish<MODE>(ep, rowg * F8 + ch, acc[r][p]);
-                        }
-                    }
-                }
-            }
-        }
-    }
-}
-
-template <int MODE>
-int launch(const char* who, const GraphArgs& g, int n_rows, int n_cols, const void* X, int batch, int F, const Epi& ep, hipStream_t s) {
-    const u32x4* X8 = reinterpret_cast<const u32x4*>(X);
-    const int F8 = F / 8;
-    if (g.blk_ptr) {
-        const int n_blocks = (n_rows + BR - 1) / BR;
-        const int blocks = F8 <= 64 ? 4 : 2;
-        const int n_tiles = (n_blocks + blocks - 1) / blocks;
-        const int per = (n_tiles + stc::kNumXcd - 1) / stc::kNumXcd;
-        const dim3 grid(per * stc::kNumXcd, batch), block(SPMM_THREADS);
-        if (F8 <= 64)         // one wave per row block
-            hipLaunchKernelGGL((spmm_bcsr_bf16_kernel<1, MODE, 4>), grid, block, 0, s, g.blk_ptr, g.blk_cols, g.blk_vals, n_rows, n_cols, X8, F8, n_blocks, n_tiles, ep);
-        else if (F8 <= 128)   // two waves per block: each covers every other column block of 64*VPT pieces
-            hipLaunchKernelGGL((spmm_bcsr_bf16_kernel<1, MODE, 2>), grid, block, 0, s, g.blk_ptr, g.blk_cols, g.blk_vals, n_rows, n_cols, X8, F8, n_blocks, n_tiles, ep);
-        else
-            hipLaunchKernelGGL((spmm_bcsr_bf16_kernel<2, MODE, 2>), grid, block, 0, s, g.blk_ptr, g.blk_cols, g.blk_vals, n_rows, n_cols, X8, F8, n_blocks, n_tiles, ep);
-    } else {
-        const int n_tiles = (n_rows + SPMM_ROWS - 1) / SPMM_ROWS;
-        const int per = (n_tiles + stc::kNumXcd - 1) / stc::kNumXcd;
-        const dim3 grid(per * stc::kNumXcd, batch), block(SPMM_THREADS);
-        if (F8 <= 64)
-            hipLaunchKernelGGL((spmm_wave_row_bf16_kernel<1, MODE>), grid, block, 0, s, g.rowptr, g.colidx, g.val, n_rows, n_cols, X8, F8, n_tiles, ep);
-        else
-            hipLaunchKernelGGL((spmm_wave_row_bf16_kernel<2, MODE>), grid, block, 0, s, g.rowptr, g.colidx, g.val, n_rows, n_cols, X8, F8, n_tiles, ep);
-    }
-    return stc::launched(who);
-}
+    template <int MODE>
+    static __device__ __forceinline__ void wave_done(const Epi&, float) {}      // nothing is reduced over a launch
+};
 
 // the plain product on bf16 rows (16-byte pieces of 8 elements) on either graph form; its pointer array is checked last
 int plain_bf16(const char* who, const char* launch_who, const GraphArgs& g, const stc::Plain& p, float alpha, void* Y, void* stream) {
@@ -404,8 +115,8 @@ int plain_bf16(const char* who, const char* launch_who, const GraphArgs& g, cons
     if (int rc = stc::check_batch(who, p.batch)) return rc;
     STC_REQUIRE(g.rowptr || g.blk_ptr, STC_EINVAL, "%s: null rowptr / blk_ptr", who);      // colidx / val may be null for a graph without edges
     Epi ep{};
-    ep.Y0 = reinterpret_cast<const u32x4*>(p.Y0); ep.Y = reinterpret_cast<u32x4*>(Y); ep.alpha = alpha; ep.beta = p.beta;
-    return launch<EP_PLAIN>(launch_who, g, p.n_rows, p.n_cols, p.X, p.batch, p.F, ep, static_cast<hipStream_t>(stream));
+    ep.Y0 = reinterpret_cast<const Raw*>(p.Y0); ep.Y = reinterpret_cast<Raw*>(Y); ep.alpha = alpha; ep.beta = p.beta;
+    return launch_gather<EP_PLAIN, RowsBf16>(launch_who, g, p.n_rows, p.n_cols, p.X, p.batch, p.F / 8, ep, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace
@@ -439,10 +150,10 @@ extern "C" int stc_spmm_blend_fwd_bf16(const int32_t* rowptr, const int32_t* col
                 STC_EALIGN, "stc_spmm_blend_fwd_bf16: operands must be 16-byte aligned");
     STC_REQUIRE(Bm != Cand && Bm != Hnew, STC_EINVAL, "stc_spmm_blend_fwd_bf16: outputs must not alias Bm (its rows are gathered by other rows)");
     Epi ep{};
-    ep.Y0 = reinterpret_cast<const u32x4*>(A);
-    ep.U = reinterpret_cast<const u32x4*>(U); ep.H = reinterpret_cast<const u32x4*>(H);
-    ep.Cand = reinterpret_cast<u32x4*>(Cand); ep.Hnew = reinterpret_cast<u32x4*>(Hnew);
-    return launch<EP_BLEND>("stc_spmm_blend_fwd_bf16 launch", g, n_rows, n_cols, Bm, batch, C * h, ep, static_cast<hipStream_t>(stream));
+    ep.Y0 = reinterpret_cast<const Raw*>(A);
+    ep.U = reinterpret_cast<const Raw*>(U); ep.H = reinterpret_cast<const Raw*>(H);
+    ep.Cand = reinterpret_cast<Raw*>(Cand); ep.Hnew = reinterpret_cast<Raw*>(Hnew);
+    return launch_gather<EP_BLEND, RowsBf16>("stc_spmm_blend_fwd_bf16 launch", g, n_rows, n_cols, Bm, batch, C * h / 8, ep, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int stc_spmm_sum_bf16(const int32_t* rowptr, const int32_t* colidx, const float* val,
@@ -462,12 +173,12 @@ extern "C" int stc_spmm_sum_bf16(const int32_t* rowptr, const int32_t* colidx, c
     if (int rc = stc::check_dy("stc_spmm_sum_bf16", dY, U, Cand, Y)) return rc;
     if (int rc = stc::check_addends("stc_spmm_sum_bf16", "addend", add, n_add, Y, nullptr)) return rc;
     Epi ep{};
-    ep.Y = reinterpret_cast<u32x4*>(Y);
-    ep.X2 = reinterpret_cast<const u32x4*>(X2);
-    ep.U = reinterpret_cast<const u32x4*>(U); ep.gCand = reinterpret_cast<const u32x4*>(Cand); ep.dY = reinterpret_cast<u32x4*>(dY);
+    ep.Y = reinterpret_cast<Raw*>(Y);
+    ep.X2 = reinterpret_cast<const Raw*>(X2);
+    ep.U = reinterpret_cast<const Raw*>(U); ep.gCand = reinterpret_cast<const Raw*>(Cand); ep.dY = reinterpret_cast<Raw*>(dY);
     ep.n_add = n_add;
-    for (int i = 0; i < n_add; ++i) ep.add[i] = reinterpret_cast<const u32x4*>(add[i]);
+    for (int i = 0; i < n_add; ++i) ep.add[i] = reinterpret_cast<const Raw*>(add[i]);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return X2 ? launch<EP_SUM2>("stc_spmm_sum_bf16 launch", g, n_rows, n_cols, X, batch, C * h, ep, s)
-              : launch<EP_SUM>("stc_spmm_sum_bf16 launch", g, n_rows, n_cols, X, batch, C * h, ep, s);
+    return X2 ? launch_gather<EP_SUM2, RowsBf16>("stc_spmm_sum_bf16 launch", g, n_rows, n_cols, X, batch, C * h / 8, ep, s)
+              : launch_gather<EP_SUM, RowsBf16>("stc_spmm_sum_bf16 launch", g, n_rows, n_cols, X, batch, C * h / 8, ep, s);
 }

@@ -1,5 +1,5 @@
-// Internal: the host-side blocks that the C entry points of the spatial aggregation share (stc_spmm.hip and stc_spmm_bf16.hip: CSR / row-blocked
-// kernels on fp32 and bf16 rows; stc_spmm_patch.hip; stc_spmm_ring2.hip; stc_dense.hip).  Where fronts differ -- an element size, a divisibility
+// Internal: the host-side blocks that the C entry points of the spatial aggregation share (stc_spmm.hip and stc_spmm_bf16.hip: the CSR / row-blocked
+// kernels of stc_spmm_gather.h on fp32 and bf16 rows; stc_spmm_patch.hip; stc_spmm_ring2.hip; stc_dense.hip).  Where fronts differ -- an element size, a divisibility
 // rule, a status code, which pointers must be given -- the difference is an argument: it shows at the call site.  Plain checks on the
 // arguments, no allocation: a launch-bound step makes several hundred of these calls.
 #pragma once

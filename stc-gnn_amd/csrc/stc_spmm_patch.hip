@@ -15,6 +15,7 @@
 // bench's unit against 211 us row-blocked and 181 us for a plain copy of the same two planes).  The sum of a row runs over its
 // entries in CSR order with one fmaf each, from zero: bit for bit the row-blocked and the CSR kernels' result.
 #include "stc_spmm_host.h"
+#include "stc_spmm_piece.h"
 
 #include <type_traits>
 
@@ -27,70 +28,29 @@ constexpr int PT_SRC = STC_PATCH_MAX_SRC;        // source rows per patch (LDS: 
 constexpr int PT_Q = 64;                         // float4 pieces per chunk: one per lane
 constexpr int PT_PER = PT_SRC / PT_WAVES;        // source rows each wave requests per chunk
 
-using v4f = __attribute__((ext_vector_type(4))) float;
+using v4f = Raw;
 
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-
-// A 16-byte piece of a feature row and its fp32 sums: four floats, or eight bf16 (bf16 storage, BASELINE configuration 5: values widen to
-// fp32 exactly, products and sums in fp32, ONE rounding to bf16 at the store -- the contract of csrc/stc_spmm_bf16.hip, same fmaf chain).
-template <bool BF16>
-struct Piece;
-
-template <>
-struct Piece<false> {                                     // four floats (kept as ONE vector value: element arrays cost this kernel 16 registers)
-    v4f v;
-    __device__ __forceinline__ void zero() { v = v4f{0.f, 0.f, 0.f, 0.f}; }
-    __device__ __forceinline__ void fma(float s, const v4f x) {
+// alpha * sum (+ beta * y0) of a piece (stc_spmm_piece.h: four floats, or eight bf16 rounded ONCE here), as the piece to store
+template <bool HAS_Y0>
+__device__ __forceinline__ v4f finish(const Piece<false>& acc, float alpha, float beta, const v4f y0) {
+    v4f out;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] = fmaf(s, x[c], v[c]);
+    for (int c = 0; c < 4; ++c) out[c] = HAS_Y0 ? fmaf(beta, y0[c], alpha * acc.v[c]) : alpha * acc.v[c];
+    return out;
+}
+template <bool HAS_Y0>
+__device__ __forceinline__ v4f finish(const Piece<true>& acc, float alpha, float beta, const v4f y0) {
+    float r[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r[i] = alpha * acc.v[i];
+    if (HAS_Y0) {
+        float t[8];
+        unpack8(y0, t);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) r[i] = fmaf(beta, t[i], r[i]);
     }
-    template <bool HAS_Y0>                                // alpha * sum (+ beta * y0), as the piece to store
-    __device__ __forceinline__ v4f finish(float alpha, float beta, const v4f y0) const {
-        v4f out;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) out[c] = HAS_Y0 ? fmaf(beta, y0[c], alpha * v[c]) : alpha * v[c];
-        return out;
-    }
-};
-
-template <>
-struct Piece<true> {                                      // eight bf16 columns, summed in fp32
-    float v[8];
-    __device__ __forceinline__ void zero() {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = 0.f;
-    }
-    __device__ __forceinline__ void fma(float s, const v4f x) {
-        const u32x4 u = __builtin_bit_cast(u32x4, x);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = fmaf(s, __uint_as_float(u[i] << 16), v[2 * i]);
-            v[2 * i + 1] = fmaf(s, __uint_as_float(u[i] & 0xffff0000u), v[2 * i + 1]);
-        }
-    }
-    template <bool HAS_Y0>
-    __device__ __forceinline__ v4f finish(float alpha, float beta, const v4f y0) const {
-        float r[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r[i] = alpha * v[i];
-        if (HAS_Y0) {
-            const u32x4 u = __builtin_bit_cast(u32x4, y0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                r[2 * i] = fmaf(beta, __uint_as_float(u[i] << 16), r[2 * i]);
-                r[2 * i + 1] = fmaf(beta, __uint_as_float(u[i] & 0xffff0000u), r[2 * i + 1]);
-            }
-        }
-        u32x4 o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bf16x2 t = {(__bf16)r[2 * i], (__bf16)r[2 * i + 1]};           // v_cvt_pk_bf16_f32, round to nearest even
-            o[i] = __builtin_bit_cast(unsigned, t);
-        }
-        return __builtin_bit_cast(v4f, o);
-    }
-};
+    return pack8_raw(r);
+}
 
 struct PatchPlan {
     const int32_t *src, *rows, *cnt;
@@ -205,7 +165,7 @@ __global__ __launch_bounds__(PT_THREADS, 2) void spmm_patch_kernel(PatchPlan pl,
                 acc.fma(v, *reinterpret_cast<const v4f*>(tile + off));
             }
             if (__builtin_amdgcn_readlane(v_cnt, i) == 0) acc.zero();                          // a row without entries sums nothing
-            __builtin_nontemporal_store(acc.template finish<HAS_Y0>(alpha, beta, y0[HAS_Y0 ? i : 0]), row < 0 ? patch_dump + lane : Y + o);
+            __builtin_nontemporal_store(finish<HAS_Y0>(acc, alpha, beta, y0[HAS_Y0 ? i : 0]), row < 0 ? patch_dump + lane : Y + o);
         }
     };
     constexpr std::true_type more{};

@@ -3,19 +3,13 @@
 // six piece products of weight >= 2^-16 on v_mfma_f32_16x16x32_bf16 (see the header of stc_node_x3.hip for the layouts).
 #pragma once
 #include "stc_node_frag.h"
+#include "stc_spmm_piece.h"      // pk_bf16 (v_cvt_pk_bf16_f32: a in the low half)
 
 namespace {
 
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 struct X3 { u32x4 h, m, l; };       // 8 fp32 values as three bf16x8 pieces
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {     // v_cvt_pk_bf16_f32: a in the low half
-    const bf16x2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
 
 // a - (low half of pk as a float) and a - (high half): ONE v_dot2c_f32_bf16 each (a + pk.lo * -1 + pk.hi * 0) instead of shift / mask +
 // subtract.  The products and the sum are exact in fp32 (the remainder of a bf16 rounding is representable), so the pieces are the same

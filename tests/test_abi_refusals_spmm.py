@@ -5,8 +5,8 @@ code and ``stc_last_error()``.  Pointers are addresses inside a host buffer and 
 (and the fp32 sum's ld / off arrays) are read.  The empty launch is in the table too: it returns STC_OK without a launch.
 
 The 15 entry points: plain products (csrc/stc_spmm.hip, stc_spmm_bf16.hip, stc_spmm_patch.hip, stc_dense.hip), the sampled product, and
-the state-row forms with their blend / sum epilogues (stc_spmm.hip, stc_spmm_bf16.hip) and two-ring launches (stc_spmm_ring2.hip).  Where
-fronts answer one fault with different codes the table records each as it is: too many addends is STC_EINVAL on stc_spmm_sum_* and
+the state-row forms with their blend / sum epilogues (stc_spmm.hip, stc_spmm_bf16.hip: both launch the kernels of stc_spmm_gather.h) and two-ring
+launches (stc_spmm_ring2.hip).  Where fronts answer one fault with different codes the table records each as it is: too many addends is STC_EINVAL on stc_spmm_sum_* and
 STC_ELIMIT on stc_ring2_*; a batch above 65535 is STC_ELIMIT everywhere but STC_EINVAL on stc_ring2_*; fewer than one category is
 STC_EINVAL on the row-blocked fronts and STC_EUNSUPPORTED on stc_ring2_*; n_cols == 0 with rows to produce is refused by the CSR, bf16 and
 state-row fronts only.  Not in the table, because they are no refusals: stc_csr_spmm_f32 with a misaligned operand or F % 4 != 0 (it

@@ -368,7 +368,8 @@ def test_cell_backward_in_one_launch_bf16(hip, nodes, C, cin):
     assert torch.isnan(outs[1][2]).all()
 
 
-@pytest.mark.parametrize('batch,grid,C,n_add,dual', [(2, (5, 5), 32, 3, True), (1, (4, 7), 64, 5, False), (2, (40, 56), 64, 0, True), (1, (1, 1), 32, 2, False)])
+@pytest.mark.parametrize('batch,grid,C,n_add,dual', [(2, (5, 5), 32, 3, True), (1, (4, 7), 64, 5, False), (2, (40, 56), 64, 0, True), (1, (1, 1), 32, 2, False),
+                                                     (2, (5, 5), 80, 3, True), (2, (5, 5), 80, 1, False)])      # C = 80: rows of 160 pieces, the widest arm of the launch ladder
 def test_state_aggregations_bf16(hip, batch, grid, C, n_add, dual):
     """stc_spmm_sum_bf16 (gradient of a state from its pieces, optional blend backward), stc_spmm_blend_fwd_bf16 (Y = A + S.Bm
     with the GRU blend) and stc_gru_blend_bwd_bf16, row-blocked and plain CSR, against the fp32 twins on the same inputs."""

@@ -380,8 +380,8 @@ for dt, tag, tol in ((torch.float32, 'f32', TOL), (torch.bfloat16, 'bf16', BTOL)
     for n, F, B, beta, inplace in ((37, 64, 2, 0.0, False), (203, 1024, 1, -1.0, True), (77, 16, 2, -1.0, False), (30, 2048, 1, 0.0, False)):
         case(f'bcsr_spmm_{tag}-n{n}-F{F}-beta{beta}{"-inplace" if inplace else ""}', {f'stc_bcsr_spmm_{tag}'},
              *_spmm_plan(lambda n=n, F=F: _banded_matrix(n, 4, n + F), F, B, beta, dt, inplace), tol=tol, cpu=(n == 37 and tag == 'f32'))
-    # every arm of the row-blocked ladders (csrc/stc_spmm.hip launch_vector: float4 per lane 1 / 2 / 4, pipelined gather for beta = 0 and whole
-    # column blocks, old loop otherwise; csrc/stc_spmm_bf16.hip launch: rows of <= 512, <= 1024, more columns), at the smallest shape with a ragged block
+    # every arm of the row-blocked ladder (csrc/stc_spmm_gather.h launch_gather.  fp32 rows: float4 per lane 1 / 2 / 4, pipelined gather for beta = 0 and
+    # whole column blocks, old loop otherwise; bf16 rows of <= 512, <= 1024, more columns), at the smallest shape with a ragged block
     for F, beta in ((512, 0.0), (320, 0.0), (1024, 0.0), (1280, -1.0)) if tag == 'f32' else ((512, 0.0), (1024, 0.0), (2048, 0.0)):
         case(f'bcsr_spmm_{tag}-n37-F{F}-beta{beta}-ladder', {f'stc_bcsr_spmm_{tag}'},
              *_spmm_plan(lambda F=F: _banded_matrix(37, 4, 37 + F), F, 2, beta, dt, False), tol=tol)
@@ -478,7 +478,7 @@ def _copy_checks(names_cols):
     return check
 
 
-def _spmm_blend(H, W, B, C, dt, copies):
+def _spmm_blend(H, W, B, C, dt, copies, blocked=True):
     h = 16
 
     def make():
@@ -500,7 +500,7 @@ def _spmm_blend(H, W, B, C, dt, copies):
             kw = dict(copies=[(t.c0, 16), (t.c1, 0)])
         if copies == 'side':
             kw = dict(copies=[(t.c0, 1)], side=t.side)
-        (k if dt == torch.float32 else k.bf16).spmm_blend_fwd(op.fwd_rowptr, op.fwd_colidx, op.fwd_val, op.fwd_plan[:3], t.Bm, t.A, t.U, t.Hp, t.Cand, t.Hnew, **kw)
+        (k if dt == torch.float32 else k.bf16).spmm_blend_fwd(op.fwd_rowptr, op.fwd_colidx, op.fwd_val, op.fwd_plan[:3] if blocked else None, t.Bm, t.A, t.U, t.Hp, t.Cand, t.Hnew, **kw)
     # side: columns [0, 1) from side, [1, 17) the state, pad [17, 20) zeroed -- the launch owns the whole row
     check = _copy_checks({'c0': range(16, 32), 'c1': range(0, 16)}) if copies == 'pair' else None
     return dict(make=make, call=call, check=check)
@@ -508,6 +508,10 @@ def _spmm_blend(H, W, B, C, dt, copies):
 
 for H, W, B, C, copies in ((5, 5, 2, 32, 'pair'), (4, 7, 3, 32, 'side'), (3, 3, 1, 64, None), (1, 1, 1, 32, None), (9, 33, 1, 32, 'pair')):
     case(f'spmm_blend_f32-{H}x{W}-C{C}-{copies}', {'stc_spmm_blend_fwd_f32'}, **_spmm_blend(H, W, B, C, torch.float32, copies), cpu=(H == 4))
+# the other pieces-per-lane arms of the launch ladder: rows of 320 float4 (C = 80, the widest) on the row-blocked kernel, and 320, 256, 128 and 64 on
+# the wave-per-row kernel (no row-block plan)
+for C, blocked in ((80, True), (80, False), (64, False), (32, False), (16, False)):
+    case(f'spmm_blend_f32-5x5-C{C}-{"blocked" if blocked else "csr"}', {'stc_spmm_blend_fwd_f32'}, **_spmm_blend(5, 5, 2, C, torch.float32, None, blocked))
 for H, W, B, C in ((5, 5, 2, 32), (4, 7, 1, 64), (1, 1, 1, 32)):
     case(f'spmm_blend_bf16-{H}x{W}-C{C}', {'stc_spmm_blend_fwd_bf16'}, **_spmm_blend(H, W, B, C, torch.bfloat16, None), tol=BTOL)
 case('spmm_blend_f32-4x7-C128-None', {'stc_spmm_blend_fwd_f32'}, **_spmm_blend(4, 7, 1, 128, torch.float32, None))          # C = 128: the widest arm

@@ -609,7 +609,11 @@ def test_cell_backward_in_one_launch(hip, nodes, cin, bias):
         assert torch.isnan(outs[1][2]).all()
 
 
-@pytest.mark.parametrize('batch,grid,C,n_add,dual', [(2, (5, 5), 32, 3, True), (1, (4, 7), 64, 5, False), (2, (40, 56), 32, 0, True), (1, (1, 1), 32, 2, False)])
+@pytest.mark.parametrize('batch,grid,C,n_add,dual', [(2, (5, 5), 32, 3, True), (1, (4, 7), 64, 5, False), (2, (40, 56), 32, 0, True), (1, (1, 1), 32, 2, False),
+                                                     # every pieces-per-lane arm of the launch ladder with one and with two gathered operands: rows of
+                                                     # C * 4 float4 = 64 (C = 16), 128 (C = 32, above), 256 (C = 64), 320 (C = 80)
+                                                     (2, (5, 5), 16, 3, True), (2, (5, 5), 16, 1, False), (1, (4, 7), 64, 2, True),
+                                                     (2, (5, 5), 80, 3, True), (2, (5, 5), 80, 1, False)])
 def test_state_gradient_from_pieces(hip, batch, grid, C, n_add, dual):
     """stc_spmm_sum_f32: Y = sum of addends (contiguous planes and column slices of wider rows) + S.(X [+ X2])."""
     h = 16
