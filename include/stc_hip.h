@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define STC_ABI_VERSION 40
+#define STC_ABI_VERSION 41
 #define STC_MAX_K 4          /* highest Chebyshev order (Ks, Kc) the node kernels accept */
 
 /* Operand formats of the split-operand matrix-core kernels (C = 32 / 64, hidden 16).  Every fp32 operand is split into low-precision
@@ -93,6 +93,9 @@ int stc_set_dispatch_level(int32_t level);
  *        stc_mixed_fusion_lr_fwd/bwd_f32:  no masking either; the result is non-finite wherever float64 torch operations on the same operands
  *          are: a NaN in A reaches every entry of G through t_A, a NaN in one row of U_A only that row of gate and G; sigmoid(+-Inf) stays
  *          1 / 0 [tests/test_mixed_fusion_lr.py test_non_finite_values_are_handed_on].
+ *        stc_mgp_csr_score_f32, stc_mgp_csr_softmax_fwd/bwd_f32, stc_mgp_csr_score_bwd_f32:  no masking; a NaN in u_i reaches the entries of
+ *          row i and column i only (and through the row softmax the rows that hold them), a NaN score stays NaN and passes the backward mask
+ *          [tests/test_mgp_csr.py test_non_finite_values_are_handed_on].
  *        node kernels (stc_bdg_node_*, stc_bdg_node_post_*), fused and planar cell kernels, all dispatch levels and both operand
  *          formats:  the node.  In the backward the pad columns [Lw, L) of THAT node's slab gradients come out non-finite where the
  *          math has zeros [test_contract_on_the_node_kernels, test_contract_on_the_fused_cell_kernels,
@@ -812,6 +815,36 @@ int stc_mgp_uv_bwd_f32(const float* X, int64_t k_stride, int64_t r_stride, int64
                        const float* dU, const float* dV, float alpha, float* partials, int32_t K, int32_t R, int32_t F, int32_t h, void* stream);
 int stc_mgp_softmax_fwd_f32(const float* P, float* Ps, int32_t R, void* stream);
 int stc_mgp_softmax_bwd_f32(const float* P, const float* Ps, const float* dPs, float* rowdot, float* dP, int32_t R, void* stream);
+/* ---- the learned spatial graph on a sparsity pattern (ABI v41; csrc/stc_mgp_csr.hip; graph_mode='csr-learned') -------------------------------
+ * The generator above restricted to the stored entries of the prior graph Gs.  U, V (R, KH): the (R, K, h) results of stc_mgp_uv_fwd_f32 read
+ * as one row of KH = K h floats per node.  rowptr (R + 1) / colidx (nnz): CSR of Gs ITSELF, entry e = (i, j) in row i; every per-entry vector
+ * (score, Ps, dPs, ds) has nnz floats in that order.  t_rowptr / t_colidx: CSR of Gs^T, whose entry f is entry t_entry[f] of Gs.
+ *     score_e = <u_i, v_j> - <v_i, u_j>                                        (what P - P^T of the dense form holds at e)
+ *     Ps_e    = exp(relu(score_e) - m_i) / sum_{e' in row i} exp(relu(score_e') - m_i)      softmax over the row's STORED entries; an entry
+ *                                                                              whose relu is 0 still adds exp(0 - m_i); an empty row produces nothing
+ *     ds_e    = [score_e > 0] Ps_e (dPs_e - sum_{row i} Ps dPs)                (a NaN score passes the mask)
+ *     dU_i    = sum_{e=(i,j)} ds_e v_j - sum_{e=(j,i)} ds_e v_j;    dV_i = -sum_{e=(i,j)} ds_e u_j + sum_{e=(j,i)} ds_e u_j
+ * On the full pattern this is softmax(relu(P - P^T), -1) of the dense entry points, row-major.  One launch each, one wave per row:
+ *   stc_mgp_csr_score_f32        16-byte loads; a row's own u_i, v_i are read once per row; the two dot products are accumulated by the same chain of
+ *                                operations, so a diagonal entry and an entry between two nodes with identical rows score exactly 0.0
+ *   stc_mgp_csr_softmax_fwd_f32  relu and max as torch has them (a NaN stays NaN); Ps must not alias score
+ *   stc_mgp_csr_softmax_bwd_f32  ds must not alias an input
+ *   stc_mgp_csr_score_bwd_f32    gathered per destination row over both orientations: every element of dU, dV (R, KH) is written once (zeros
+ *                                for a node without entries), no atomics; dU, dV must not alias an input or each other
+ * Bitwise reproducible from run to run and between eager launches and HIP-graph replays.  Accepted (stc_mgp_csr_supported): R >= 1, nnz >= 0,
+ * KH a multiple of 4 in [4, STC_MGP_CSR_MAX_KH] (STC_EUNSUPPORTED outside: 16-byte pieces, and the score kernel keeps 32 KH bytes of LDS per
+ * workgroup), R KH < 2^31 (STC_ELIMIT; R, nnz and the elements of U / V are counted in int32, offsets are formed in 64 bits).  Negative sizes:
+ * STC_EINVAL.  R = 0, or nnz = 0 where only per-entry vectors are written, launches nothing.  U, V, dU, dV 16-byte aligned, everything else
+ * 4-byte.  The index arrays are trusted (graph.CsrGraph validates them on the host). */
+#define STC_MGP_CSR_MAX_KH 4096
+int stc_mgp_csr_supported(int32_t R, int32_t KH, int32_t nnz);
+int stc_mgp_csr_score_f32(const float* U, const float* V, const int32_t* rowptr, const int32_t* colidx, float* score, int32_t R, int32_t KH, int32_t nnz,
+                          void* stream);
+int stc_mgp_csr_softmax_fwd_f32(const float* score, const int32_t* rowptr, float* Ps, int32_t R, int32_t nnz, void* stream);
+int stc_mgp_csr_softmax_bwd_f32(const float* score, const float* Ps, const float* dPs, const int32_t* rowptr, float* ds, int32_t R, int32_t nnz,
+                                void* stream);
+int stc_mgp_csr_score_bwd_f32(const float* U, const float* V, const float* ds, const int32_t* rowptr, const int32_t* colidx, const int32_t* t_rowptr,
+                              const int32_t* t_colidx, const int32_t* t_entry, float* dU, float* dV, int32_t R, int32_t KH, int32_t nnz, void* stream);
 /* Adam on one large fp32 parameter (csrc/stc_adam.hip; ABI v29; the optimizer of the reference's harness step, Model_Trainer.py:71-87: torch.optim.Adam with
  * L2 weight decay, no amsgrad), one streaming launch: the two MixedFusion matrices above are 2 x 400 MB at the SF shape.
  *     g' = g + weight_decay p;   m = m + (1 - beta1)(g' - m);   v = beta2 v + (1 - beta2) g'^2

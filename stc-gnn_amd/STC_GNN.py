@@ -19,6 +19,9 @@ Beyond the reference:
 * ``STCGNN(..., graph_mode='csr-fixed')`` skips ``MGP_Gen`` (whose
   ``MixedFusion`` holds 2*N^4 parameters and cannot exist beyond N ~ 300) and
   uses ``As`` / ``Ac`` directly as ``Gs`` / ``Gc``.
+* ``STCGNN(..., graph_mode='csr-learned', spatial_graph=As, fusion_rank=r)`` learns
+  ``Gs`` on the stored entries of the sparse prior graph (``MGP_Gen_Csr``: any N,
+  rank-r fusion over nnz); in grad mode its cells run one autograd node per cell.
 
 Inputs must live on a ROCm device; there is no CPU execution path.
 """
@@ -29,8 +32,8 @@ from typing import List, Optional, Sequence, Union
 import torch
 from torch import nn
 
-from stc_hip import fusion, ops
-from stc_hip.graph import CsrGraph, SpatialOperand, csr_operand, dense_operand
+from stc_hip import fusion, learned, ops
+from stc_hip.graph import CsrGraph, SpatialOperand, csr_operand, csr_pattern, dense_operand, learned_csr_operand
 
 GraphLike = Union[torch.Tensor, CsrGraph, 'GraphPair']
 
@@ -43,8 +46,10 @@ class GraphPair:
     """
 
     def __init__(self, Gs, Gc: torch.Tensor, Ks: int, Kc: int):
-        if isinstance(Gs, CsrGraph):
-            self.spatial: SpatialOperand = csr_operand(Gs, Gc.device)
+        if isinstance(Gs, SpatialOperand):                               # prepared by the caller (csr-learned: learned values on a fixed pattern)
+            self.spatial: SpatialOperand = Gs
+        elif isinstance(Gs, CsrGraph):
+            self.spatial = csr_operand(Gs, Gc.device)
         elif isinstance(Gs, torch.Tensor) and Gs.layout != torch.strided:
             self.spatial = csr_operand(_as_csr_graph(Gs), Gc.device)
         elif isinstance(Gs, torch.Tensor):
@@ -240,10 +245,16 @@ class MixedFusion(nn.Module):
     launches per direction; other cases stay on torch.
     """
 
-    def __init__(self, in_dim: int, rank: Optional[int] = None):
+    def __init__(self, in_dim: int, rank: Optional[int] = None, dim: Optional[int] = None):
         super().__init__()
         self.in_dim = in_dim
-        if rank is None:
+        self.dim = dim          # csr-learned: A and P are the dim = nnz stored values of a sparse graph (1-D), gated by rank-r factors over nnz
+        if dim is not None:
+            if rank is None:
+                raise ValueError('MixedFusion over the values of a sparse graph needs a rank (two Linear(nnz, nnz) layers are out of reach)')
+            self.lin_A = FactorisedLinear(dim, rank)
+            self.lin_P = FactorisedLinear(dim, rank)
+        elif rank is None:
             self.lin_A = nn.Linear(in_dim ** 2, in_dim ** 2)
             self.lin_P = nn.Linear(in_dim ** 2, in_dim ** 2)
         else:
@@ -251,6 +262,13 @@ class MixedFusion(nn.Module):
             self.lin_P = FactorisedLinear(in_dim ** 2, rank)
 
     def forward(self, A: torch.Tensor, P: torch.Tensor):
+        if self.dim is not None:
+            assert A.shape == (self.dim,) and P.shape == (self.dim,)
+            params = (self.lin_A.U, self.lin_A.V, self.lin_A.bias, self.lin_P.U, self.lin_P.V, self.lin_P.bias)
+            if A.is_cuda and fusion.mixed_fusion_lr_supported(A, P, *params):
+                return fusion.mixed_fusion_lr(A, P, *params)
+            gate = torch.sigmoid(self.lin_A(A) + self.lin_P(P))
+            return gate * A + (1 - gate) * P
         assert A.dim() == 2 and P.dim() == 2
         n = self.in_dim
         if isinstance(self.lin_A, nn.Linear) and A.is_cuda:
@@ -309,16 +327,69 @@ class MGP_Gen(nn.Module):
         return Gs, Gc
 
 
+class MGP_Gen_Csr(MGP_Gen):
+    """``MGP_Gen`` with the spatial graph learned on the stored entries of a sparse prior graph (``graph_mode='csr-learned'``; not in the
+    reference, whose learned ``Gs`` is a dense (N, N) matrix): the score ``<u_i, v_j> - <v_i, u_j>`` at the entries (i, j) of ``graph``, a
+    softmax over every row's stored entries, and a rank-r ``MixedFusion`` over the nnz values (``stc_hip.learned``, ``stc_hip.fusion``).  The
+    category branch is ``MGP_Gen``'s.  Same attribute and key names as ``MGP_Gen``; parameter order follows the entry order of ``graph``
+    (CSR of Gs, rows ascending, columns ascending), so on the full pattern a ``state_dict`` of ``MGP_Gen(..., fusion_rank=r)`` loads unchanged
+    and gives the same graphs.  ``forward`` returns (a ``SpatialOperand`` with the learned values, Gc)."""
+
+    DEFAULT_RANK = 16
+
+    def __init__(self, graph: CsrGraph, num_categories: int, hidden_dim: int, alpha: int = 3, fusion_rank: Optional[int] = None):
+        nn.Module.__init__(self)
+        if not isinstance(graph, CsrGraph) or graph.nnz == 0:
+            raise ValueError('MGP_Gen_Csr needs the prior graph as a CsrGraph with at least one stored entry')
+        self.alpha = alpha
+        self.batch_sharded = False
+        self.graph = graph                                          # the pattern (and the default prior values): not a parameter, not in the state_dict
+        self.params_S = self.init_params(num_categories, hidden_dim)
+        self.aggreg_S = MixedFusion(graph.n, self.DEFAULT_RANK if fusion_rank is None else fusion_rank, dim=graph.nnz)
+        self.params_C = self.init_params(graph.n, hidden_dim)
+        self.aggreg_C = MixedFusion(num_categories)
+
+    def _same_pattern(self, As: CsrGraph) -> bool:
+        if As is self.graph:
+            return True
+        if getattr(As, '_stc_same_pattern_as', None) is not self.graph:         # compared once per graph object
+            a, b = As._host, self.graph._host
+            if As.n != self.graph.n or As.nnz != self.graph.nnz or not ((a['bwd_rowptr'] == b['bwd_rowptr']).all() and (a['bwd_colidx'] == b['bwd_colidx']).all()):
+                return False
+            As._stc_same_pattern_as = self.graph
+        return True
+
+    def forward(self, X_seq: torch.Tensor, As: CsrGraph, Ac: torch.Tensor):
+        if not isinstance(As, CsrGraph) or not self._same_pattern(As):
+            raise ValueError('csr-learned: As must be a CsrGraph with the sparsity pattern the model was built on (the parameters are per stored entry)')
+        pattern = csr_pattern(self.graph, X_seq.device)
+        reduce = None
+        if self.batch_sharded:
+            from stc_hip.dist import allreduce_sum
+            reduce = allreduce_sum
+        Ps = learned.mgp_csr_front(X_seq, self.params_S['Wu'], self.params_S['Wv'], pattern, float(self.alpha), reduce)
+        G = self.aggreg_S(As.on(X_seq.device)['bwd_val'].to(Ps.dtype), Ps)    # (fp32 on the device; a float64 module on the CPU in tests)
+        Gc = self.aggreg_C(Ac, self._learned(X_seq, self.params_C, 3))
+        return learned_csr_operand(self.graph, G), Gc
+
+
 class STCGNN(nn.Module):
-    """Encoder-decoder STC-GNN (reference ``STC_GNN.py:175-207``); the drop-in boundary."""
+    """Encoder-decoder STC-GNN (reference ``STC_GNN.py:175-207``); the drop-in boundary.
+
+    ``graph_mode='csr-learned'`` (not in the reference): the spatial graph is learned on the stored entries of the sparse prior graph, which
+    the CONSTRUCTOR takes as ``spatial_graph`` (a ``CsrGraph`` or a torch sparse tensor): the fusion's parameters are per stored entry, so nnz
+    is needed before the first forward pass, and a ``state_dict`` must be loadable into a freshly built model.  ``forward`` is then given a
+    graph with the same pattern (usually the same object) whose values are the prior.  ``fusion_rank`` defaults to 16; nodes are not
+    renumbered (entry order defines parameter order); float32 storage only.  In grad mode the cells run one autograd node per cell (the
+    general path: the graph values need a gradient); under ``no_grad`` they take whatever route the predicates give a fixed sparse graph."""
 
     def __init__(self, num_nodes: int, num_categories: int, Ks: int, Kc: int, input_dim: int, hidden_dim: int,
                  num_layers: int, out_horizon: int, use_bias=True, activation=None,
                  graph_mode: str = 'dense-learned', reorder_nodes: bool = True, batch_sharded: bool = False,
-                 fusion_rank: Optional[int] = None, storage_dtype: torch.dtype = torch.float32):
+                 fusion_rank: Optional[int] = None, storage_dtype: torch.dtype = torch.float32, spatial_graph=None):
         super().__init__()
-        if graph_mode not in ('dense-learned', 'csr-fixed'):
-            raise ValueError("graph_mode must be 'dense-learned' (reference semantics) or 'csr-fixed'")
+        if graph_mode not in ('dense-learned', 'csr-fixed', 'csr-learned'):
+            raise ValueError("graph_mode must be 'dense-learned' (reference semantics), 'csr-fixed' or 'csr-learned'")
         if storage_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError('storage_dtype must be torch.float32 (reference arithmetic) or torch.bfloat16')
         if storage_dtype == torch.bfloat16 and graph_mode != 'csr-fixed':
@@ -331,6 +402,16 @@ class STCGNN(nn.Module):
         self.Ks, self.Kc = Ks, Kc
         if graph_mode == 'dense-learned':
             self.mix_graph_pair = MGP_Gen(num_nodes, num_categories, hidden_dim, fusion_rank=fusion_rank)   # rank: SURVEY 8(f3)
+            self.mix_graph_pair.batch_sharded = batch_sharded
+        elif graph_mode == 'csr-learned':
+            if isinstance(spatial_graph, torch.Tensor) and spatial_graph.layout != torch.strided:
+                spatial_graph = _as_csr_graph(spatial_graph)
+            if not isinstance(spatial_graph, CsrGraph):
+                raise ValueError("graph_mode='csr-learned' needs spatial_graph=: the prior graph As as a CsrGraph or a torch sparse tensor "
+                                 '(its stored entries are the pattern the graph is learned on)')
+            if spatial_graph.n != num_nodes:
+                raise ValueError(f'spatial_graph has {spatial_graph.n} nodes, the model {num_nodes}')
+            self.mix_graph_pair = MGP_Gen_Csr(spatial_graph, num_categories, hidden_dim, fusion_rank=fusion_rank)
             self.mix_graph_pair.batch_sharded = batch_sharded
         self.encoder = STC_Encoder(num_nodes, num_categories, Ks, Kc, input_dim, hidden_dim, num_layers,
                                    use_bias, activation, return_all_layers=True)
@@ -353,6 +434,10 @@ class STCGNN(nn.Module):
         inv = None
         if self.graph_mode == 'dense-learned':
             Gs, Gc = self.mix_graph_pair(X_seq, As, Ac)
+        elif self.graph_mode == 'csr-learned':
+            if isinstance(As, torch.Tensor) and As.layout != torch.strided:
+                As = _as_csr_graph(As)
+            Gs, Gc = self.mix_graph_pair(X_seq, As, Ac)                  # Gs: a SpatialOperand on the prior's pattern, in the given node order
         else:
             Gs, Gc = As, Ac
             if isinstance(Gs, torch.Tensor) and Gs.layout != torch.strided:

@@ -10,6 +10,7 @@ classes, constructors, ``forward`` signatures and ``state_dict`` keys as
     stc_hip.graph   CSR containers for the spatial graph (fixed sparse / learned dense)
     stc_hip.ops     autograd operators = host sequences of kernel launches
     stc_hip.fusion  the rank-r MixedFusion operator (two launches per direction)
+    stc_hip.learned the learned spatial graph on a sparsity pattern (csr-learned mode)
     stc_hip.dist    batch-sharded training: RCCL all-reduce of the gradient bucket
 """
 from .graph import CsrGraph  # noqa: F401

@@ -22,7 +22,7 @@ from .graph import is_full_pattern
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, 'libstc_hip.so')
 # Mirrors of include/stc_hip.h (#define STC_<name>; tests/test_abi.py compares each, and HipKernels.ACT_AMAX_SLOTS, with the header)
-ABI_VERSION = 40
+ABI_VERSION = 41
 FMT_BF16X3, FMT_F16X2 = 0, 1          # operand formats of the split-operand matrix-core kernels
 MAX_K = 4
 STC_ELIMIT = -3            # include/stc_hip.h: a size beyond a kernel limit
@@ -32,6 +32,7 @@ RING2_INTERIOR, RING2_FIRST, RING2_SECOND, RING2_WIDTH = 32, 64, 96, 8     # row
 LOSS_CHUNK = 4096          # STC_LOSS_CHUNK: elements of one run per workgroup of the ComboLoss kernels
 FUSION_LR_CHUNK = 512      # STC_FUSION_LR_CHUNK: rows per partial-sum workgroup of the rank-r MixedFusion kernels
 FUSION_LR_MAX_RANK = 64    # the highest rank stc_mixed_fusion_lr_* accept
+MGP_CSR_MAX_KH = 4096       # STC_MGP_CSR_MAX_KH: the longest U / V row (floats) of the stc_mgp_csr_* kernels
 
 
 class StcError(RuntimeError):
@@ -133,6 +134,11 @@ _ABI = {
     'stc_mgp_uv_bwd_f32': (_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _f32, _p, _i32, _i32, _i32, _i32, _p]),
     'stc_mgp_softmax_fwd_f32': (_int, [_p, _p, _i32, _p]),
     'stc_mgp_softmax_bwd_f32': (_int, [_p, _p, _p, _p, _p, _i32, _p]),
+    'stc_mgp_csr_supported': (_int, [_i32, _i32, _i32]),
+    'stc_mgp_csr_score_f32': (_int, [_p] * 5 + [_i32, _i32, _i32, _p]),
+    'stc_mgp_csr_softmax_fwd_f32': (_int, [_p, _p, _p, _i32, _i32, _p]),
+    'stc_mgp_csr_softmax_bwd_f32': (_int, [_p] * 5 + [_i32, _i32, _p]),
+    'stc_mgp_csr_score_bwd_f32': (_int, [_p] * 10 + [_i32, _i32, _i32, _p]),
     'stc_adam_f32': (_int, [_p] * 4 + [_i64, _p] + [C.c_double] * 5 + [_p]),
     # ---- ComboLoss
     'stc_combo_loss_workspace_bytes': (_size, [_i64, _i64, _i64]),
@@ -1402,6 +1408,69 @@ class HipKernels:
         rowdot, dP = torch.empty(R, dtype=torch.float32, device=P.device), torch.empty_like(P)
         self._launch('stc_mgp_softmax_bwd_f32', P, _ptr(P), _ptr(Ps), _ptr(dPs), _ptr(rowdot), _ptr(dP), R)
         return dP
+
+    # ---- the learned spatial graph on a sparsity pattern (include/stc_hip.h stc_mgp_csr_*; ABI v41) -------------------------------------
+    def mgp_csr_supported(self, R, KH, nnz) -> bool:
+        return 0 < R < (1 << 31) and 0 <= KH < (1 << 31) and 0 <= nnz < (1 << 31) and bool(self.lib.stc_mgp_csr_supported(R, KH, nnz))
+
+    def _mgp_csr_rows(self, what, U, V, rowptr, nnz):
+        """The checks of the launches that read U, V rows; returns (R, KH)."""
+        _tensor(what + '.U', U)
+        if U.dim() < 2:
+            raise StcError(f'{what}.U: (R, KH) or (R, K, h) expected, got {tuple(U.shape)}')
+        _tensor(what + '.V', V, tuple(U.shape))
+        R, KH = U.shape[0], U[0].numel() if U.shape[0] else 0
+        self._i32(what + '.rowptr', rowptr, R + 1)
+        if not self.mgp_csr_supported(R, KH, nnz):
+            raise StcError(f'{what}: R = {R}, KH = {KH}, nnz = {nnz} outside the kernels (KH a multiple of 4 in [4, {MGP_CSR_MAX_KH}], R KH < 2^31)')
+        return R, KH
+
+    def mgp_csr_score(self, U, V, rowptr, colidx):
+        """score (nnz): <u_i, v_j> - <v_i, u_j> at the stored entries (i, j) of the CSR pattern (``stc_mgp_csr_score_f32``: one launch)."""
+        nnz = colidx.numel()
+        R, KH = self._mgp_csr_rows('mgp_csr_score', U, V, rowptr, nnz)
+        self._i32('mgp_csr_score.colidx', colidx)
+        self._same_device(U, V, rowptr, colidx)
+        score = torch.empty(nnz, dtype=torch.float32, device=U.device)
+        self._launch('stc_mgp_csr_score_f32', U, _ptr(U), _ptr(V), _ptr(rowptr), _ptr(colidx), _ptr(score), R, KH, nnz, nbytes=8 * KH * (R + nnz) + 4 * nnz)
+        return score
+
+    def mgp_csr_softmax_fwd(self, score, rowptr):
+        """Ps (nnz): softmax of relu(score) over the stored entries of every row (``stc_mgp_csr_softmax_fwd_f32``: one launch)."""
+        _tensor('mgp_csr_softmax.score', score, (score.numel(),))
+        self._i32('mgp_csr_softmax.rowptr', rowptr)
+        self._same_device(score, rowptr)
+        Ps = torch.empty_like(score)
+        self._launch('stc_mgp_csr_softmax_fwd_f32', score, _ptr(score), _ptr(rowptr), _ptr(Ps), rowptr.numel() - 1, score.numel(), nbytes=16 * score.numel())
+        return Ps
+
+    def mgp_csr_softmax_bwd(self, score, Ps, dPs, rowptr):
+        """ds (nnz) from dPs (``stc_mgp_csr_softmax_bwd_f32``: one launch)."""
+        _tensor('mgp_csr_softmax.score', score, (score.numel(),))
+        for name, t in (('Ps', Ps), ('dPs', dPs)):
+            _tensor('mgp_csr_softmax.' + name, t, tuple(score.shape))
+        self._i32('mgp_csr_softmax.rowptr', rowptr)
+        self._same_device(score, Ps, dPs, rowptr)
+        ds = torch.empty_like(score)
+        self._launch('stc_mgp_csr_softmax_bwd_f32', score, _ptr(score), _ptr(Ps), _ptr(dPs), _ptr(rowptr), _ptr(ds), rowptr.numel() - 1, score.numel(),
+                     nbytes=24 * score.numel())
+        return ds
+
+    def mgp_csr_score_bwd(self, U, V, ds, rowptr, colidx, t_rowptr, t_colidx, t_entry):
+        """(dU, dV), shaped like U: gathered per row over the pattern (rowptr / colidx: CSR of Gs) and its transpose (t_rowptr / t_colidx: CSR of
+        Gs^T, whose entry f is entry t_entry[f] of Gs) (``stc_mgp_csr_score_bwd_f32``: one launch)."""
+        nnz = colidx.numel()
+        R, KH = self._mgp_csr_rows('mgp_csr_score_bwd', U, V, rowptr, nnz)
+        _tensor('mgp_csr_score_bwd.ds', ds, (nnz,))
+        self._i32('mgp_csr_score_bwd.colidx', colidx)
+        self._i32('mgp_csr_score_bwd.t_rowptr', t_rowptr, R + 1)
+        self._i32('mgp_csr_score_bwd.t_colidx', t_colidx, nnz)
+        self._i32('mgp_csr_score_bwd.t_entry', t_entry, nnz)
+        self._same_device(U, V, ds, rowptr, colidx, t_rowptr, t_colidx, t_entry)
+        dU, dV = torch.empty_like(U), torch.empty_like(V)
+        self._launch('stc_mgp_csr_score_bwd_f32', U, _ptr(U), _ptr(V), _ptr(ds), _ptr(rowptr), _ptr(colidx), _ptr(t_rowptr), _ptr(t_colidx), _ptr(t_entry),
+                     _ptr(dU), _ptr(dV), R, KH, nnz, nbytes=8 * KH * (R + 2 * nnz))
+        return dU, dV
 
     def adam(self, p, g, m, v, step, lr, beta1, beta2, eps, weight_decay):
         """One Adam update of a large fp32 parameter in place (``stc_adam_f32``: torch.optim.Adam's arithmetic with L2 weight decay); ``step``: a

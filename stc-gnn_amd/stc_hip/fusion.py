@@ -17,13 +17,15 @@ _FUSED = True            # ROCm fp32 operands go to the fused kernels (False: th
 
 def mixed_fusion_lr_supported(A, P, UA, VA, bA, UP, VP, bP) -> bool:
     """Whether ``mixed_fusion_lr`` takes these operands: float32 on one ROCm device, contiguous parameters, everything 16-byte aligned,
-    A and P (n, n), factors (n^2, r) with 1 <= r <= 64, biases (n^2) (asks for the kernel set only when the tensors are on a device).
+    A and P (n, n) -- or 1-D of equal length D, the values of a graph on a sparsity pattern (``graph_mode='csr-learned'``: the kernels take any
+    D) --, factors (D, r) with D = n^2 and 1 <= r <= 64, biases (D) (asks for the kernel set only when the tensors are on a device).
     No (n, r) is excluded by measurement: the kernels' replayed forward + backward was faster than the torch route at every pair
     measured (profiles/r12/mixed_fusion_lr_ab.txt)."""
     ts = (A, P, UA, VA, bA, UP, VP, bP)
     if not (_FUSED and all(isinstance(t, torch.Tensor) for t in ts) and ops._f32_on_gpu(ts) and all(t.device == A.device for t in ts)):
         return False
-    if A.dim() != 2 or A.shape[0] != A.shape[1] or P.shape != A.shape or A.numel() == 0 or UA.dim() != 2:
+    square = A.dim() == 2 and A.shape[0] == A.shape[1]
+    if not (square or A.dim() == 1) or P.shape != A.shape or A.numel() == 0 or UA.dim() != 2:      # 1-D: the stored values of a sparse graph (D = nnz)
         return False
     D, r = A.numel(), UA.shape[1]
     if not (1 <= r <= FUSION_LR_MAX_RANK and all(t.shape == (D, r) for t in (UA, VA, UP, VP)) and bA.shape == (D,) and bP.shape == (D,)):

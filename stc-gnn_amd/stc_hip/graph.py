@@ -679,6 +679,40 @@ def dense_operand(Gs: torch.Tensor) -> SpatialOperand:
     return SpatialOperand(n, rowptr, colidx, fwd_val, rowptr, colidx, bwd_val, n * n)
 
 
+def csr_pattern(graph: CsrGraph, device: torch.device) -> Dict[str, torch.Tensor]:
+    """The sparsity pattern of ``graph`` as the learned-graph operators of ``stc_hip.learned`` read it, on ``device`` (cached per graph and
+    device).  Entry e = (i, j) of Gs sits in row i of ``rowptr`` / ``colidx`` (CSR of Gs itself: the graph's ``bwd_*`` arrays), and every
+    per-entry vector is in that order.  ``t_rowptr`` / ``t_colidx``: CSR of Gs^T (``fwd_*``), whose entry f is entry ``t_entry[f]`` of Gs
+    (int32 for the kernels, ``to_fwd`` the same as an int64 gather index: ``fwd_val = values[to_fwd]``); ``rows``: the row of every entry."""
+    d = graph.on(device)
+    device = d['bwd_rowptr'].device
+    cache = graph.__dict__.setdefault('_pattern_dev', {})
+    pat = cache.get(device)
+    if pat is None:
+        perm = graph._host['bwd_perm']                               # bwd_val = fwd_val[bwd_perm]
+        inv = np.empty_like(perm)
+        inv[perm] = np.arange(perm.size, dtype=perm.dtype)
+        rows = np.repeat(np.arange(graph.n, dtype=np.int64), np.diff(graph._host['bwd_rowptr'].astype(np.int64)))
+        pat = dict(n=graph.n, nnz=graph.nnz, rowptr=d['bwd_rowptr'], colidx=d['bwd_colidx'], t_rowptr=d['fwd_rowptr'], t_colidx=d['fwd_colidx'],
+                   t_entry=torch.from_numpy(inv.astype(np.int32)).to(device), to_fwd=torch.from_numpy(inv).to(device),
+                   rows=torch.from_numpy(rows).to(device), cols=d['bwd_colidx'].long())
+        cache[device] = pat
+    return pat
+
+
+def learned_csr_operand(graph: CsrGraph, values: torch.Tensor) -> SpatialOperand:
+    """A learned graph on the pattern of ``graph`` (``graph_mode='csr-learned'``): ``values`` (nnz), in the entry order of Gs itself
+    (``csr_pattern``), may carry autograd history.  The forward values are a differentiable gather into the order of Gs^T, the backward values
+    ``values`` detached.  The values change every step, so there are no row-block, patch or two-ring plans and no second-order source."""
+    if values.dim() != 1 or values.numel() != graph.nnz:
+        raise ValueError(f'learned_csr_operand: {graph.nnz} values expected (one per stored entry), got {tuple(values.shape)}')
+    pat = csr_pattern(graph, values.device)
+    # G = gate * A + (1 - gate) * Ps is a convex mix of the prior A and a row-stochastic Ps: its absolute row sums stay within the larger of theirs
+    bound = max(graph.row_sum_bound, 1.0)
+    return SpatialOperand(graph.n, pat['t_rowptr'], pat['t_colidx'], values.index_select(0, pat['to_fwd']), pat['rowptr'], pat['colidx'],
+                          values.detach(), graph.nnz, None, None, bound, None, None, False, None)
+
+
 def csr_operand(graph: CsrGraph, device: torch.device) -> SpatialOperand:
     d = graph.on(device)
     def plan(side):
