@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define STC_ABI_VERSION 41
+#define STC_ABI_VERSION 42
 #define STC_MAX_K 4          /* highest Chebyshev order (Ks, Kc) the node kernels accept */
 
 /* Operand formats of the split-operand matrix-core kernels (C = 32 / 64, hidden 16).  Every fp32 operand is split into low-precision
@@ -737,6 +737,19 @@ int stc_mix_grad_f32(const float* A, const float* B, double* partials, int32_t n
  * operands (the same fp32 product chain per plane and tile, the same float64 fold order), so the setting changes time only.  Other values:
  * STC_EINVAL, setting unchanged. */
 int stc_set_graph_grad_form(int32_t form);
+
+/* The same graph product SAMPLED at the stored entries of a CSR pattern (ABI v42): the value gradient of a learned graph on a sparse pattern
+ * (graph_mode 'csr-learned' on the few-category cell kernels).  rowptr (n_rows + 1) / colidx (nnz): the CSR of Gs^T, whose row i lists the
+ * source nodes of destination i; A, B: planes of (n_rows, F) floats, F a multiple of 4 up to 512, selected and cut into chunks as above:
+ *   partials[chunk][e] = sum_{g = chunk, chunk + n_chunks, ..} sum_f A[g][i(e)][f] * B[g][colidx[e]][f]        e in [rowptr[i], rowptr[i + 1])
+ * Per plane and entry every lane forms its share as an fp32 fmaf chain and adds it to a FLOAT64 sum that runs over the planes and then over
+ * the wave; no atomics: bitwise reproducible.  Every entry of every chunk is WRITTEN (a chunk without a plane: zeros), nothing outside
+ * [0, nnz) of a chunk's row; chunk_stride as above (0 = nnz).  Rows of any length, rows without entries.  nnz == 0 or n_sel == 0 launches
+ * nothing.  Non-finite values are not masked: a NaN in row i of A reaches the entries of row i, in row j of B the entries with column j,
+ * and nothing else changes a bit [tests/test_graph_grad_csr.py test_a_nan_reaches_its_row_or_column_only]. */
+int stc_graph_grad_csr_f32(const int32_t* rowptr, const int32_t* colidx, int32_t n_rows, int32_t nnz, const float* A, const float* B, double* partials,
+                           int32_t n_chunks, int32_t cell0, int32_t cell_step, int32_t n_sel, int32_t batch, int32_t F, int64_t chunk_stride,
+                           void* stream);
 
 /* Gradient of the category graph through ONE BDG_Dif for FEW categories (ABI v33; reference STC_GNN.py:38-42 through autograd), on the
  * exact-fp32 matrix cores:  dTc[c][p][d] = sum_r sum_o U_c[r][p][o] * dY[r][d][o],  U_c[r] = sum_n Z_n[r] . W[(n, c, :), :]  (r: nodes).

@@ -343,6 +343,7 @@ class MGP_Gen_Csr(MGP_Gen):
             raise ValueError('MGP_Gen_Csr needs the prior graph as a CsrGraph with at least one stored entry')
         self.alpha = alpha
         self.batch_sharded = False
+        self.sampled_grad = False                                   # put on the operand ``forward`` returns (STCGNN sets it from ``csr_cells``)
         self.graph = graph                                          # the pattern (and the default prior values): not a parameter, not in the state_dict
         self.params_S = self.init_params(num_categories, hidden_dim)
         self.aggreg_S = MixedFusion(graph.n, self.DEFAULT_RANK if fusion_rank is None else fusion_rank, dim=graph.nnz)
@@ -370,7 +371,7 @@ class MGP_Gen_Csr(MGP_Gen):
         Ps = learned.mgp_csr_front(X_seq, self.params_S['Wu'], self.params_S['Wv'], pattern, float(self.alpha), reduce)
         G = self.aggreg_S(As.on(X_seq.device)['bwd_val'].to(Ps.dtype), Ps)    # (fp32 on the device; a float64 module on the CPU in tests)
         Gc = self.aggreg_C(Ac, self._learned(X_seq, self.params_C, 3))
-        return learned_csr_operand(self.graph, G), Gc
+        return learned_csr_operand(self.graph, G, self.sampled_grad), Gc
 
 
 class STCGNN(nn.Module):
@@ -381,13 +382,22 @@ class STCGNN(nn.Module):
     is needed before the first forward pass, and a ``state_dict`` must be loadable into a freshly built model.  ``forward`` is then given a
     graph with the same pattern (usually the same object) whose values are the prior.  ``fusion_rank`` defaults to 16; nodes are not
     renumbered (entry order defines parameter order); float32 storage only.  In grad mode the cells run one autograd node per cell (the
-    general path: the graph values need a gradient); under ``no_grad`` they take whatever route the predicates give a fixed sparse graph."""
+    general path: the graph values need a gradient); under ``no_grad`` they take whatever route the predicates give a fixed sparse graph.
+    ``csr_cells='fused'`` (csr-learned only; default ``'per-cell'``) prefers the few-category cell executor in grad mode too, which forms the
+    value gradient at the stored entries (``stc_graph_grad_csr_f32``): Chebyshev order 2, hidden 16, C <= 16 on the HIP kernel set; where
+    ``small.small_graph_supported`` declines, the per-cell path runs with the same bits as ``'per-cell'``."""
 
     def __init__(self, num_nodes: int, num_categories: int, Ks: int, Kc: int, input_dim: int, hidden_dim: int,
                  num_layers: int, out_horizon: int, use_bias=True, activation=None,
                  graph_mode: str = 'dense-learned', reorder_nodes: bool = True, batch_sharded: bool = False,
-                 fusion_rank: Optional[int] = None, storage_dtype: torch.dtype = torch.float32, spatial_graph=None):
+                 fusion_rank: Optional[int] = None, storage_dtype: torch.dtype = torch.float32, spatial_graph=None,
+                 csr_cells: str = 'per-cell'):
         super().__init__()
+        if csr_cells not in ('per-cell', 'fused'):
+            raise ValueError("csr_cells must be 'per-cell' (one autograd node per cell) or 'fused' (the few-category cell executor)")
+        if csr_cells == 'fused' and graph_mode != 'csr-learned':
+            raise ValueError("csr_cells='fused' needs graph_mode='csr-learned' (the other modes choose their cell route themselves)")
+        self.csr_cells = csr_cells              # read at every forward
         if graph_mode not in ('dense-learned', 'csr-fixed', 'csr-learned'):
             raise ValueError("graph_mode must be 'dense-learned' (reference semantics), 'csr-fixed' or 'csr-learned'")
         if storage_dtype not in (torch.float32, torch.bfloat16):
@@ -437,6 +447,7 @@ class STCGNN(nn.Module):
         elif self.graph_mode == 'csr-learned':
             if isinstance(As, torch.Tensor) and As.layout != torch.strided:
                 As = _as_csr_graph(As)
+            self.mix_graph_pair.sampled_grad = self.csr_cells == 'fused'
             Gs, Gc = self.mix_graph_pair(X_seq, As, Ac)                  # Gs: a SpatialOperand on the prior's pattern, in the given node order
         else:
             Gs, Gc = As, Ac

@@ -22,7 +22,7 @@ from .graph import is_full_pattern
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, 'libstc_hip.so')
 # Mirrors of include/stc_hip.h (#define STC_<name>; tests/test_abi.py compares each, and HipKernels.ACT_AMAX_SLOTS, with the header)
-ABI_VERSION = 41
+ABI_VERSION = 42
 FMT_BF16X3, FMT_F16X2 = 0, 1          # operand formats of the split-operand matrix-core kernels
 MAX_K = 4
 STC_ELIMIT = -3            # include/stc_hip.h: a size beyond a kernel limit
@@ -122,6 +122,7 @@ _ABI = {
                                + [_i32, _p, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _size, _i32, _i32, _i32, _i32, _p]),
     'stc_graph_grad_f32': (_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _p]),
     'stc_set_graph_grad_form': (_int, [_i32]),
+    'stc_graph_grad_csr_f32': (_int, [_p, _p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _p]),
     'stc_mix_grad_f32': (_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _p]),
     'stc_mixed_fusion_workspace_bytes': (_size, [_i32, _i32]),
     'stc_mixed_fusion_fwd_f32': (_int, [_p] * 8 + [_i32, _p]),
@@ -1250,6 +1251,43 @@ class HipKernels:
         chunks = self.graph_grad_chunks(n_sel * batch, N, A.shape[2], A.device)
         part = torch.empty(chunks, N, N, dtype=torch.float64, device=A.device)
         self._launch('stc_graph_grad_f32', A, A.data_ptr(), Bm.data_ptr(), part.data_ptr(), chunks, cell0, cell_step, n_sel, batch, N, Cc * A.shape[3], 0)
+        return part.sum(0)
+
+    GRAPH_GRAD_CSR_WAVES = 4096          # (row, chunk) waves that fill the chip: 256 compute units x 4 SIMDs x 4 waves
+    GRAPH_GRAD_CSR_MAX_CHUNKS = 64
+    GRAPH_GRAD_CSR_PART_DOUBLES = 1 << 22    # chunks x nnz of one product's partial block: 32 MiB of float64
+
+    @classmethod
+    def graph_grad_csr_chunks(cls, planes, N, nnz, device=None) -> int:
+        """Float64 partials of a ``graph_grad_csr`` product over ``planes`` planes of N rows with ``nnz`` stored entries.  The kernel runs one
+        wave per (row, chunk), so: chunks = ceil(``GRAPH_GRAD_CSR_WAVES`` / N) -- enough waves to fill the chip --, never more than ``planes``
+        (a chunk without a plane only writes zeros) or ``GRAPH_GRAD_CSR_MAX_CHUNKS``, and never so many that chunks x nnz passes
+        ``GRAPH_GRAD_CSR_PART_DOUBLES`` (the block is written and re-read once: it stays small next to the slabs, planes x N x F floats); at
+        least 1.  A function of its first three arguments alone (``device`` is not read): an eager step and a replayed one fold in one order."""
+        fill = -(-cls.GRAPH_GRAD_CSR_WAVES // max(1, N))
+        return max(1, min(planes, cls.GRAPH_GRAD_CSR_MAX_CHUNKS, fill, cls.GRAPH_GRAD_CSR_PART_DOUBLES // max(1, nnz)))
+
+    def graph_grad_csr(self, rowptr, colidx, A, Bm, cell0, cell_step, n_sel, N, into=None):
+        """(nnz,) float64: ``graph_grad`` sampled at the stored entries of the CSR pattern (rowptr, colidx) of N rows (the operand's ``fwd_*``
+        arrays: CSR of Gs^T, so the result is in ``fwd_val``'s order) -- entry e of row i: the sum over the selected cells and samples of
+        < A_g[i], B_g[colidx[e]] > (``stc_graph_grad_csr_f32``).  ``into``: as ``graph_grad``, a block of nnz columns."""
+        batch, Cc = self._grad_operands('graph_grad_csr', A, Bm, cell0, cell_step, n_sel, N)
+        if A.shape[3] != Bm.shape[3] or Cc * A.shape[3] > 512:
+            raise StcError(f'graph_grad_csr: widths {A.shape[3]} / {Bm.shape[3]} differ, or {Cc} x {A.shape[3]} floats per node pass 512')
+        self._i32('graph_grad_csr.rowptr', rowptr, N + 1)
+        self._i32('graph_grad_csr.colidx', colidx)
+        nnz, F = colidx.numel(), Cc * A.shape[3]
+        self._same_device(A, rowptr, colidx)
+        if into is not None:
+            part, ptr, chunks, stride = self._grad_block('graph_grad_csr', into, nnz)
+            self._same_device(A, part)
+            self._launch('stc_graph_grad_csr_f32', A, rowptr.data_ptr(), colidx.data_ptr(), N, nnz, A.data_ptr(), Bm.data_ptr(), ptr, chunks, cell0, cell_step,
+                         n_sel, batch, F, stride)
+            return None
+        chunks = self.graph_grad_csr_chunks(n_sel * batch, N, nnz, A.device)
+        part = (torch.zeros if n_sel == 0 else torch.empty)(chunks, nnz, dtype=torch.float64, device=A.device)      # (no selected cell: nothing is launched)
+        self._launch('stc_graph_grad_csr_f32', A, rowptr.data_ptr(), colidx.data_ptr(), N, nnz, A.data_ptr(), Bm.data_ptr(), part.data_ptr(), chunks, cell0,
+                     cell_step, n_sel, batch, F, 0)
         return part.sum(0)
 
     def mix_grad(self, A, Bm, cell0, cell_step, n_sel, N, into=None):

@@ -634,6 +634,8 @@ class SpatialOperand:
     ring2_clusters: bool = False         # those plans are over ring-bounded clusters (1 708 ragged patches for the bench's grid under a random order
                                          # against 1 568 tiles: every launch +17 %), where only the forms that replace two gathering launches pay
     source: Optional['CsrGraph'] = None  # the fixed graph this operand came from (its second Chebyshev matrix: CsrGraph.second_order)
+    sampled_grad: bool = False           # a learned graph on a sparse pattern whose caller prefers the few-category executor, which forms the
+                                         # value gradient at the stored entries (``small.small_graph_supported``); else one autograd node per cell
 
 
 _PATTERN_CACHE: Dict[Tuple[int, torch.device], Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -700,17 +702,18 @@ def csr_pattern(graph: CsrGraph, device: torch.device) -> Dict[str, torch.Tensor
     return pat
 
 
-def learned_csr_operand(graph: CsrGraph, values: torch.Tensor) -> SpatialOperand:
+def learned_csr_operand(graph: CsrGraph, values: torch.Tensor, sampled_grad: bool = False) -> SpatialOperand:
     """A learned graph on the pattern of ``graph`` (``graph_mode='csr-learned'``): ``values`` (nnz), in the entry order of Gs itself
     (``csr_pattern``), may carry autograd history.  The forward values are a differentiable gather into the order of Gs^T, the backward values
-    ``values`` detached.  The values change every step, so there are no row-block, patch or two-ring plans and no second-order source."""
+    ``values`` detached.  The values change every step, so there are no row-block, patch or two-ring plans and no second-order source.
+    ``sampled_grad``: the operand's field of that name (a preference for the fused cell executor, default off)."""
     if values.dim() != 1 or values.numel() != graph.nnz:
         raise ValueError(f'learned_csr_operand: {graph.nnz} values expected (one per stored entry), got {tuple(values.shape)}')
     pat = csr_pattern(graph, values.device)
     # G = gate * A + (1 - gate) * Ps is a convex mix of the prior A and a row-stochastic Ps: its absolute row sums stay within the larger of theirs
     bound = max(graph.row_sum_bound, 1.0)
     return SpatialOperand(graph.n, pat['t_rowptr'], pat['t_colidx'], values.index_select(0, pat['to_fwd']), pat['rowptr'], pat['colidx'],
-                          values.detach(), graph.nnz, None, None, bound, None, None, False, None)
+                          values.detach(), graph.nnz, None, None, bound, None, None, False, None, bool(sampled_grad))
 
 
 def csr_operand(graph: CsrGraph, device: torch.device) -> SpatialOperand:

@@ -38,8 +38,12 @@ def _c(t):
 
 def small_graph_supported(k, op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widths, dtype=torch.float32) -> bool:
     """Fixed graphs, or the reference's learned ones: a learned spatial graph must be dense (values = the full N x N pattern, as
-    ``graph.dense_operand`` builds it) -- its gradient is formed as a dense product."""
-    if dtype != torch.float32 or not hasattr(k, 'cell_small_supported') or (op.fwd_val.requires_grad and op.nnz != op.n * op.n):
+    ``graph.dense_operand`` builds it) -- its gradient is formed as a dense product.  A learned graph on a SPARSE pattern
+    (``graph.learned_csr_operand``) is taken only where the caller asked for it (``op.sampled_grad``: ``STCGNN(csr_cells='fused')``), at
+    Chebyshev order 2, by a kernel set with the sampled product (``graph_grad_csr``); its gradient is formed at the stored entries."""
+    if dtype != torch.float32 or not hasattr(k, 'cell_small_supported'):
+        return False
+    if op.fwd_val.requires_grad and op.nnz != op.n * op.n and not (op.sampled_grad and Ks == 2 and hasattr(k, 'graph_grad_csr')):
         return False
     full = op.nnz == op.n * op.n
     # the graph as the learned mode hands it over: full pattern, requiring grad -- or, with grad mode off (evaluation: the generator's Gs does
@@ -323,16 +327,18 @@ class _StcSmallGraph(Function):
             dWg, dbg = row[:nW * 32].view(nW, 32), row[nW * 32:nW * 32 + 32]
             dWc, dbc = row[nW * 32 + 32:nW * 48 + 32].view(nW, H16), row[nW * 48 + 32:nW * 48 + 48]
             flat += [dWg, dbg if st[1] is not None else None, dWc, dbc if st[3] is not None else None]
-        graph_grads = _graph_gradients(bufs, k, Tc, stacks, schedule, cin, pos, need_Tc, need_val, need_t2 and ctx.t2b is not None) if learned else (None,) * 3
+        graph_grads = _graph_gradients(bufs, k, op, Tc, stacks, schedule, cin, pos, need_Tc, need_val, need_t2 and ctx.t2b is not None) if learned else (None,) * 3
         return (None,) * 6 + graph_grads + (None,) * n_ext + tuple(flat)
 
 
-def _graph_gradients(bufs, k, Tc, stacks, schedule, cin, pos, need_Tc, need_val, need_t2=False):
+def _graph_gradients(bufs, k, op, Tc, stacks, schedule, cin, pos, need_Tc, need_val, need_t2=False):
     """(dT_c, d fwd_val, d T_2) of a learned-graph backward pass from what the cell launches left in ``bufs`` (module docstring), per width group
     (index 0: narrow inputs, 1: 16-column inputs), in the kernels' column order [H (16) | X (cin) | 0]; W's rows are re-ordered to match.  d T_2
     (order 3) is the same product as d fwd_val on the third slabs' gradients, its partials in the same buffer.  The sums over cells and samples
     run in ``graph_grad`` / ``mix_grad`` (stc_graph_grad_f32 / stc_mix_grad_f32: fp32 matrix products per plane, float64 accumulation):
       d fwd_val = sum_cells [dZ1g x Z0 + dZ1c x Z0c]                                      (every cell of a width at once)
+                  on a sparse pattern (``op.nnz != N * N``, order 2): the same products at the stored entries only, in ``op.fwd_val``'s
+                  order (``graph_grad_csr``: stc_graph_grad_csr_f32) -- (nnz,) instead of (N, N)
       dT_c[c, d] = < W[(ks, c)], Q_ks[c, :, d, :] >,  Q_ks = Z_ks^T . dY                  (per parameter set and convolution)."""
     (B, N, C), Ks, counts, Kc = bufs.dims, bufs.Ks, bufs.counts, Tc.shape[0]
     # every product of the pass leaves its float64 partials in ONE (chunks, total) buffer, side by side, and one sum adds them all: per
@@ -377,7 +383,15 @@ def _graph_gradients(bufs, k, Tc, stacks, schedule, cin, pos, need_Tc, need_val,
     block = lambda s0, dY: C * s0.shape[-1] * C * dY.shape[-1]
     total = sum(Ks * block(e[0][0], e[2]) for es in classes.values() for e in es)
     dS = dT2 = None
-    if need_val or need_t2:                                       # (N x N blocks are small: more, shorter workgroups -- a buffer of their own)
+    if need_val and op.nnz != N * N:                              # a sparse pattern: the products sampled at its entries, one shared partial buffer
+        dS = torch.zeros(op.nnz, dtype=torch.float64, device=Tc.device)
+        if graph_jobs:
+            planes = min(n for _, _, n in graph_jobs) * B
+            gpart = k.grad_partials(Tc, len(graph_jobs) * op.nnz, chunks=k.graph_grad_csr_chunks(planes, N, op.nnz, Tc.device))
+            for i, (A, Bm, n_sel) in enumerate(graph_jobs):
+                k.graph_grad_csr(op.fwd_rowptr, op.fwd_colidx, A, Bm, 0, 1, n_sel, N, into=(gpart, i * op.nnz))
+            dS = gpart.view(-1, len(graph_jobs), op.nnz).sum((0, 1))                           # ONE sum for the partials of every job
+    elif need_val or need_t2:                                     # (N x N blocks are small: more, shorter workgroups -- a buffer of their own)
         kinds = int(bool(need_val)) + int(bool(need_t2))
         both = torch.zeros(kinds, N, N, dtype=torch.float64, device=Tc.device)
         if graph_jobs:

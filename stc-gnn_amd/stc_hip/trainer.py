@@ -65,7 +65,8 @@ class Trainer:
                             out_horizon=params['pred_len'], graph_mode=graph_mode,
                             batch_sharded=self.world > 1 and graph_mode in ('dense-learned', 'csr-learned'),
                             fusion_rank=None if fusion_rank is None else int(fusion_rank),
-                            spatial_graph=s_adj if graph_mode == 'csr-learned' else None).to(dev)
+                            spatial_graph=s_adj if graph_mode == 'csr-learned' else None,
+                            csr_cells=params.get('csr_cells', 'per-cell')).to(dev)      # csr-learned: 'fused' prefers the few-category cell executor
         sdist.broadcast_parameters(self.model)                          # every replica starts from rank 0's draw
         self.criterion = ComboLoss()
         self.bucket = sdist.GradBucket(self.model.parameters())        # every .grad is a view into one flat buffer

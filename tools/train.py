@@ -43,9 +43,13 @@ ap.add_argument('-stride', '--time_slice', type=int, default=None, help=argparse
 ap.add_argument('-hipgraph', '--hip_graph', type=int, default=0, choices=[0, 1], help='replay the train step as a captured HIP graph (one rank; launch-bound shapes)')
 ap.add_argument('-rank', '--fusion_rank', type=int, default=None,
                 help="learned graphs: rank-r factors in place of MixedFusion's two Linear(N^2, N^2) layers (2 N^4 parameters: NYC and CHI do not fit one GPU without)")
+ap.add_argument('-cells', '--csr_cells', default=None, choices=['per-cell', 'fused'],
+                help="csr-learned: 'fused' prefers the few-category cell executor with the value gradient sampled at the stored entries "
+                     "(order 2, hidden 16, C <= 16); default per-cell = one autograd node per cell")
 params = vars(ap.parse_args())
-if params['fusion_rank'] is None:
-    del params['fusion_rank']                                   # the key exists only when given: the CSV parameter line of a run without it is unchanged
+for key in ('fusion_rank', 'csr_cells'):
+    if params[key] is None:
+        del params[key]                                         # the key exists only when given: the CSV parameter line of a run without it is unchanged
 rank, world, local = sdist.init_from_env()                      # under torchrun: one rank per GPU, each on its own device
 if world > 1:
     params['device'] = f'cuda:{local}'
