@@ -82,6 +82,17 @@ BwdCarve bwd_carve(const NodeDims& d, bool want_dT) {
     return c;
 }
 
+// The backward keeps W^T and the dW accumulators resident (J x KD floats each): at L = Ho = 64 -- the gates convolution of a wide cell at hidden
+// width 32 -- they take 130 KiB, and the default tile of up to 32 category rows no longer fits beside them.  Fewer nodes per tile then, down to
+// one (the kernel takes any TN); shapes that fit keep their tile, and with it their bits.
+NodeDims fit_bwd(NodeDims d, bool want_dT) {
+    while (d.TN > 1 && (size_t)bwd_carve(d, want_dT).total * sizeof(float) > stc::kMaxLdsBytes) {
+        --d.TN;
+        d.rows = d.TN * d.C;
+    }
+    return d;
+}
+
 __device__ __forceinline__ void fma4(float4& a, float s, const float4& w) {
     a.x = fmaf(s, w.x, a.x); a.y = fmaf(s, w.y, a.y); a.z = fmaf(s, w.z, a.z); a.w = fmaf(s, w.w, a.w);
 }
@@ -791,8 +802,8 @@ extern "C" int stc_bdg_node_bwd_f32(const float* const* Z, int32_t Ks, const flo
         if (rc == STC_OK) return stc::grad_tail_reduce(&g, 1, n_parts, s);
         if (rc != STC_NOT_HANDLED) return rc;
     }
-    const NodeDims d = make_dims(Ks, Kc, C, L, Lw, Ho);
     const bool want_dT = dTc != nullptr && Kc > 1;
+    const NodeDims d = fit_bwd(make_dims(Ks, Kc, C, L, Lw, Ho), want_dT);
     const BwdCarve cv = bwd_carve(d, want_dT);
     const size_t lds = (size_t)cv.total * sizeof(float);
     STC_REQUIRE(lds <= stc::kMaxLdsBytes, STC_ELIMIT,

@@ -286,12 +286,20 @@ def check_node_backward(tag, d, ref, dZ, dW, db, dT, bound=TOL):
 
 def run_node(hip, family, p, level):
     """Forward with and without bias, backward with and without dT, the weight gradient a second time."""
-    shape = node_shape(family, p)
+    run_node_shape(hip, node_shape(family, p), seed_of(family, p), (family, point_id(p)), f'{family} {point_id(p)} level {level}', level)
+
+
+#: the gates convolution of a cell with a 32-column input at hidden width 32 (Ks = Kc = 2): L = 32 + 32, Ho = 2 x 32.  Outside ``GENERIC_CLASSES``
+#: because the generic backward takes it for few categories only: W^T and the dW accumulators fill 130 KiB of the LDS, the tile shrinks to what
+#: fits beside them (csrc/stc_node.hip ``fit_bwd``) -- one node of up to 21 categories, 15 when dT_c is wanted too
+HIDDEN32_GATES = (64, 64, 64, 2, 2)
+
+
+def run_node_shape(hip, shape, seed, key, tag, level):
     nodes, C, L, Lw, Ho, Ks, Kc = shape
-    d = node_operands(*shape, seed=seed_of(family, p))
-    ref = node_reference((family, point_id(p)), d)
+    d = node_operands(*shape, seed=seed)
+    ref = node_reference(key, d)
     Zs, Tc, W, dY = cu(d['Zs']), cu(d['Tc']), cu(d['W']), cu(d['dY'])
-    tag = f'{family} {point_id(p)} level {level}'
     with at_level(hip, level):
         for b in (d['b'], None):
             Y = nan(nodes, C, Ho)

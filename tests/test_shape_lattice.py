@@ -169,6 +169,31 @@ def test_generic_node_kernel(hip, p):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('level', [0, 2])
+@pytest.mark.parametrize('C', [1, 5, 15])
+def test_generic_node_kernel_at_the_widths_of_hidden_32(hip, C, level):
+    """``S.HIDDEN32_GATES``: what STCGNN(hidden_dim=32) asks of the node backward on its per-cell path (tests/test_model_lattice.py, route
+    hidden32).  With the tile fixed at 32 category rows the launch was refused for EVERY C (173 328 B of LDS at C = 5); the tile now shrinks to fit.
+    C = 1: 32 nodes per tile become 22; C = 5: 6 become 4; C = 15: 2 become 1, the most categories that fit with dT_c.  More nodes than two
+    default tiles, so the shrunken tiles number at least three and the last one is ragged."""
+    nodes = 2 * (32 // C) + 1
+    S.run_node_shape(hip, (nodes, C, *S.HIDDEN32_GATES), S.seed_of('hidden32', dict(C=C)), ('hidden32', C), f'hidden-32 gates C={C} level {level}', level)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('C,want_dT', [(16, True), (22, False), (32, False)])
+def test_generic_node_kernel_declines_hidden_32_beyond_its_lds(hip, C, want_dT):
+    """... and just beyond what fits with one node per tile the backward still answers STC_ELIMIT, before any launch: no silent fall-back."""
+    from stc_hip._lib import StcError
+    shape = (3, C, *S.HIDDEN32_GATES)
+    d = S.node_operands(*shape, seed=7)
+    Zs, Tc, W, dY = S.cu(d['Zs']), S.cu(d['Tc']), S.cu(d['W']), S.cu(d['dY'])
+    with S.at_level(hip, 2), pytest.raises(StcError) as err:
+        hip.bdg_node_bwd(Zs, Tc, W, dY, [S.nan(3, C, 64), S.nan(3, C, 64)], S.nan(*W.shape), S.nan(64), S.nan(2, C, C) if want_dT else None)
+    assert err.value.code == ELIMIT, err.value
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize('level', [0, 1])
 @pytest.mark.parametrize('p', S.points('fused_cell'))
 def test_fused_cell_kernels(hip, p, level):
