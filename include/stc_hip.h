@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define STC_ABI_VERSION 42
+#define STC_ABI_VERSION 43
 #define STC_MAX_K 4          /* highest Chebyshev order (Ks, Kc) the node kernels accept */
 
 /* Operand formats of the split-operand matrix-core kernels (C = 32 / 64, hidden 16).  Every fp32 operand is split into low-precision
@@ -763,6 +763,28 @@ int stc_mix_dt_supported(int32_t Ks, int32_t Kc, int32_t C, int32_t L, int32_t H
 size_t stc_mix_dt_workspace_bytes(int32_t Ks);
 int stc_mix_dt_f32(const float* const* Z, int32_t Ks, const float* W, const float* dY, float* dTc, void* workspace,
                    size_t workspace_bytes, int64_t rows, int32_t C, int32_t L, int32_t Lw, int32_t Ho, void* stream);
+
+/* Gradient of the category graph's Chebyshev stack from the PLANAR cells of the cell-graph executor (ABI v43, csrc/stc_cell_dtc_planar.hip;
+ * graph_mode 'csr-category-learned': fixed sparse spatial graph, learned category graph).  Order 2 (Ks = Kc = 2), hidden 16, fp32 planes
+ * (rows, C, w) with C in {32, 64}; input plane of cin = 16 or 1..4 columns (stc_cell_dtc_planar_supported).  W in the reference's layout
+ * (4 L, Ho), L = cin + 16; block (n, kc) = its L rows from (2 n + kc) L, input columns first.  T_0 = I is a constant: only dTc[1] is formed.
+ *   gates      V[r][c][o] = [X|H][r][c][:] . Wg[block (0, 1)][:, o] + [SX|SH][r][c][:] . Wg[block (1, 1)][:, o]            o < 32
+ *              dG[r][d][o] = dHnew (Cand - H) U (1 - U),  dG[r][d][16 + o] = dRH H R (1 - R)      o < 16; re-formed in registers, never stored
+ *              partials[slot(r)][c][d] += sum_o V[r][c][o] dG[r][d][o]
+ *   candidate  V0 = [X|RH][r] . Wc[block (0, 1)], V1 = [X|RH][r] . Wc[block (1, 1)]     (dY = dHnew U (1 - Cand^2), dBm = S^T dY)
+ *              partials[slot(r)][c][d] += sum_{o < 16} V0[r][c][o] dY[r][d][o] + V1[r][c][o] dBm[r][d][o]
+ * A workgroup owns a fixed run of consecutive rows and ADDS its C x C float64 result to its own slot of partials (slots, C, C),
+ * slots = stc_cell_dtc_planar_slots(rows): the caller zeroes partials once per backward pass, every cell's two launches add, one sum over
+ * the slots finishes dTc[1].  Products in fp32 (fmaf), float64 from the per-row result on; no atomics, one fixed order: bitwise
+ * reproducible.  Nothing outside [0, slots * C * C) doubles is written; no operand is.  Non-finite values are not masked.  rows == 0
+ * launches nothing.  State-sized planes 16-byte aligned, a narrow input plane 4-byte, partials 8-byte (STC_EALIGN); other refusals STC_EINVAL. */
+int stc_cell_dtc_planar_supported(int32_t C, int32_t cin, int32_t h);
+size_t stc_cell_dtc_planar_slots(int64_t rows);
+int stc_cell_dtc_gates_planar_f32(const float* X, int32_t cin, const float* H, const float* SX, const float* SH, const float* Wg, const float* U,
+                                  const float* R, const float* Cand, const float* dHnew, const float* dRH, double* partials, int64_t rows,
+                                  int32_t C, void* stream);
+int stc_cell_dtc_cand_planar_f32(const float* X, int32_t cin, const float* RH, const float* Wc, const float* dY, const float* dBm, double* partials,
+                                 int64_t rows, int32_t C, void* stream);
 
 /* ---- MixedFusion of the learned graph generator (reference STC_GNN.py:246-261, called by MGP_Gen :227-243) ----------------------------
  *   gate = sigmoid(W_A vec(A) + b_A + W_P vec(P) + b_P),   G = gate * A + (1 - gate) * P        D = n^2 entries; W_A, W_P (D, D) row-major

@@ -22,6 +22,10 @@ Beyond the reference:
 * ``STCGNN(..., graph_mode='csr-learned', spatial_graph=As, fusion_rank=r)`` learns
   ``Gs`` on the stored entries of the sparse prior graph (``MGP_Gen_Csr``: any N,
   rank-r fusion over nnz); in grad mode its cells run one autograd node per cell.
+* ``STCGNN(..., graph_mode='csr-category-learned')`` treats ``As`` exactly as ``'csr-fixed'``
+  does and learns the category graph alone (``MGP_Gen_Category``: the generator's category
+  branch); at Chebyshev order 2, hidden 16, C in {32, 64} the cells stay in the cell-graph
+  executor, whose planar backward forms the gradient of ``Gc``.
 
 Inputs must live on a ROCm device; there is no CPU execution path.
 """
@@ -374,6 +378,23 @@ class MGP_Gen_Csr(MGP_Gen):
         return learned_csr_operand(self.graph, G, self.sampled_grad), Gc
 
 
+class MGP_Gen_Category(MGP_Gen):
+    """The category branch of ``MGP_Gen`` alone (``graph_mode='csr-category-learned'``; not in the reference): ``Gc = MixedFusion(C)(Ac, P_c)`` with
+    ``P_c`` from the input window, for a spatial graph that stays fixed -- no N x N fusion exists.  Only ``params_C`` and ``aggreg_C``, under
+    the reference's key names and created in the reference's relative order, so those entries of an ``MGP_Gen`` ``state_dict`` load unchanged.
+    ``forward(X_seq, Ac)`` returns ``Gc``; ``X_seq`` in the node order the parameters were built for (``params_C`` has one row per node)."""
+
+    def __init__(self, num_nodes: int, num_categories: int, hidden_dim: int, alpha: int = 3):
+        nn.Module.__init__(self)
+        self.alpha = alpha
+        self.batch_sharded = False
+        self.params_C = self.init_params(num_nodes, hidden_dim)
+        self.aggreg_C = MixedFusion(num_categories)
+
+    def forward(self, X_seq: torch.Tensor, Ac: torch.Tensor):
+        return self.aggreg_C(Ac, self._learned(X_seq, self.params_C, 3))
+
+
 class STCGNN(nn.Module):
     """Encoder-decoder STC-GNN (reference ``STC_GNN.py:175-207``); the drop-in boundary.
 
@@ -385,7 +406,13 @@ class STCGNN(nn.Module):
     general path: the graph values need a gradient); under ``no_grad`` they take whatever route the predicates give a fixed sparse graph.
     ``csr_cells='fused'`` (csr-learned only; default ``'per-cell'``) prefers the few-category cell executor in grad mode too, which forms the
     value gradient at the stored entries (``stc_graph_grad_csr_f32``): Chebyshev order 2, hidden 16, C <= 16 on the HIP kernel set; where
-    ``small.small_graph_supported`` declines, the per-cell path runs with the same bits as ``'per-cell'``."""
+    ``small.small_graph_supported`` declines, the per-cell path runs with the same bits as ``'per-cell'``.
+
+    ``graph_mode='csr-category-learned'`` (not in the reference): ``As`` is handled exactly as in ``'csr-fixed'`` (``CsrGraph`` or torch sparse
+    tensor, ``reorder_nodes``, plans); the category graph is ``MixedFusion(C)(Ac, P_c)`` from ``MGP_Gen_Category``, with ``P_c`` computed from
+    the window in the caller's node order, before any renumbering.  In grad mode the cells ask the cell-graph executor for the gradient of
+    ``Gc``'s Chebyshev stack (``ops.stc_cell_graph(learn_Tc=True)``: order 2, hidden 16, C in {32, 64}, fp32); other shapes run one autograd
+    node per cell.  Under ``no_grad`` the route is ``'csr-fixed'``'s."""
 
     def __init__(self, num_nodes: int, num_categories: int, Ks: int, Kc: int, input_dim: int, hidden_dim: int,
                  num_layers: int, out_horizon: int, use_bias=True, activation=None,
@@ -398,8 +425,8 @@ class STCGNN(nn.Module):
         if csr_cells == 'fused' and graph_mode != 'csr-learned':
             raise ValueError("csr_cells='fused' needs graph_mode='csr-learned' (the other modes choose their cell route themselves)")
         self.csr_cells = csr_cells              # read at every forward
-        if graph_mode not in ('dense-learned', 'csr-fixed', 'csr-learned'):
-            raise ValueError("graph_mode must be 'dense-learned' (reference semantics), 'csr-fixed' or 'csr-learned'")
+        if graph_mode not in ('dense-learned', 'csr-fixed', 'csr-learned', 'csr-category-learned'):
+            raise ValueError("graph_mode must be 'dense-learned' (reference semantics), 'csr-fixed', 'csr-learned' or 'csr-category-learned'")
         if storage_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError('storage_dtype must be torch.float32 (reference arithmetic) or torch.bfloat16')
         if storage_dtype == torch.bfloat16 and graph_mode != 'csr-fixed':
@@ -422,6 +449,9 @@ class STCGNN(nn.Module):
             if spatial_graph.n != num_nodes:
                 raise ValueError(f'spatial_graph has {spatial_graph.n} nodes, the model {num_nodes}')
             self.mix_graph_pair = MGP_Gen_Csr(spatial_graph, num_categories, hidden_dim, fusion_rank=fusion_rank)
+            self.mix_graph_pair.batch_sharded = batch_sharded
+        elif graph_mode == 'csr-category-learned':
+            self.mix_graph_pair = MGP_Gen_Category(num_nodes, num_categories, hidden_dim)
             self.mix_graph_pair.batch_sharded = batch_sharded
         self.encoder = STC_Encoder(num_nodes, num_categories, Ks, Kc, input_dim, hidden_dim, num_layers,
                                    use_bias, activation, return_all_layers=True)
@@ -450,7 +480,8 @@ class STCGNN(nn.Module):
             self.mix_graph_pair.sampled_grad = self.csr_cells == 'fused'
             Gs, Gc = self.mix_graph_pair(X_seq, As, Ac)                  # Gs: a SpatialOperand on the prior's pattern, in the given node order
         else:
-            Gs, Gc = As, Ac
+            # csr-category-learned: Gc from the window as the caller gave it (the generator's parameters are per node, in the caller's order)
+            Gs, Gc = As, (self.mix_graph_pair(X_seq, Ac) if self.graph_mode == 'csr-category-learned' else Ac)
             if isinstance(Gs, torch.Tensor) and Gs.layout != torch.strided:
                 Gs = _as_csr_graph(Gs)                  # a torch sparse graph gets the same treatment as a CsrGraph (cached on the tensor)
             if self.reorder_nodes and isinstance(Gs, CsrGraph):
@@ -494,11 +525,13 @@ class STCGNN(nn.Module):
             return None
         h = hidden.pop()
         B, T, N, C, cin0 = X.shape
-        if X.requires_grad or not ops.cell_graph_supported(pair.spatial, pair.Tc, self.Ks, C, h, [cin0, h], dtype=X.dtype):
+        # csr-category-learned: the executor is asked for Gc's gradient (it has none to give under no_grad); the other modes call as they always did
+        learn = dict(learn_Tc=True) if self.graph_mode == 'csr-category-learned' else {}
+        if X.requires_grad or not ops.cell_graph_supported(pair.spatial, pair.Tc, self.Ks, C, h, [cin0, h], dtype=X.dtype, **learn):
             return None
         n_layers, horizon = len(enc), self.decoder.out_horizon
         # inputs, then the zero initial states -- as shapes only where the executor runs their cells in the first-step forms (no plane is read)
-        if ops.first_step_route(pair.spatial, pair.Tc, self.Ks, C, h, [cin0, h], dtype=X.dtype):
+        if ops.first_step_route(pair.spatial, pair.Tc, self.Ks, C, h, [cin0, h], dtype=X.dtype, **learn):
             ext = [X[:, t] for t in range(T)] + [ops.zero_state(c.gates.W, (B, c.num_nodes, c.num_categories, c.hidden_dim), X.dtype) for c in enc]
         else:
             ext = [X[:, t] for t in range(T)] + [c.init_hidden(B).to(X.dtype) for c in enc]
@@ -518,7 +551,7 @@ class STCGNN(nn.Module):
                 schedule.append((n_layers + l, x, hs))
         stacks = [(c.gates.W, c.gates.b if c.gates.use_bias else None, c.candi.W, c.candi.b if c.candi.use_bias else None) for c in cells]
         outputs = [did(n_layers - 1, s_) for s_ in range(horizon)]
-        return ops.stc_cell_graph(pair.spatial, pair.Tc, self.Ks, schedule, outputs, ext, stacks)
+        return ops.stc_cell_graph(pair.spatial, pair.Tc, self.Ks, schedule, outputs, ext, stacks, **learn)
 
     def _head(self, H: torch.Tensor) -> torch.Tensor:
         """sigmoid(out_proj(H)).squeeze(-1) (reference STC_GNN.py:206-207).  The two Linears have no nonlinearity

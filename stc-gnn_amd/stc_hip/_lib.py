@@ -22,7 +22,7 @@ from .graph import is_full_pattern
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, 'libstc_hip.so')
 # Mirrors of include/stc_hip.h (#define STC_<name>; tests/test_abi.py compares each, and HipKernels.ACT_AMAX_SLOTS, with the header)
-ABI_VERSION = 42
+ABI_VERSION = 43
 FMT_BF16X3, FMT_F16X2 = 0, 1          # operand formats of the split-operand matrix-core kernels
 MAX_K = 4
 STC_ELIMIT = -3            # include/stc_hip.h: a size beyond a kernel limit
@@ -123,6 +123,10 @@ _ABI = {
     'stc_graph_grad_f32': (_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _p]),
     'stc_set_graph_grad_form': (_int, [_i32]),
     'stc_graph_grad_csr_f32': (_int, [_p, _p, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _p]),
+    'stc_cell_dtc_planar_supported': (_int, [_i32, _i32, _i32]),
+    'stc_cell_dtc_planar_slots': (_size, [_i64]),
+    'stc_cell_dtc_gates_planar_f32': (_int, [_p, _i32] + [_p] * 10 + [_i64, _i32, _p]),
+    'stc_cell_dtc_cand_planar_f32': (_int, [_p, _i32] + [_p] * 5 + [_i64, _i32, _p]),
     'stc_mix_grad_f32': (_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _p]),
     'stc_mixed_fusion_workspace_bytes': (_size, [_i32, _i32]),
     'stc_mixed_fusion_fwd_f32': (_int, [_p] * 8 + [_i32, _p]),
@@ -925,6 +929,47 @@ class HipKernels:
         self._launch('stc_cell_gates_bwd_planar_f32', H, _ptr(X), _ptr(H), _ptr(SX), _ptr(SH), _ptr(Tc), _ptr(W), _ptr(dRH), _ptr(Cand),
                      _ptr(U), _ptr(Rg), _ptr(dHnew), zp, _ptr(dW), _ptr(db), _ptr(dH), self.operand_format,
                      self._act_amax('planar', act_amax, 4, H), _ptr(ws), ws.numel(), R, Cc, cin + h, h, nbytes=nbytes)
+
+    # ---- dT_c of the planar cells: the category graph's gradient on a fixed sparse spatial graph (ABI v43) ----
+    #: ``cell_dtc_gates`` / ``cell_dtc_cand`` exist: what ``ops.stc_cell_graph(learn_Tc=True)`` asks before it differentiates ``Tc`` in the general
+    #: executor (on the class, so ``for_graph`` views have it; the CPU twin has no such attribute and keeps the per-cell route)
+    cell_dtc_planar = True
+
+    def cell_dtc_planar_supported(self, Cc, cin, h) -> bool:
+        return bool(self.lib.stc_cell_dtc_planar_supported(Cc, cin, h))
+
+    def cell_dtc_slots(self, rows) -> int:
+        """Slots of the float64 ``partials`` (slots, C, C) buffer that the dT_c launches over ``rows`` rows add into."""
+        return int(self.lib.stc_cell_dtc_planar_slots(rows))
+
+    def _dtc_checked(self, what, X, state_planes, W, Ho, partials):
+        R, Cc, h = state_planes[0].shape
+        cin = X.shape[-1]
+        if not self.cell_dtc_planar_supported(Cc, cin, h):
+            raise StcError(f'{what}: C in (32, 64), hidden 16, input plane 16 or 1..4 columns wide; got C={Cc} h={h} cin={cin}')
+        _tensor(what + '.X', X, (R, Cc, cin))
+        for i, t in enumerate(state_planes):
+            _tensor(f'{what}.plane[{i}]', t, (R, Cc, h))
+        _tensor(what + '.W', W, (4 * (cin + h), Ho))
+        _tensor(what + '.partials', partials, (self.cell_dtc_slots(R), Cc, Cc), torch.float64)
+        self._same_device(X, *state_planes, W, partials)
+        return R, Cc, cin
+
+    def cell_dtc_gates(self, X, H, SX, SH, Wg, U, Rg, Cand, dHnew, dRH, partials):
+        """The gates convolution's share of dT_c[1] ADDED to ``partials`` (stc_cell_dtc_gates_planar_f32): planes as ``cell_gates_bwd_planar``
+        reads them, the gate gradient re-formed in registers.  Nine planes read, nothing but ``partials`` written."""
+        R, Cc, cin = self._dtc_checked('cell_dtc_gates', X, (H, SH, U, Rg, Cand, dHnew, dRH), Wg, 32, partials)
+        _tensor('cell_dtc_gates.SX', SX, (R, Cc, cin))
+        self._same_device(X, SX)
+        self._launch('stc_cell_dtc_gates_planar_f32', H, _ptr(X), cin, _ptr(H), _ptr(SX), _ptr(SH), _ptr(Wg), _ptr(U), _ptr(Rg), _ptr(Cand), _ptr(dHnew),
+                     _ptr(dRH), _ptr(partials), R, Cc, nbytes=4 * R * Cc * (2 * cin + 7 * 16))
+
+    def cell_dtc_cand(self, X, RH, Wc, dY, dBm, partials):
+        """The candidate convolution's share of dT_c[1] ADDED to ``partials`` (stc_cell_dtc_cand_planar_f32): dY = dHnew U (1 - Cand^2) and
+        dBm = S^T dY are the planes of the two-launch planar backward.  Four planes read."""
+        R, Cc, cin = self._dtc_checked('cell_dtc_cand', X, (RH, dY, dBm), Wc, 16, partials)
+        self._launch('stc_cell_dtc_cand_planar_f32', RH, _ptr(X), cin, _ptr(RH), _ptr(Wc), _ptr(dY), _ptr(dBm), _ptr(partials), R, Cc,
+                     nbytes=4 * R * Cc * (cin + 3 * 16))
 
     # ---- the whole backward of a planar cell step in one launch ----------------------------------------
     def cell_bwd_planar_supported(self, Cc, h) -> bool:

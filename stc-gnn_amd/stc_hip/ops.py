@@ -538,6 +538,7 @@ _POST_AGG = True         # candidate convolution as Y = A + S.Bm (narrow SpMM af
 _SMALL = True            # small graphs (N*C rows per sample fit the caches, C <= 16): one launch per cell step and direction
 _RING2 = True            # state gradient + transpose aggregation of dY in one launch where the graph has a two-ring plan (no dY plane)
 _RING2_FWD = True        # ... and the forward's blend + aggregation of the new state (stc_ring2_blend_f32)
+_DTC = True              # a learned category graph on a fixed sparse spatial graph inside this executor: dT_c from the planar cells (``learn_Tc=``; False: one node per cell)
 _FIRST_STEP = True       # cells on the zero initial state (a layer's first time step) in their first-step forms: no H, S.H, R planes, no dH, dS.H
 _SUM_GATHERS, _CHAIN_FIRST_ADD = 2, 2     # kernel limits, not switches: planes that stc_spmm_sum_* / the two-ring launches gather through S (X, X2); first-ring addends of stc_ring2_chain_f32
 
@@ -550,11 +551,13 @@ def _first_step_kernels(k, dtype, C: int, h: int) -> bool:
     return bool(_FIRST_STEP and dtype == torch.float32 and getattr(k, 'first_step_cells', False) and k.cell_first_supported(C, h))
 
 
-def first_step_route(op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widths, dtype=torch.float32) -> bool:
+def first_step_route(op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widths, dtype=torch.float32, learn_Tc: bool = False) -> bool:
     """Whether ``stc_cell_graph`` runs the PLANAR_ONE_BWD cells of this problem whose state is a zero initial state in their first-step forms
     (fp32 planes, order 2, a kernel set with ``first_step_cells``, not the few-category executor): the caller then passes ``zero_state`` views
-    instead of planes of zeros."""
+    instead of planes of zeros.  Never while the executor differentiates ``Tc`` (``learn_Tc``): its cells are PLANAR, which has no such form."""
     k = kernels()
+    if _learns_tc(learn_Tc, Tc):
+        return False
     return Ks == 2 and _first_step_kernels(k, dtype, C, h) and not (_SMALL and small_graph_supported(k, op, Tc, Ks, C, h, x_widths, dtype))
 
 
@@ -572,15 +575,33 @@ def _is_zero_state(t: torch.Tensor) -> bool:
     return z is not None and t.dim() == 4 and not any(t.stride()) and t.untyped_storage().data_ptr() == z.untyped_storage().data_ptr()
 
 
-def cell_graph_supported(op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widths, dtype=torch.float32) -> bool:
+def _learns_tc(learn_Tc: bool, Tc) -> bool:
+    """Whether a call asks the general executor for the category graph's gradient: the caller's word, grad mode, a ``Tc`` that requires grad."""
+    return bool(learn_Tc and torch.is_grad_enabled() and Tc.requires_grad)
+
+
+def _dtc_route(k, op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widths, dtype) -> bool:
+    """Whether the general executor can differentiate ``Tc`` for this problem (``stc_cell_graph(learn_Tc=True)``): the switch, fp32 planes,
+    order 2, a kernel set with the planar cells' dT_c kernels that takes every input width, every cell in ``_Form.PLANAR`` (the two-launch
+    backward, in which dY, dBm and dRH exist), a spatial graph that needs no gradient."""
+    widths = sorted(set(x_widths))
+    return bool(_DTC and dtype == torch.float32 and Ks == 2 and Tc.shape[0] == 2 and getattr(k, 'cell_dtc_planar', False)
+                and not op.fwd_val.requires_grad and all(k.cell_dtc_planar_supported(C, w, h) for w in widths)
+                and all(f is _Form.PLANAR for f in _cell_forms(k, Ks, 2, C, h, widths, False, learn_Tc=True)))
+
+
+def cell_graph_supported(op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widths, dtype=torch.float32, learn_Tc: bool = False) -> bool:
     """Whether ``stc_cell_graph`` can run a schedule: matrix-core cell kernels for every row width that occurs, hidden 16,
     graphs that need no gradient (``csr-fixed`` mode).  ``dtype`` = storage type of the state tensors: bfloat16 runs the
-    all-planar bf16 kernel set (Ks = Kc = 2; inputs 16 or 1..4 columns wide)."""
+    all-planar bf16 kernel set (Ks = Kc = 2; inputs 16 or 1..4 columns wide).  ``learn_Tc``: the caller wants the gradient of a ``Tc`` that
+    requires grad from the general executor (``graph_mode='csr-category-learned'``); the answer is then ``_dtc_route``'s."""
     if not _CELL_GRAPH or h != 16:
         return False
     k = kernels()
     if _SMALL and small_graph_supported(k, op, Tc, Ks, C, h, x_widths, dtype):
         return True                                                   # small graphs, fixed or learned: one launch per cell step (stc_hip/small.py)
+    if _learns_tc(learn_Tc, Tc):
+        return _dtc_route(k, op, Tc, Ks, C, h, x_widths, dtype)
     if Tc.requires_grad or op.fwd_val.requires_grad:
         return False
     if dtype == torch.bfloat16:
@@ -616,9 +637,10 @@ class _Form(enum.Enum):
 _FORM_METHODS = {_Form.PLANAR3: ('planar3', 'planar3'), _Form.PLANAR_ONE_BWD: ('planar', 'planar_one_bwd'), _Form.PLANAR: ('planar', 'planar'),
                  _Form.ROWS_POST: ('rows_cell', 'rows_cell'), _Form.ROWS_SLABS: ('rows_cell', 'rows_cell')}
 
-def _cell_forms(k, Ks: int, Kc: int, C: int, h: int, cin, bf16: bool):
+def _cell_forms(k, Ks: int, Kc: int, C: int, h: int, cin, bf16: bool, learn_Tc: bool = False):
     """The ``_Form`` of every cell from its input width ``cin[j]``: planar where the planar kernels take the shape -- 16 + 16 columns, or
-    (layer 0) a narrow input plane of 1..4 columns beside the 16 state columns -- else interleaved rows."""
+    (layer 0) a narrow input plane of 1..4 columns beside the 16 state columns -- else interleaved rows.  ``learn_Tc``: the backward forms dT_c,
+    from planes that only the two-launch backward holds -- PLANAR where it would be PLANAR_ONE_BWD."""
     planar2 = (_PLANAR and _POST_AGG and Ks == 2 and k.cell_planar_supported(Ks, Kc, C, h)
                and k.node_post_supported(Ks, Kc, C, 2 * h, h))
     post20 = bool(planar2) and k.node_post_supported(Ks, Kc, C, 20, h)
@@ -631,7 +653,7 @@ def _cell_forms(k, Ks: int, Kc: int, C: int, h: int, cin, bf16: bool):
         elif planar2 and (w == h or (post20 and 1 <= w <= 4)):
             # the one-launch backward (stc_cell_bwd_planar_f32) forms R*H itself
             one_bwd = k.cell_bwd_planar_supported(C, h, w) if bf16 else k.cell_bwd_planar_supported(C, h)
-            forms.append(_Form.PLANAR_ONE_BWD if one_bwd else _Form.PLANAR)
+            forms.append(_Form.PLANAR_ONE_BWD if one_bwd and not learn_Tc else _Form.PLANAR)
         else:                                                       # (Ks = 1 has no S.Bm term: slabs)
             post = Ks > 1 and _POST_AGG and k.node_post_supported(Ks, Kc, C, w + h + (-(w + h)) % 4, h)
             forms.append(_Form.ROWS_POST if post else _Form.ROWS_SLABS)
@@ -925,8 +947,10 @@ class _BackwardPass(_Pass):
     """... and, in the backward, what every state is still owed (``owes``: one ``_Ledger`` record per state, filled by its consumers through ``finish`` /
     ``leave`` / ``claim``, emptied by ``owed`` / ``owed_ring2`` when its own cell runs) and the parameter gradients (``params``: ``_ParamGrads``)."""
 
-    def __init__(self, k, op: SpatialOperand, Ks: int, Tc, schedule, stacks, cin, forms, dims, bf16: bool, zmax_all):
+    def __init__(self, k, op: SpatialOperand, Ks: int, Tc, schedule, stacks, cin, forms, dims, bf16: bool, zmax_all, learn_Tc: bool = False):
         super().__init__(k, op, Ks, Tc, schedule, cin, forms, dims, bf16, zmax_all, (op.bwd_rowptr, op.bwd_colidx, op.bwd_val, op.bwd_plan))
+        # a learned category graph: every PLANAR cell's two dT_c launches ADD into one float64 buffer, zeroed here, folded once (``_dtc_fold``)
+        self.dtc = torch.zeros(k.cell_dtc_slots(self.B * self.N), self.C, self.C, dtype=torch.float64, device=Tc.device) if learn_Tc else None
         # state gradient sums fused with a transpose aggregation where the graph has a two-ring plan (stc_ring2_sum_f32 / _chain_f32)
         self.ring2 = _RING2 and not bf16 and op.bwd_ring2 is not None and k.ring2_fits(self.B, self.N, self.C, self.h)
         self.owes, self.params = _Ledger(), _ParamGrads(stacks, schedule)
@@ -1049,6 +1073,9 @@ class _BackwardPass(_Pass):
         else:
             k.node_post_bwd(*rows((RH,)), Tc, Wc, *rows((dY, dBm, dRH)), dWc, dbc, X2=Xp.view(-1, self.C, self.cin[j]), **post_kw)
             planes = [None, None] + rows((dHd, dSH))
+        if self.dtc is not None:                                    # dT_c while the planes are alive: dY, dBm here, dRH as the launch above left it
+            k.cell_dtc_cand(*rows((Xp, RH)), Wc, *rows((dY, dBm)), self.dtc)
+            k.cell_dtc_gates(*rows((Xp, Hprev, SXp, SHp)), Wg, *rows((U, Rg, Cand, dHnew, dRH)), self.dtc)
         del dY, dBm
         # (dH = None: the kernel adds the prologue's share into the H plane's gradient)
         k.cell_gates_bwd_planar(*rows((Xp, Hprev, SXp, SHp)), Tc, Wg, *rows((dRH, Cand, U, Rg, dHnew)), planes, dWg, dbg, None, **gates_kw)
@@ -1093,7 +1120,14 @@ class _BackwardPass(_Pass):
         self.params.add(s_id, (dWg, dbg, dWc, dbc))
 
 
-def _begin_forward(op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, tensors, forward_only: bool = False):
+def _dtc_fold(partials, Tc):
+    """dT_c (2, C, C) in ``Tc``'s type from the float64 slots the dT_c launches added into: dTc[1] = their sum, dTc[0] = 0 (T_0 = I is a constant)."""
+    dTc = torch.zeros_like(Tc)
+    dTc[1].copy_(partials.sum(0))
+    return dTc
+
+
+def _begin_forward(op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, tensors, forward_only: bool = False, learn_Tc: bool = False):
     """What both routes of ``stc_cell_graph`` do before the first launch: kernel set, contiguous operands, one form per cell, the output stack.
     Returns (pass, parameter sets, output stack, output cell -> slot)."""
     k = kernels().for_graph(_amplification(op, Ks))              # (a heavy graph: the 24-bit operand format, _lib.HEAVY_ROW_SUM)
@@ -1105,7 +1139,7 @@ def _begin_forward(op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, T
     h = 16
     B, N, C = ext[0].shape[:3]
     cin = [ext[x[1]].shape[-1] if x[0] == 'ext' else h for _, x, _ in schedule]
-    forms = _cell_forms(k, Ks, Tc.shape[0], C, h, cin, bf16)
+    forms = _cell_forms(k, Ks, Tc.shape[0], C, h, cin, bf16, learn_Tc)
     if bf16 and not all(f.planar for f in forms):
         raise ValueError('stc_cell_graph: bfloat16 states need an all-planar schedule (Ks = 2, inputs 16 or 1..4 columns wide)')
     p = _ForwardPass(k, op, Ks, Tc, fwd_val, schedule, ext, cin, forms, bf16, forward_only)
@@ -1147,7 +1181,8 @@ class _StcCellGraph(Function):
 
     @staticmethod
     def forward(ctx, op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, *tensors):
-        p, stacks, out_stack, out_slot = _begin_forward(op, Ks, schedule, outputs, n_ext, Tc, fwd_val, tensors)
+        learn_Tc = ctx.needs_input_grad[5]                           # (``stc_cell_graph`` lets a ``Tc`` that requires grad through only with ``learn_Tc``)
+        p, stacks, out_stack, out_slot = _begin_forward(op, Ks, schedule, outputs, n_ext, Tc, fwd_val, tensors, learn_Tc=learn_Tc)
         saved = []
         for j, (s_id, _, _) in enumerate(schedule):
             saved += p.cell(j, stacks[s_id], _alias(out_stack, out_slot[j]) if j in out_slot else None)
@@ -1171,7 +1206,8 @@ class _StcCellGraph(Function):
         cells = []
         for f in forms:                                              # what each cell saved, by its form
             cells, sv = cells + [sv[:f.saved(Ks)]], sv[f.saved(Ks):]
-        p = _BackwardPass(k, op, Ks, Tc, schedule, stacks, cin, forms, dims, bf16, ctx.zmax_all)
+        learn_Tc = ctx.needs_input_grad[5]
+        p = _BackwardPass(k, op, Ks, Tc, schedule, stacks, cin, forms, dims, bf16, ctx.zmax_all, learn_Tc)
         grad_stack = _c(grad_stack)
         for i, j in enumerate(outputs):
             p.owes.finish(j, grad_stack[i])                          # read-only here: sums go to fresh buffers
@@ -1181,10 +1217,10 @@ class _StcCellGraph(Function):
             getattr(p, _FORM_METHODS[forms[j]][1])(j, *stacks[schedule[j][0]], cells[j])
         flat = p.params.result()
         n_ext = len(ctx.needs_input_grad) - 7 - len(flat)
-        return (None,) * 7 + (None,) * n_ext + tuple(flat)
+        return (None,) * 5 + (_dtc_fold(p.dtc, Tc) if learn_Tc else None, None) + (None,) * n_ext + tuple(flat)
 
 
-def stc_cell_graph(op: SpatialOperand, Tc, Ks: int, schedule, outputs, ext, stacks):
+def stc_cell_graph(op: SpatialOperand, Tc, Ks: int, schedule, outputs, ext, stacks, learn_Tc: bool = False):
     """Run a schedule of STC_Cells (see ``_StcCellGraph``).  ``ext``: external (B,N,C,*) tensors (inputs, initial states;
     they get no gradient); ``stacks``: [(Wg, bg, Wc, bc)] parameter sets; returns the new states of the ``outputs`` cells
     stacked along a new leading axis, (len(outputs), B, N, C, h) -- written in place by the kernels, no stack pass.
@@ -1198,14 +1234,26 @@ def stc_cell_graph(op: SpatialOperand, Tc, Ks: int, schedule, outputs, ext, stac
     only while it requires grad, or with grad mode off (``small.small_graph_supported``).  In grad mode with that graph frozen the call
     goes to the general executor, which has cell kernels for C in {16, 32, 64} only: on few categories it then fails in its first launch's
     host check (``StcError``: shape not on the fused path) -- loud, but without naming the graph.  Ask ``cell_graph_supported`` first, as
-    the module does (it then runs one node per cell)."""
+    the module does (it then runs one node per cell).
+
+    ``learn_Tc=True`` (``graph_mode='csr-category-learned'``): a ``Tc`` that requires grad is differentiated by the general executor -- fp32
+    planes, order 2, C in {32, 64}, every cell in ``_Form.PLANAR``, whose two-launch backward also adds the cell's share of dT_c[1] to one float64
+    buffer (``stc_cell_dtc_gates_planar_f32`` / ``_cand_planar_f32``); ``cell_graph_supported(..., learn_Tc=True)`` tells beforehand, a problem
+    outside it raises ``ValueError``.  ``op.fwd_val`` is refused as before.  With the default every answer and refusal is unchanged."""
     ext = list(ext)
     _refuse_differentiable(ext=ext)
     k = kernels()
     if _SMALL and small_graph_supported(k, op, Tc, Ks, ext[0].shape[2], 16, {ext[x[1]].shape[-1] if x[0] == 'ext' else 16 for _, x, _ in schedule},
                                         ext[0].dtype):
         return stc_small_graph(k, op, Tc, Ks, schedule, outputs, ext, stacks)
-    _refuse_differentiable(Tc=Tc, fwd_val=op.fwd_val)
+    if _learns_tc(learn_Tc, Tc):
+        _refuse_differentiable(fwd_val=op.fwd_val)
+        widths = {ext[x[1]].shape[-1] if x[0] == 'ext' else 16 for _, x, _ in schedule}
+        if not _dtc_route(k.for_graph(_amplification(op, Ks)), op, Tc, Ks, ext[0].shape[2], 16, widths, ext[0].dtype):
+            raise ValueError('stc_cell_graph: learn_Tc needs fp32 planes, Chebyshev order 2, C in (32, 64), inputs 16 or 1..4 columns wide and a kernel '
+                             'set with the planar dT_c kernels (cell_graph_supported(..., learn_Tc=True) tells beforehand; stc_cell differentiates every input)')
+    else:
+        _refuse_differentiable(Tc=Tc, fwd_val=op.fwd_val)
     flat = [p for st in stacks for p in st]
     if not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in (Tc, op.fwd_val, *ext, *flat)):
         with torch.no_grad():                                        # no backward will follow: nothing saved, nothing stored for one (``_forward_only``)

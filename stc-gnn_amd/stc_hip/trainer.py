@@ -48,7 +48,7 @@ class Trainer:
             s_adj = CsrGraph.from_dense(torch.from_numpy(np.asarray(s_adj)).float())      # the stored (non-zero) entries are the learned pattern
         self.prior_graph = [s_adj if isinstance(s_adj, CsrGraph) else torch.from_numpy(np.asarray(s_adj)).float().to(dev),
                             torch.from_numpy(np.asarray(data['c_cor'])).float().to(dev)]
-        if isinstance(s_adj, CsrGraph) and graph_mode not in ('csr-fixed', 'csr-learned'):
+        if isinstance(s_adj, CsrGraph) and graph_mode not in ('csr-fixed', 'csr-learned', 'csr-category-learned'):
             raise ValueError("a CsrGraph prior graph needs graph_mode='csr-fixed' (the learned-graph mode mixes a dense prior)")
         if params.get('model', 'STC-GNN') != 'STC-GNN':
             raise NotImplementedError('Invalid model name.')
@@ -59,11 +59,13 @@ class Trainer:
         fusion_rank = params.get('fusion_rank')
         if fusion_rank is not None and graph_mode == 'csr-fixed':
             raise ValueError("params['fusion_rank'] is for the learned graphs (graph_mode='dense-learned' / 'csr-learned'); 'csr-fixed' has no MixedFusion")
+        if fusion_rank is not None and graph_mode == 'csr-category-learned':
+            raise ValueError("params['fusion_rank'] is for a learned spatial graph; 'csr-category-learned' learns the C x C category graph alone (no N x N fusion exists)")
         self.model = STCGNN(num_nodes=params['H'] * params['W'], num_categories=params['C'],
                             Ks=params['cheby_order'], Kc=params['cheby_order'], input_dim=1,
                             hidden_dim=params['hidden_dim'], num_layers=params['nn_layers'],
                             out_horizon=params['pred_len'], graph_mode=graph_mode,
-                            batch_sharded=self.world > 1 and graph_mode in ('dense-learned', 'csr-learned'),
+                            batch_sharded=self.world > 1 and graph_mode in ('dense-learned', 'csr-learned', 'csr-category-learned'),
                             fusion_rank=None if fusion_rank is None else int(fusion_rank),
                             spatial_graph=s_adj if graph_mode == 'csr-learned' else None,
                             csr_cells=params.get('csr_cells', 'per-cell')).to(dev)      # csr-learned: 'fused' prefers the few-category cell executor
@@ -73,9 +75,9 @@ class Trainer:
         self.hip_graph = bool(hip_graph) and self.world == 1 and str(dev).startswith('cuda')
         # torch.optim.Adam, with parameters of >= 64 MiB (MixedFusion's two matrices in the learned-graph mode) updated by stc_adam_f32 (optim.py)
         # (csr-learned: the capturable form eager as well, so that eager and replayed training take the same Adam arithmetic and end in the same
-        # parameters bit for bit; the modes that existed before keep torch's host-scalar form when they run eager)
+        # parameters bit for bit, and so for csr-category-learned; the modes that existed before keep torch's host-scalar form when they run eager)
         self.optimizer = StcAdam(self.model.parameters(), lr=params['learn_rate'], weight_decay=params['decay_rate'],
-                                 capturable=self.hip_graph or (graph_mode == 'csr-learned' and str(dev).startswith('cuda')))
+                                 capturable=self.hip_graph or (graph_mode in ('csr-learned', 'csr-category-learned') and str(dev).startswith('cuda')))
         self._captured = {}                                           # batch shape -> [eager steps seen, graph, static x, static y, static loss]
         self._capture_shape = None                                    # only the FIRST batch shape seen (the full batch) is captured
         self._capture_stream = torch.cuda.Stream(dev) if self.hip_graph else None

@@ -34,9 +34,10 @@ ap.add_argument('-dr', '--decay_rate', type=float, default=1e-4)
 ap.add_argument('-epoch', '--num_epochs', type=int, default=100)
 ap.add_argument('-test', '--test_only', type=int, default=0, choices=[0, 1])
 # beyond Main.py: fixed sparse graphs (any N) and a synthetic incident series, so that the trainer runs at sizes the SF file does not have
-ap.add_argument('-graph', '--graph_mode', default='dense-learned', choices=['dense-learned', 'csr-fixed', 'csr-learned'],
+ap.add_argument('-graph', '--graph_mode', default='dense-learned', choices=['dense-learned', 'csr-fixed', 'csr-learned', 'csr-category-learned'],
                 help="dense-learned = the reference's learned graphs (MGP_Gen, N <~ 300); csr-fixed = the prior graph used as given, row-normalised; "
-                     "csr-learned = graphs learned on the stored entries of the sparse prior graph (any N; rank-r fusion, -rank, default 16)")
+                     "csr-learned = graphs learned on the stored entries of the sparse prior graph (any N; rank-r fusion, -rank, default 16); "
+                     "csr-category-learned = the prior spatial graph as in csr-fixed, the category graph learned (any N)")
 ap.add_argument('-synthetic', '--synthetic', type=int, nargs=4, metavar=('H', 'W', 'C', 'T'), default=None,
                 help='train on a Bernoulli(0.1635) incident series of T steps on an H x W queen grid with C categories instead of a city file')
 ap.add_argument('-stride', '--time_slice', type=int, default=None, help=argparse.SUPPRESS)
@@ -61,7 +62,7 @@ if syn is None:
     data = sdata.load_incidents(os.path.join(params['input_dir'], f'{params["city"]}-incidents-{params["time_slice"]}h.npz'))
 else:
     params.update(H=syn[0], W=syn[1], C=syn[2], time_slice=ts or 4)
-    data = sdata.synthetic_incidents(*syn, sparse_graph=params['graph_mode'] in ('csr-fixed', 'csr-learned'))
+    data = sdata.synthetic_incidents(*syn, sparse_graph=params['graph_mode'] in ('csr-fixed', 'csr-learned') or params['graph_mode'] == 'csr-category-learned')
 loaders = sdata.get_data_loader(params, data, params['obs_len'], params['pred_len'], params['split_ratio'])
 trainer = Trainer(params, data, graph_mode=params.pop('graph_mode'), hip_graph=bool(params.pop('hip_graph')))
 if not params['test_only']:
