@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define STC_ABI_VERSION 43
+#define STC_ABI_VERSION 44
 #define STC_MAX_K 4          /* highest Chebyshev order (Ks, Kc) the node kernels accept */
 
 /* Operand formats of the split-operand matrix-core kernels (C = 32 / 64, hidden 16).  Every fp32 operand is split into low-precision
@@ -785,6 +785,31 @@ int stc_cell_dtc_gates_planar_f32(const float* X, int32_t cin, const float* H, c
                                   int32_t C, void* stream);
 int stc_cell_dtc_cand_planar_f32(const float* X, int32_t cin, const float* RH, const float* Wc, const float* dY, const float* dBm, double* partials,
                                  int64_t rows, int32_t C, void* stream);
+
+/* The value gradient of a learned spatial graph on a sparse pattern from the PLANAR cells of the cell-graph executor (ABI v44; graph_mode
+ * 'csr-learned' with csr_cells = 'fused' at C in {32, 64}).  A planar cell applies S three times (S.X, S.H, the candidate's A + S.Bm), so at entry
+ * e = (i, j) of the CSR of Gs^T:   dval[e] = sum_cells sum_b < dSX[b][i], X[b][j] > + < dSH[b][i], H[b][j] > + < dY[b][i], Bm[b][j] >.
+ *
+ * stc_graph_grad_csr_pairs_f32 (csrc/stc_graph_grad_csr_pairs.hip): the sampled product of stc_graph_grad_csr_f32 over n_pairs = 1..3 pairs of planes,
+ *   acc[e] += sum_{p < n_pairs} sum_{b < batch} sum_{f < F[p]} A[p][b][i(e)][f] * B[p][b][colidx[e]][f]        e in [rowptr[i], rowptr[i + 1])
+ * A, B, F: HOST arrays of n_pairs device pointers / widths; A[p], B[p] contiguous (batch, n_rows, F[p]) fp32 planes, F[p] a multiple of 4 in
+ * [4, 1024], unequal widths in one launch allowed.  acc (nnz float64) is ADDED TO (the caller zeroes it once per backward pass).  One wave per
+ * row, every entry owned by exactly one wave: no atomics; per (pair, sample, entry) a lane's share is an fp32 fmaf chain in a fixed order,
+ * float64 from there on (over the samples, the pairs in order, then the wave): bitwise reproducible.  Rows of any length, rows without
+ * entries; nothing outside [0, nnz) of acc is written, no operand is.  nnz == 0, batch == 0 or n_rows == 0 launches nothing.  Non-finite values
+ * are not masked: a NaN in row i of A[p] reaches the entries of row i, in row j of B[p] the entries with column j, and nothing else changes a
+ * bit.  Planes 16-byte aligned, acc 8-byte, rowptr / colidx 4-byte (STC_EALIGN); other refusals STC_EINVAL, all before any HIP call.
+ *
+ * stc_cell_dsx_narrow_planar_f32 (csrc/stc_cell_dsx_narrow.hip): the d(S.x) plane of a planar cell whose input plane is NARROW (cin = 1..4; layer 0),
+ * which stc_cell_gates_bwd_planar_f32 does not form because the input needs no gradient.  Order 2, hidden 16, C in {32, 64}; Wg (4 L, 32),
+ * L = cin + 16, block (n, kc) as above; Tc (2, C, C); dG the gate gradient exactly as stc_cell_dtc_gates_planar_f32 re-forms it:
+ *   dSx[r][c][l] = sum_o dG[r][c][o] Wg[block (1, 0)][l][o] + sum_d Tc[1][c][d] sum_o dG[r][d][o] Wg[block (1, 1)][l][o]        l < cin
+ * dSx (rows, C, cin) is WRITTEN, nothing else.  fp32 fmaf throughout, no atomics, one owner per element.  rows == 0 launches nothing.
+ * State-sized planes 16-byte aligned, Wg / Tc / dSx 4-byte (STC_EALIGN); other refusals STC_EINVAL, before any HIP call. */
+int stc_graph_grad_csr_pairs_f32(const int32_t* rowptr, const int32_t* colidx, int32_t n_rows, int32_t nnz, const float* const* A,
+                                 const float* const* B, const int32_t* F, int32_t n_pairs, int32_t batch, double* acc, void* stream);
+int stc_cell_dsx_narrow_planar_f32(const float* H, const float* Wg, const float* Tc, const float* U, const float* R, const float* Cand,
+                                   const float* dHnew, const float* dRH, float* dSx, int32_t cin, int64_t rows, int32_t C, void* stream);
 
 /* ---- MixedFusion of the learned graph generator (reference STC_GNN.py:246-261, called by MGP_Gen :227-243) ----------------------------
  *   gate = sigmoid(W_A vec(A) + b_A + W_P vec(P) + b_P),   G = gate * A + (1 - gate) * P        D = n^2 entries; W_A, W_P (D, D) row-major

@@ -405,8 +405,10 @@ class STCGNN(nn.Module):
     renumbered (entry order defines parameter order); float32 storage only.  In grad mode the cells run one autograd node per cell (the
     general path: the graph values need a gradient); under ``no_grad`` they take whatever route the predicates give a fixed sparse graph.
     ``csr_cells='fused'`` (csr-learned only; default ``'per-cell'``) prefers the few-category cell executor in grad mode too, which forms the
-    value gradient at the stored entries (``stc_graph_grad_csr_f32``): Chebyshev order 2, hidden 16, C <= 16 on the HIP kernel set; where
-    ``small.small_graph_supported`` declines, the per-cell path runs with the same bits as ``'per-cell'``.
+    value gradient at the stored entries (``stc_graph_grad_csr_f32``): Chebyshev order 2, hidden 16, C <= 16 on the HIP kernel set.  At C in
+    {32, 64} (order 2, hidden 16, fp32) ``'fused'`` runs the general cell-graph executor as ONE autograd node that forms both gradients: the
+    spatial values' at the stored entries from its planar cells (``stc_graph_grad_csr_pairs_f32``, ``ops._dval_route``) and ``Gc``'s Chebyshev
+    stack's (``learn_Tc=True``).  Where both executors decline, the per-cell path runs with the same bits as ``'per-cell'``.
 
     ``graph_mode='csr-category-learned'`` (not in the reference): ``As`` is handled exactly as in ``'csr-fixed'`` (``CsrGraph`` or torch sparse
     tensor, ``reorder_nodes``, plans); the category graph is ``MixedFusion(C)(Ac, P_c)`` from ``MGP_Gen_Category``, with ``P_c`` computed from
@@ -526,7 +528,9 @@ class STCGNN(nn.Module):
         h = hidden.pop()
         B, T, N, C, cin0 = X.shape
         # csr-category-learned: the executor is asked for Gc's gradient (it has none to give under no_grad); the other modes call as they always did
-        learn = dict(learn_Tc=True) if self.graph_mode == 'csr-category-learned' else {}
+        # csr-learned with csr_cells='fused': both graphs are learned -- the executor is asked for Gc's gradient too (C in {32, 64}; ``ops._dval_route``)
+        fused = self.graph_mode == 'csr-learned' and self.csr_cells == 'fused'
+        learn = dict(learn_Tc=True) if self.graph_mode == 'csr-category-learned' or fused else {}
         if X.requires_grad or not ops.cell_graph_supported(pair.spatial, pair.Tc, self.Ks, C, h, [cin0, h], dtype=X.dtype, **learn):
             return None
         n_layers, horizon = len(enc), self.decoder.out_horizon

@@ -15,15 +15,15 @@
 // thread's FLOAT64 accumulator.  The next row's planes are requested before the current row's products.  After its last row the workgroup ADDS
 // its accumulators to its own slot of `partials` (slots, C, C): no atomics, one fixed order -- bitwise reproducible; the caller zeroes the
 // buffer once, every launch of a backward pass adds, one sum over the slots finishes dT_c[1].
-#include "stc_common.h"
+#include "stc_cell_dtc_gate.h"
 
 namespace {
 
-using v4f = __attribute__((ext_vector_type(4))) float;
+using stc_dtc::v4f;
 constexpr int DTC_RUN = 256;               // consecutive rows of one workgroup = rows per slot of `partials`
 constexpr int DTC_THREADS = 256;
-constexpr int DTC_H = 16, DTC_COLS = 32;   // hidden width; gradient columns per category (gates: update | reset; candidate: dY | dBm)
-constexpr int DTC_GS = DTC_COLS + 4;       // LDS row stride of the V and gradient tiles (16 rows land on 16 different banks of four)
+constexpr int DTC_H = stc_dtc::H, DTC_COLS = stc_dtc::COLS;   // hidden width; gradient columns per category (gates: update | reset; candidate: dY | dBm)
+constexpr int DTC_GS = stc_dtc::GS;        // LDS row stride of the V and gradient tiles (16 rows land on 16 different banks of four)
 
 struct DtcPlanes {
     const float* x[2];        // input planes (rows, C, cin): X, SX (candidate: X)
@@ -60,6 +60,7 @@ __global__ __launch_bounds__(DTC_THREADS) void dtc_planar_kernel(DtcPlanes p, co
     v4f hr[HK], xr[XK > 0 ? XK : 1], ga[GK], gb[GK], gc[GK], gd[GK];
     float xn[4];
     const v4f zero = {0.f, 0.f, 0.f, 0.f};
+    const stc_dtc::GatePlanes gp{p.g[0], p.g[1], p.g[2], p.g[3], p.g[4], p.h[0]};     // (gates: the planes the gate gradient is re-formed from)
     auto request = [&](long long r) {                                  // one row's planes into registers
         const size_t row16 = (size_t)r * C * DTC_H;
 #pragma unroll
@@ -84,10 +85,8 @@ __global__ __launch_bounds__(DTC_THREADS) void dtc_planar_kernel(DtcPlanes p, co
             const size_t at = row16 + (size_t)(q >> 3) * DTC_H + (size_t)(q & 3) * 4;
             const bool second = (q & 7) >= 4;
             if constexpr (GATES) {
-                ga[k] = *reinterpret_cast<const v4f*>((second ? p.g[3] : p.g[0]) + at);           // dRH : dHnew
-                gb[k] = *reinterpret_cast<const v4f*>(p.h[0] + at);                               // H
-                gc[k] = *reinterpret_cast<const v4f*>((second ? p.g[4] : p.g[2]) + at);           // R : U
-                gd[k] = second ? zero : *reinterpret_cast<const v4f*>(p.g[1] + at);               // Cand (update gate only)
+                const stc_dtc::GatePiece g = stc_dtc::gate_request(gp, at, second);               // dRH : dHnew | H | R : U | Cand
+                ga[k] = g.a, gb[k] = g.b, gc[k] = g.c, gd[k] = g.d;
             } else {
                 ga[k] = *reinterpret_cast<const v4f*>((second ? p.g[1] : p.g[0]) + at);           // dBm : dY
             }
@@ -114,12 +113,7 @@ __global__ __launch_bounds__(DTC_THREADS) void dtc_planar_kernel(DtcPlanes p, co
             const int q = tid + DTC_THREADS * k;
             v4f g;
             if constexpr (GATES) {
-                const bool second = (q & 7) >= 4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float f = second ? gb[k][e] : gd[k][e] - gb[k][e];                      // H : Cand - H
-                    g[e] = ga[k][e] * f * gc[k][e] * (1.f - gc[k][e]);
-                }
+                g = stc_dtc::gate_form(stc_dtc::GatePiece{ga[k], gb[k], gc[k], gd[k]}, (q & 7) >= 4);
             } else {
                 g = ga[k];
             }

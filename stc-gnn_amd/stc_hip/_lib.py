@@ -12,6 +12,7 @@ missing or a tensor is not a ROCm tensor the call fails loudly.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional, Sequence
 
@@ -22,7 +23,7 @@ from .graph import is_full_pattern
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, 'libstc_hip.so')
 # Mirrors of include/stc_hip.h (#define STC_<name>; tests/test_abi.py compares each, and HipKernels.ACT_AMAX_SLOTS, with the header)
-ABI_VERSION = 43
+ABI_VERSION = 44
 FMT_BF16X3, FMT_F16X2 = 0, 1          # operand formats of the split-operand matrix-core kernels
 MAX_K = 4
 STC_ELIMIT = -3            # include/stc_hip.h: a size beyond a kernel limit
@@ -127,6 +128,8 @@ _ABI = {
     'stc_cell_dtc_planar_slots': (_size, [_i64]),
     'stc_cell_dtc_gates_planar_f32': (_int, [_p, _i32] + [_p] * 10 + [_i64, _i32, _p]),
     'stc_cell_dtc_cand_planar_f32': (_int, [_p, _i32] + [_p] * 5 + [_i64, _i32, _p]),
+    'stc_graph_grad_csr_pairs_f32': (_int, [_p, _p, _i32, _i32, _pp, _pp, _pi, _i32, _i32, _p, _p]),
+    'stc_cell_dsx_narrow_planar_f32': (_int, [_p] * 9 + [_i32, _i64, _i32, _p]),
     'stc_mix_grad_f32': (_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _p]),
     'stc_mixed_fusion_workspace_bytes': (_size, [_i32, _i32]),
     'stc_mixed_fusion_fwd_f32': (_int, [_p] * 8 + [_i32, _p]),
@@ -970,6 +973,55 @@ class HipKernels:
         R, Cc, cin = self._dtc_checked('cell_dtc_cand', X, (RH, dY, dBm), Wc, 16, partials)
         self._launch('stc_cell_dtc_cand_planar_f32', RH, _ptr(X), cin, _ptr(RH), _ptr(Wc), _ptr(dY), _ptr(dBm), _ptr(partials), R, Cc,
                      nbytes=4 * R * Cc * (cin + 3 * 16))
+
+    # ---- the value gradient of a learned sparse spatial graph from the planar cells (ABI v44) ----
+    #: ``graph_grad_csr_pairs`` / ``cell_dsx_narrow`` exist: what ``ops._dval_route`` asks before the general executor differentiates ``op.fwd_val``
+    #: (on the class, so ``for_graph`` views have it; the CPU twin has no such attribute and keeps the per-cell route)
+    cell_graph_vals = True
+    GRAPH_GRAD_PAIRS_MAX, GRAPH_GRAD_PAIRS_MAX_F = 3, 1024
+
+    def graph_grad_csr_pairs(self, rowptr, colidx, pairs, N, acc):
+        """``acc`` (nnz,) float64 += the sum over ``pairs`` = [(A, B)], 1 to 3 of them, of the sampled product of ``graph_grad_csr``:
+        entry e of row i takes sum_b < A[b, i], B[b, colidx[e]] > with A, B (batch, N, ...) read as (batch, N, F) planes, F = the floats of one
+        node (a multiple of 4 up to 1024; each pair its own).  One launch (``stc_graph_grad_csr_pairs_f32``); nothing but ``acc`` is written."""
+        if not 1 <= len(pairs) <= self.GRAPH_GRAD_PAIRS_MAX:
+            raise StcError(f'graph_grad_csr_pairs: {len(pairs)} pairs, the kernel takes 1 to {self.GRAPH_GRAD_PAIRS_MAX}')
+        batch = pairs[0][0].shape[0]
+        widths = []
+        for i, (A, Bm) in enumerate(pairs):
+            _tensor(f'graph_grad_csr_pairs.A[{i}]', A)
+            _tensor(f'graph_grad_csr_pairs.B[{i}]', Bm, A.shape)
+            if A.dim() < 3 or A.shape[0] != batch or A.shape[1] != N:
+                raise StcError(f'graph_grad_csr_pairs: plane {i} has shape {tuple(A.shape)}, expected ({batch}, {N}, ...)')
+            F = math.prod(A.shape[2:])
+            if F % 4 or not 4 <= F <= self.GRAPH_GRAD_PAIRS_MAX_F:
+                raise StcError(f'graph_grad_csr_pairs: plane {i} has {F} floats per node, a multiple of 4 in [4, {self.GRAPH_GRAD_PAIRS_MAX_F}] is needed')
+            widths.append(F)
+        self._i32('graph_grad_csr_pairs.rowptr', rowptr, N + 1)
+        self._i32('graph_grad_csr_pairs.colidx', colidx)
+        nnz = colidx.numel()
+        _tensor('graph_grad_csr_pairs.acc', acc, (nnz,), torch.float64)
+        self._same_device(acc, rowptr, colidx, *[t for pr in pairs for t in pr])
+        n = len(pairs)
+        ap, bp = (_p * n)(*[A.data_ptr() for A, _ in pairs]), (_p * n)(*[Bm.data_ptr() for _, Bm in pairs])
+        self._launch('stc_graph_grad_csr_pairs_f32', acc, rowptr.data_ptr(), colidx.data_ptr(), N, nnz, ap, bp, (_i32 * n)(*widths), n, batch, acc.data_ptr(),
+                     nbytes=8 * batch * N * sum(widths))
+
+    def cell_dsx_narrow(self, H, Wg, Tc, U, Rg, Cand, dHnew, dRH, dSx):
+        """The d(S.x) plane (rows, C, cin) of a planar cell with a narrow input, cin = 1..4, WRITTEN to ``dSx`` (stc_cell_dsx_narrow_planar_f32):
+        the gate gradient re-formed in registers as ``cell_dtc_gates`` does, through Wg's blocks of the aggregated input columns and T_c[1]."""
+        R, Cc, h = H.shape
+        cin = dSx.shape[-1]
+        if Cc not in (32, 64) or h != 16 or not 1 <= cin <= 4:
+            raise StcError(f'cell_dsx_narrow: C in (32, 64), hidden 16, input plane 1..4 columns wide; got C={Cc} h={h} cin={cin}')
+        for i, t in enumerate((H, U, Rg, Cand, dHnew, dRH)):
+            _tensor(f'cell_dsx_narrow.plane[{i}]', t, (R, Cc, h))
+        _tensor('cell_dsx_narrow.Wg', Wg, (4 * (cin + h), 2 * h))
+        _tensor('cell_dsx_narrow.Tc', Tc, (2, Cc, Cc))
+        _tensor('cell_dsx_narrow.dSx', dSx, (R, Cc, cin))
+        self._same_device(H, Wg, Tc, U, Rg, Cand, dHnew, dRH, dSx)
+        self._launch('stc_cell_dsx_narrow_planar_f32', H, _ptr(H), _ptr(Wg), _ptr(Tc), _ptr(U), _ptr(Rg), _ptr(Cand), _ptr(dHnew), _ptr(dRH), _ptr(dSx), cin, R, Cc,
+                     nbytes=4 * R * Cc * (6 * 16 + cin))
 
     # ---- the whole backward of a planar cell step in one launch ----------------------------------------
     def cell_bwd_planar_supported(self, Cc, h) -> bool:

@@ -539,6 +539,7 @@ _SMALL = True            # small graphs (N*C rows per sample fit the caches, C <
 _RING2 = True            # state gradient + transpose aggregation of dY in one launch where the graph has a two-ring plan (no dY plane)
 _RING2_FWD = True        # ... and the forward's blend + aggregation of the new state (stc_ring2_blend_f32)
 _DTC = True              # a learned category graph on a fixed sparse spatial graph inside this executor: dT_c from the planar cells (``learn_Tc=``; False: one node per cell)
+_DVAL = True             # a learned spatial graph on a sparse pattern inside this executor, where the caller asked (``op.sampled_grad``): its value gradient from the planar cells (False: one node per cell)
 _FIRST_STEP = True       # cells on the zero initial state (a layer's first time step) in their first-step forms: no H, S.H, R planes, no dH, dS.H
 _SUM_GATHERS, _CHAIN_FIRST_ADD = 2, 2     # kernel limits, not switches: planes that stc_spmm_sum_* / the two-ring launches gather through S (X, X2); first-ring addends of stc_ring2_chain_f32
 
@@ -554,9 +555,9 @@ def _first_step_kernels(k, dtype, C: int, h: int) -> bool:
 def first_step_route(op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widths, dtype=torch.float32, learn_Tc: bool = False) -> bool:
     """Whether ``stc_cell_graph`` runs the PLANAR_ONE_BWD cells of this problem whose state is a zero initial state in their first-step forms
     (fp32 planes, order 2, a kernel set with ``first_step_cells``, not the few-category executor): the caller then passes ``zero_state`` views
-    instead of planes of zeros.  Never while the executor differentiates ``Tc`` (``learn_Tc``): its cells are PLANAR, which has no such form."""
+    instead of planes of zeros.  Never while the executor differentiates ``Tc`` (``learn_Tc``) or the spatial values (``_dval_route``): its cells are PLANAR, which has no such form."""
     k = kernels()
-    if _learns_tc(learn_Tc, Tc):
+    if _learns_tc(learn_Tc, Tc) or _dval_route(k, op, Tc, Ks, C, h, x_widths, dtype):
         return False
     return Ks == 2 and _first_step_kernels(k, dtype, C, h) and not (_SMALL and small_graph_supported(k, op, Tc, Ks, C, h, x_widths, dtype))
 
@@ -580,13 +581,26 @@ def _learns_tc(learn_Tc: bool, Tc) -> bool:
     return bool(learn_Tc and torch.is_grad_enabled() and Tc.requires_grad)
 
 
+def _dval_route(k, op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widths, dtype) -> bool:
+    """Whether the general executor forms the value gradient of a learned spatial graph for this problem: the switch, the caller's word
+    (``op.sampled_grad``: ``STCGNN(csr_cells='fused')``), values that require grad in grad mode, a sparse pattern (the full pattern is the dense
+    learned graph), fp32 planes, Ks = Kc = 2, hidden 16, C in {32, 64}, every input 16 or 1..4 columns wide, a kernel set with
+    ``cell_graph_vals``, every cell in ``_Form.PLANAR`` (the two-launch backward, in which dS.X, dS.H and dY exist as planes)."""
+    widths = sorted(set(x_widths))
+    return bool(_DVAL and op.sampled_grad and torch.is_grad_enabled() and op.fwd_val.requires_grad and op.nnz != op.n * op.n
+                and dtype == torch.float32 and Ks == 2 and Tc.shape[0] == 2 and h == 16 and C in (32, 64)
+                and all(w == h or 1 <= w <= 4 for w in widths) and getattr(k, 'cell_graph_vals', False)
+                and all(f is _Form.PLANAR for f in _cell_forms(k, Ks, 2, C, h, widths, False, learn_Tc=True)))
+
+
 def _dtc_route(k, op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widths, dtype) -> bool:
     """Whether the general executor can differentiate ``Tc`` for this problem (``stc_cell_graph(learn_Tc=True)``): the switch, fp32 planes,
     order 2, a kernel set with the planar cells' dT_c kernels that takes every input width, every cell in ``_Form.PLANAR`` (the two-launch
-    backward, in which dY, dBm and dRH exist), a spatial graph that needs no gradient."""
+    backward, in which dY, dBm and dRH exist), a spatial graph that needs no gradient -- or whose value gradient the same backward forms
+    (``_dval_route``)."""
     widths = sorted(set(x_widths))
     return bool(_DTC and dtype == torch.float32 and Ks == 2 and Tc.shape[0] == 2 and getattr(k, 'cell_dtc_planar', False)
-                and not op.fwd_val.requires_grad and all(k.cell_dtc_planar_supported(C, w, h) for w in widths)
+                and (not op.fwd_val.requires_grad or _dval_route(k, op, Tc, Ks, C, h, x_widths, dtype)) and all(k.cell_dtc_planar_supported(C, w, h) for w in widths)
                 and all(f is _Form.PLANAR for f in _cell_forms(k, Ks, 2, C, h, widths, False, learn_Tc=True)))
 
 
@@ -594,7 +608,8 @@ def cell_graph_supported(op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widt
     """Whether ``stc_cell_graph`` can run a schedule: matrix-core cell kernels for every row width that occurs, hidden 16,
     graphs that need no gradient (``csr-fixed`` mode).  ``dtype`` = storage type of the state tensors: bfloat16 runs the
     all-planar bf16 kernel set (Ks = Kc = 2; inputs 16 or 1..4 columns wide).  ``learn_Tc``: the caller wants the gradient of a ``Tc`` that
-    requires grad from the general executor (``graph_mode='csr-category-learned'``); the answer is then ``_dtc_route``'s."""
+    requires grad from the general executor (``graph_mode='csr-category-learned'``); the answer is then ``_dtc_route``'s.  Spatial values that
+    require grad are taken only on an operand with ``sampled_grad`` and only where ``_dval_route`` holds."""
     if not _CELL_GRAPH or h != 16:
         return False
     k = kernels()
@@ -602,6 +617,8 @@ def cell_graph_supported(op: SpatialOperand, Tc, Ks: int, C: int, h: int, x_widt
         return True                                                   # small graphs, fixed or learned: one launch per cell step (stc_hip/small.py)
     if _learns_tc(learn_Tc, Tc):
         return _dtc_route(k, op, Tc, Ks, C, h, x_widths, dtype)
+    if not Tc.requires_grad and _dval_route(k, op, Tc, Ks, C, h, x_widths, dtype):
+        return True                                                   # a learned sparse spatial graph alone (``csr_cells='fused'``, frozen category generator)
     if Tc.requires_grad or op.fwd_val.requires_grad:
         return False
     if dtype == torch.bfloat16:
@@ -621,12 +638,12 @@ class _Form(enum.Enum):
     saves (H, U, R, Cand) for backward and then, in this order:"""
     PLANAR3 = 'order-3 planar'          # Zx[0..2], Zh[1..2], Zr[0..2]: gates and slab-planar candidate on three Chebyshev planes per side
     PLANAR_ONE_BWD = 'planar, one-launch backward'     # X, S.X, S.H: the backward re-forms R*H, which is never stored
-    PLANAR = 'planar'                   # X, S.X, S.H, R*H: node_post backward of the candidate, then the planar gates backward
+    PLANAR = 'planar'                   # X, S.X, S.H, R*H[, Bm]: node_post backward of the candidate, then the planar gates backward (Bm: only while the spatial values are learned)
     ROWS_POST = 'rows, post-aggregation'   # Zg[0..Ks-1], CandIn: interleaved [Xt | H | 0] rows, candidate as Y = A + S.Bm (Ks = 2)
     ROWS_SLABS = 'rows, slabs'          # Zg[0..Ks-1], Zc[0..Ks-1]: interleaved rows, candidate convolution on its Chebyshev slabs
 
-    def saved(self, Ks: int) -> int:
-        return 4 + {'PLANAR3': 8, 'PLANAR_ONE_BWD': 3, 'PLANAR': 4, 'ROWS_POST': Ks + 1, 'ROWS_SLABS': 2 * Ks}[self.name]
+    def saved(self, Ks: int, vals: bool = False) -> int:            # vals: the value gradient is formed (``_dval_route``) -- PLANAR also keeps Bm
+        return 4 + {'PLANAR3': 8, 'PLANAR_ONE_BWD': 3, 'PLANAR': 5 if vals else 4, 'ROWS_POST': Ks + 1, 'ROWS_SLABS': 2 * Ks}[self.name]
 
     @property
     def planar(self) -> bool:
@@ -687,11 +704,12 @@ class _ForwardPass(_Pass):
     """... and, in the forward, the new states, the input rows of the interleaved cells and the aggregations of every source tensor (formed
     once for all the planar cells that consume it)."""
 
-    def __init__(self, k, op: SpatialOperand, Ks: int, Tc, fwd_val, schedule, ext, cin, forms, bf16: bool, forward_only: bool = False):
+    def __init__(self, k, op: SpatialOperand, Ks: int, Tc, fwd_val, schedule, ext, cin, forms, bf16: bool, forward_only: bool = False, keep_bm: bool = False):
         # (forward only: no backward will read the maxima -- no buffer, and the launches get no slots to fill)
         zmax_all = k.act_amax_buffer(ext[0], len(schedule), 2, 2 * Ks) if (not forward_only and not bf16 and any(f.planar for f in forms)) else None   # (one zero fill)
         super().__init__(k, op, Ks, Tc, schedule, cin, forms, ext[0].shape[:3], bf16, zmax_all, (op.fwd_rowptr, op.fwd_colidx, fwd_val, op.fwd_plan))
         self.fwd_val, self.ext = fwd_val, ext
+        self.keep_bm = keep_bm                                      # the backward forms the spatial values' gradient: PLANAR cells save the candidate's Bm plane
         self.state = [None] * len(schedule)                         # plain (B,N,C,h) new state of every cell
         self.XH, self.agg = {}, {}
         self.consumers = [[] for _ in schedule]
@@ -811,7 +829,7 @@ class _ForwardPass(_Pass):
             self.agg[('cell', j)] = SHn
         else:                                                       # (the row-blocked blend reads a plane of zeros: built here only)
             k.spmm_blend_fwd(*self.graph, Bm, A, U, self.source(hs) if first else Hprev, Cand, Hnew, copies=copies, side=side)
-        return [Xp, SXp, SHp] + ([] if RH is None else [RH])
+        return [Xp, SXp, SHp] + ([] if RH is None else [RH]) + ([Bm] if self.keep_bm else [])
 
     def rows_cell(self, j, Wg, bg, Wc, bc, Hprev, U, Rg, Cand, Hnew, copies, side):
         """ROWS_POST and ROWS_SLABS: gates convolution on the Chebyshev slabs of the [Xt | H | 0] rows, gate math in its epilogue."""
@@ -947,10 +965,12 @@ class _BackwardPass(_Pass):
     """... and, in the backward, what every state is still owed (``owes``: one ``_Ledger`` record per state, filled by its consumers through ``finish`` /
     ``leave`` / ``claim``, emptied by ``owed`` / ``owed_ring2`` when its own cell runs) and the parameter gradients (``params``: ``_ParamGrads``)."""
 
-    def __init__(self, k, op: SpatialOperand, Ks: int, Tc, schedule, stacks, cin, forms, dims, bf16: bool, zmax_all, learn_Tc: bool = False):
+    def __init__(self, k, op: SpatialOperand, Ks: int, Tc, schedule, stacks, cin, forms, dims, bf16: bool, zmax_all, learn_Tc: bool = False, learn_val: bool = False):
         super().__init__(k, op, Ks, Tc, schedule, cin, forms, dims, bf16, zmax_all, (op.bwd_rowptr, op.bwd_colidx, op.bwd_val, op.bwd_plan))
         # a learned category graph: every PLANAR cell's two dT_c launches ADD into one float64 buffer, zeroed here, folded once (``_dtc_fold``)
         self.dtc = torch.zeros(k.cell_dtc_slots(self.B * self.N), self.C, self.C, dtype=torch.float64, device=Tc.device) if learn_Tc else None
+        # a learned sparse spatial graph: every PLANAR cell's launch ADDS its share of dval, in ``fwd_val``'s order, to one float64 buffer (stc_graph_grad_csr_pairs_f32)
+        self.dval = torch.zeros(op.nnz, dtype=torch.float64, device=Tc.device) if learn_val else None
         # state gradient sums fused with a transpose aggregation where the graph has a two-ring plan (stc_ring2_sum_f32 / _chain_f32)
         self.ring2 = _RING2 and not bf16 and op.bwd_ring2 is not None and k.ring2_fits(self.B, self.N, self.C, self.h)
         self.owes, self.params = _Ledger(), _ParamGrads(stacks, schedule)
@@ -1054,7 +1074,7 @@ class _BackwardPass(_Pass):
 
     def planar(self, j, Wg, bg, Wc, bc, saved):
         k, rows, Tc, (s_id, x, hs) = self.k, self.rows, self.Tc, self.schedule[j]
-        Hprev, U, Rg, Cand, Xp, SXp, SHp, RH = saved
+        Hprev, U, Rg, Cand, Xp, SXp, SHp, RH, *Bm = saved            # (Bm: saved only while the spatial values are learned)
         dHnew, dY = self.owed(j, (U, Cand))
         wide = self.cin[j] == self.h                                # else: narrow input plane (layer 0), which needs no gradient
         # the candidate's input planes are (X, R*H): X's maximum as the gates forward left it, R*H rides on H's (|R*H| <= |H|).  Slot
@@ -1076,9 +1096,17 @@ class _BackwardPass(_Pass):
         if self.dtc is not None:                                    # dT_c while the planes are alive: dY, dBm here, dRH as the launch above left it
             k.cell_dtc_cand(*rows((Xp, RH)), Wc, *rows((dY, dBm)), self.dtc)
             k.cell_dtc_gates(*rows((Xp, Hprev, SXp, SHp)), Wg, *rows((U, Rg, Cand, dHnew, dRH)), self.dtc)
-        del dY, dBm
+        del dBm
+        if self.dval is None:
+            del dY
         # (dH = None: the kernel adds the prologue's share into the H plane's gradient)
         k.cell_gates_bwd_planar(*rows((Xp, Hprev, SXp, SHp)), Tc, Wg, *rows((dRH, Cand, U, Rg, dHnew)), planes, dWg, dbg, None, **gates_kw)
+        if self.dval is not None:
+            # the cell's three applications of S -- S.X, S.H, A + S.Bm -- in one launch: dval[e = (i, j)] += <dS.X[i], X[j]> + <dS.H[i], H[j]> + <dY[i], Bm[j]>
+            if not wide:                                            # the gates backward forms no d(S.x) plane for a narrow input, which needs no gradient
+                dSX = Xp.new_empty(Xp.shape)
+                k.cell_dsx_narrow(*rows((Hprev,)), Wg, Tc, *rows((U, Rg, Cand, dHnew, dRH, dSX)))
+            k.graph_grad_csr_pairs(self.op.fwd_rowptr, self.op.fwd_colidx, [(dSX, Xp), (dSH, Hprev), (dY, Bm[0])], self.N, self.dval)
         if wide and x[0] == 'cell':
             self.owes.leave(x[1], [dXd, dXc], [dSX])                # as the X plane: gates' and candidate's direct shares
         if hs[0] == 'cell':
@@ -1127,7 +1155,8 @@ def _dtc_fold(partials, Tc):
     return dTc
 
 
-def _begin_forward(op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, tensors, forward_only: bool = False, learn_Tc: bool = False):
+def _begin_forward(op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, tensors, forward_only: bool = False, learn_Tc: bool = False,
+                   learn_val: bool = False):
     """What both routes of ``stc_cell_graph`` do before the first launch: kernel set, contiguous operands, one form per cell, the output stack.
     Returns (pass, parameter sets, output stack, output cell -> slot)."""
     k = kernels().for_graph(_amplification(op, Ks))              # (a heavy graph: the 24-bit operand format, _lib.HEAVY_ROW_SUM)
@@ -1139,10 +1168,10 @@ def _begin_forward(op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, T
     h = 16
     B, N, C = ext[0].shape[:3]
     cin = [ext[x[1]].shape[-1] if x[0] == 'ext' else h for _, x, _ in schedule]
-    forms = _cell_forms(k, Ks, Tc.shape[0], C, h, cin, bf16, learn_Tc)
+    forms = _cell_forms(k, Ks, Tc.shape[0], C, h, cin, bf16, learn_Tc or learn_val)      # (the value gradient needs the planes of the two-launch backward as well)
     if bf16 and not all(f.planar for f in forms):
         raise ValueError('stc_cell_graph: bfloat16 states need an all-planar schedule (Ks = 2, inputs 16 or 1..4 columns wide)')
-    p = _ForwardPass(k, op, Ks, Tc, fwd_val, schedule, ext, cin, forms, bf16, forward_only)
+    p = _ForwardPass(k, op, Ks, Tc, fwd_val, schedule, ext, cin, forms, bf16, forward_only, keep_bm=learn_val)
     out_stack = ext[0].new_empty(len(outputs), B, N, C, h)      # the requested states are produced in place, stacked
     return p, stacks, out_stack, _out_slots(outputs)
 
@@ -1182,7 +1211,8 @@ class _StcCellGraph(Function):
     @staticmethod
     def forward(ctx, op: SpatialOperand, Ks: int, schedule, outputs, n_ext: int, Tc, fwd_val, *tensors):
         learn_Tc = ctx.needs_input_grad[5]                           # (``stc_cell_graph`` lets a ``Tc`` that requires grad through only with ``learn_Tc``)
-        p, stacks, out_stack, out_slot = _begin_forward(op, Ks, schedule, outputs, n_ext, Tc, fwd_val, tensors, learn_Tc=learn_Tc)
+        learn_val = ctx.needs_input_grad[6]                          # (... and values that require grad only where ``_dval_route`` holds)
+        p, stacks, out_stack, out_slot = _begin_forward(op, Ks, schedule, outputs, n_ext, Tc, fwd_val, tensors, learn_Tc=learn_Tc, learn_val=learn_val)
         saved = []
         for j, (s_id, _, _) in enumerate(schedule):
             saved += p.cell(j, stacks[s_id], _alias(out_stack, out_slot[j]) if j in out_slot else None)
@@ -1204,10 +1234,10 @@ class _StcCellGraph(Function):
         Tc, *sv = ctx.saved_tensors
         stacks, sv = _stacks(sv[:4 * n_sets]), sv[4 * n_sets:]
         cells = []
+        learn_Tc, learn_val = ctx.needs_input_grad[5], ctx.needs_input_grad[6]
         for f in forms:                                              # what each cell saved, by its form
-            cells, sv = cells + [sv[:f.saved(Ks)]], sv[f.saved(Ks):]
-        learn_Tc = ctx.needs_input_grad[5]
-        p = _BackwardPass(k, op, Ks, Tc, schedule, stacks, cin, forms, dims, bf16, ctx.zmax_all, learn_Tc)
+            cells, sv = cells + [sv[:f.saved(Ks, learn_val)]], sv[f.saved(Ks, learn_val):]
+        p = _BackwardPass(k, op, Ks, Tc, schedule, stacks, cin, forms, dims, bf16, ctx.zmax_all, learn_Tc, learn_val)
         grad_stack = _c(grad_stack)
         for i, j in enumerate(outputs):
             p.owes.finish(j, grad_stack[i])                          # read-only here: sums go to fresh buffers
@@ -1217,7 +1247,8 @@ class _StcCellGraph(Function):
             getattr(p, _FORM_METHODS[forms[j]][1])(j, *stacks[schedule[j][0]], cells[j])
         flat = p.params.result()
         n_ext = len(ctx.needs_input_grad) - 7 - len(flat)
-        return (None,) * 5 + (_dtc_fold(p.dtc, Tc) if learn_Tc else None, None) + (None,) * n_ext + tuple(flat)
+        dval = p.dval.to(op.fwd_val.dtype) if learn_val else None    # (in ``fwd_val``'s order: the pattern the launches walked is the forward CSR)
+        return (None,) * 5 + (_dtc_fold(p.dtc, Tc) if learn_Tc else None, dval) + (None,) * n_ext + tuple(flat)
 
 
 def stc_cell_graph(op: SpatialOperand, Tc, Ks: int, schedule, outputs, ext, stacks, learn_Tc: bool = False):
@@ -1239,19 +1270,31 @@ def stc_cell_graph(op: SpatialOperand, Tc, Ks: int, schedule, outputs, ext, stac
     ``learn_Tc=True`` (``graph_mode='csr-category-learned'``): a ``Tc`` that requires grad is differentiated by the general executor -- fp32
     planes, order 2, C in {32, 64}, every cell in ``_Form.PLANAR``, whose two-launch backward also adds the cell's share of dT_c[1] to one float64
     buffer (``stc_cell_dtc_gates_planar_f32`` / ``_cand_planar_f32``); ``cell_graph_supported(..., learn_Tc=True)`` tells beforehand, a problem
-    outside it raises ``ValueError``.  ``op.fwd_val`` is refused as before.  With the default every answer and refusal is unchanged."""
+    outside it raises ``ValueError``.  ``op.fwd_val`` is refused as before.  With the default every answer and refusal is unchanged.
+
+    A learned SPARSE spatial graph (``graph.learned_csr_operand(..., sampled_grad=True)``: ``STCGNN(graph_mode='csr-learned', csr_cells='fused')``)
+    whose values require grad is differentiated here where ``_dval_route`` holds -- fp32 planes, Ks = Kc = 2, hidden 16, C in {32, 64}, inputs 16
+    or 1..4 columns wide, a kernel set with ``cell_graph_vals``: every cell runs in ``_Form.PLANAR`` and also keeps its Bm plane; its backward
+    adds < dS.X, X > + < dS.H, H > + < dY, Bm > at the stored entries to one float64 buffer (``stc_graph_grad_csr_pairs_f32``, one launch per cell;
+    the d(S.x) plane of a narrow input from ``stc_cell_dsx_narrow_planar_f32``), returned in ``fwd_val``'s order.  With ``learn_Tc`` both graphs
+    are learned in the one node; without ``sampled_grad`` values that require grad are refused as before."""
     ext = list(ext)
     _refuse_differentiable(ext=ext)
     k = kernels()
     if _SMALL and small_graph_supported(k, op, Tc, Ks, ext[0].shape[2], 16, {ext[x[1]].shape[-1] if x[0] == 'ext' else 16 for _, x, _ in schedule},
                                         ext[0].dtype):
         return stc_small_graph(k, op, Tc, Ks, schedule, outputs, ext, stacks)
+    widths = {ext[x[1]].shape[-1] if x[0] == 'ext' else 16 for _, x, _ in schedule}
+    kg = k.for_graph(_amplification(op, Ks))
+    learn_val = _dval_route(kg, op, Tc, Ks, ext[0].shape[2], 16, widths, ext[0].dtype)
     if _learns_tc(learn_Tc, Tc):
-        _refuse_differentiable(fwd_val=op.fwd_val)
-        widths = {ext[x[1]].shape[-1] if x[0] == 'ext' else 16 for _, x, _ in schedule}
-        if not _dtc_route(k.for_graph(_amplification(op, Ks)), op, Tc, Ks, ext[0].shape[2], 16, widths, ext[0].dtype):
+        if not learn_val:
+            _refuse_differentiable(fwd_val=op.fwd_val)
+        if not _dtc_route(kg, op, Tc, Ks, ext[0].shape[2], 16, widths, ext[0].dtype):
             raise ValueError('stc_cell_graph: learn_Tc needs fp32 planes, Chebyshev order 2, C in (32, 64), inputs 16 or 1..4 columns wide and a kernel '
                              'set with the planar dT_c kernels (cell_graph_supported(..., learn_Tc=True) tells beforehand; stc_cell differentiates every input)')
+    elif learn_val:
+        _refuse_differentiable(Tc=Tc)                                # the value route alone
     else:
         _refuse_differentiable(Tc=Tc, fwd_val=op.fwd_val)
     flat = [p for st in stacks for p in st]
